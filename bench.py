@@ -308,7 +308,7 @@ class Job:
         Fn.log_phase("pyramid_end", side)
         reducer.zero_grad()
         Fn.log_phase("grads_cleared", cur)
-        out = model(tf)
+        out = self.last_out = model(tf)
         Fn.log_phase("forward_queued", cur)
         loss = self.cross_entropy(out, self.labels_dev[i % len(batches)])  # the trainer's own loss call (classification_training.py)
         loss.backward()
@@ -340,6 +340,37 @@ class Job:
                 self.model(self.state["tf"])
             torch.cuda.synchronize()
             return (time.perf_counter() - t1) / steps * 1e3
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 18  # elements kept of an array too large to keep whole when everything does not fit
+
+
+def dump_outputs(path, job, loss):
+    """What the timed step hands its caller after the last timed step, as float32 / float64 .npy files under `path`: the loss,
+    the logits and the model's state (parameters after the SGD update, batch-norm running statistics).  When the whole does not
+    fit in DUMP_BYTES, every array of more than DUMP_SAMPLE elements is replaced by the same DUMP_SAMPLE of its flattened
+    elements, chosen by a fixed seed from its size alone."""
+    import numpy as np
+
+    arrays = {"loss": loss.detach(), "logits": job.last_out.detach()}
+    arrays.update(("state." + k, v.detach()) for k, v in job.model.state_dict().items())
+    out = {}
+    for name, t in arrays.items():
+        t = t.cpu()
+        out[name] = (t.double() if t.dtype in (torch.float64, torch.int64) else t.float()).numpy()
+    if sum(a.nbytes for a in out.values()) > DUMP_BYTES:
+        for name, a in out.items():
+            if a.size > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(a.size).choice(a.size, DUMP_SAMPLE, replace=False))
+                out[name] = a.reshape(-1)[idx]
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes after sampling, more than {DUMP_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
 
 
 def layer_table_from(warm, pair_table=None):
@@ -449,6 +480,9 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the `other_configs` leg (BASELINE configs #4 and #3's per-GPU shape, K steps each after the headline)")
     ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write the last timed step's loss, logits and updated model state as DIR/<name>.npy "
+                    "(rank 0; float32 / float64, at most 64 MB in all)")
     ap.add_argument("--timeline", action="store_true", help="after the timed region: print where the phases of a step "
                     "fall on the GPU clock of every stream and when the host queued them (diagnostic)")
     args = ap.parse_args()
@@ -498,7 +532,7 @@ def main():
         os.environ.setdefault("RANK", "0"), os.environ.setdefault("WORLD_SIZE", "1")
     _dummies = []
     if int(os.environ.get("BENCH_DUMMY_STREAMS", "0")) > 0:
-        # measurement hook (scripts/cliff_profile.sh): N idle streams, each used once BEFORE the process group exists, so that the
+        # measurement hook: N idle streams, each used once BEFORE the process group exists, so that the
         # hardware queues the HIP runtime hands out in order of first use are taken and RCCL's stream lands N queues further on
         for _ in range(int(os.environ["BENCH_DUMMY_STREAMS"])):
             st_ = torch.cuda.Stream(device=dev)
@@ -695,6 +729,9 @@ def main():
         prof_.disable()
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        n_ = dump_outputs(args.dump_outputs, job, loss)
+        print(f"[bench] outputs of the last timed step: {n_ / 2 ** 20:.1f} MB under {args.dump_outputs}", file=sys.stderr)
     if prof_ is not None and rank == 0:
         import io
         import pstats
