@@ -31,6 +31,9 @@ _DP_LAUNCH_IN_CALL = os.environ.get("MINK_DP_LAUNCH", "call") != "stream"
 _KEEPALIVE = []  # gradient scratch of the running backward pass: the weight-gradient stream reads it until the final join
 Fn._AFTER_JOIN.append(_KEEPALIVE.clear)
 _ALIGN = 64  # floats: kNetAlign of csrc/trunk.hip (every block's region starts on a 256-byte boundary)
+# Test seam (tests/test_gpu_layerwise.py): keep the backward pass's gradient arena, the trunk's incoming gradient and the gradient
+# that reaches the stem on the node's `saved` (_Saved.grad_stage).  Off: nothing is kept, allocated or synchronised.
+KEEP_GRAD_ARENA = False
 
 
 class _Stage:
@@ -300,21 +303,63 @@ class _Saved:
 
     def __init__(self, stem, arena, rows, tables, plan):
         self.stem, self.arena, self.rows, self.tables, self.plan = stem, arena, rows, tables, plan
+        self.g_buf = self.g_out = self.g_stem_out = None  # (KEEP_GRAD_ARENA: filled by the backward pass)
 
     def __len__(self):
         return 1 + len(self.plan.stages)
 
-    def _stage(self, i):
+    def _offset(self, i):
+        """(offset, activation floats) of block i's region of the arena."""
         off = 0
         for j, st in enumerate(self.plan.stages):
-            n_out = self.rows[st.level]
-            width = (6 if st.down is not None else 4) * n_out * st.C
+            width = (6 if st.down is not None else 4) * self.rows[st.level] * st.C
             if j == i:
-                lv_in = st.level - (st.stride == 2)
-                t = self.tables[st.level]
-                return (self.arena[off : off + width], t[1] if st.stride == 2 else t[0], t[0], t[2] if st.stride == 2 else None,
-                        2 << lv_in, 2 << st.level, self.rows[lv_in], n_out)
+                return off, width
             off += _align(width) + _align(6 * st.C)
+        raise IndexError(i)
+
+    def _stage(self, i):
+        off, width = self._offset(i)
+        st = self.plan.stages[i]
+        lv_in = st.level - (st.stride == 2)
+        t = self.tables[st.level]
+        return (self.arena[off : off + width], t[1] if st.stride == 2 else t[0], t[0], t[2] if st.stride == 2 else None,
+                2 << lv_in, 2 << st.level, self.rows[lv_in], self.rows[st.level])
+
+    def stats(self, i):
+        """Block i's batch statistics: [C] views (mean1, invstd1, mean2, invstd2, meand, invstdd) -- the last two unwritten
+        without a shortcut convolution."""
+        off, width = self._offset(i)
+        C = self.plan.stages[i].C
+        s = self.arena[off + _align(width) : off + _align(width) + 6 * C]
+        return tuple(s[j * C : (j + 1) * C] for j in range(6))
+
+    def grad_stage(self, i):
+        """Block i's part of the kept gradient arena (KEEP_GRAD_ARENA; layout: block_backward_impl and mink_net_backward of
+        csrc/trunk.hip, the LAST block first): a dict of [rows, channels] views g_y2, g_res, g_h1, g_y1, then g_xa (identity
+        shortcut; unwritten when the block left its input gradient to the block before it) or g_yd, g_sc (shortcut
+        convolution), and g_x (the block's input gradient; the stem's incoming gradient for block 0)."""
+        if self.g_buf is None:
+            raise RuntimeError("no gradient arena kept: set trunk.KEEP_GRAD_ARENA before the backward pass")
+        goff = 0
+        for j in range(len(self.plan.stages) - 1, -1, -1):
+            st = self.plan.stages[j]
+            down = st.down is not None
+            n_out, n_in = self.rows[st.level], self.rows[st.level - (st.stride == 2)]
+            gtmp = _align((4 + down) * n_out * st.C + (n_out if down else n_in) * st.cin + 64)
+            if j == i:
+                g = self.g_buf[goff:]
+                no = n_out * st.C
+                names = ["g_y2", "g_res", "g_h1", "g_y1"] + (["g_yd"] if down else [])
+                v = {k: g[q * no : (q + 1) * no].view(n_out, st.C) for q, k in enumerate(names)}
+                p = len(names) * no
+                if down:
+                    v["g_sc"] = g[p : p + n_out * st.cin].view(n_out, st.cin)
+                else:
+                    v["g_xa"] = g[p : p + n_in * st.cin].view(n_in, st.cin)
+                v["g_x"] = g[gtmp : gtmp + n_in * st.cin].view(n_in, st.cin)
+                return v
+            goff += gtmp + _align(n_in * st.cin)
         raise IndexError(i)
 
     def __getitem__(self, i):
@@ -533,6 +578,10 @@ class TrunkFunction(torch.autograd.Function):
         if Fn._TIMING_MODE == 1:
             Fn.note_table(nbr0, *[t for ts_ in tables for t in ts_], *bwd_tables)
         _KEEPALIVE.append((g_buf, g_out, flat, gw_pad, bwd_tables))  # (never the gradients handed to autograd: a second reference makes it clone them at once)
+        if KEEP_GRAD_ARENA:
+            saved.g_buf, saved.g_out = g_buf, g_out
+            saved.g_stem_out = saved.grad_stage(0)["g_x"]
+            assert saved.g_stem_out.data_ptr() == plan.net.g_stem_out, "gradient arena layout differs from mink_net_backward's"
         if in_call:
             sink.flush()
             for i in range(3):

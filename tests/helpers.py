@@ -73,3 +73,96 @@ def host_threads(cap=16):
         except (OSError, ValueError, IndexError):
             continue
     return max(1, min(cap, n))
+
+
+# ---- the bench's training step at full size and what the parity tests read back from it (tests/test_gpu_parity_full.py,
+# tests/test_gpu_layerwise.py)
+def _baseline_batch(batch=16, grid=128, cin=28):
+    from nerf_downstream_amd.co3d_3d.src.data.synthetic import SparseVoxelDataset
+    from nerf_downstream_amd.co3d_3d.src.data.utils import collate_mink
+
+    ds = SparseVoxelDataset(phase="train", num_samples=1 << 20, num_classes=51, grid=grid, features=["density", "sh"])
+    return collate_mink([ds[i] for i in range(batch)])  # exactly bench.py's first batch
+
+
+def _bench_like_step(hip, batch, labels, passes=3):
+    """The training step exactly as bench.py queues it: flat gradient buffer as the gradient sink of the backward kernels,
+    coordinate pyramid launched ahead (defer=True) and finished after the previous pass, map plan replayed on the prepare
+    stream (so the shortcut branch forks onto its own stream and the weight gradients run on theirs).  The first pass
+    records the plan, the second runs while the third batch's maps are replayed from it (the pyramid of pass p+1 is
+    launched before forward p, as in bench.py, so it takes two passes to reach the steady state); gradients and logits
+    are those of the LAST pass (train-mode batch norm: neither depends on the
+    running statistics that move between passes)."""
+    import torch
+    import torch.nn.functional as F
+
+    from nerf_downstream_amd.parallel import BucketedGradAllReduce
+
+    reducer = BucketedGradAllReduce(hip)
+    tf = hip.process_input(batch)
+    out = field = None
+    for p in range(passes):
+        nxt = hip.process_input(batch, defer=True) if p + 1 < passes else None
+        reducer.zero_grad()
+        field = tf
+        out = hip(tf)
+        F.cross_entropy(out, labels).backward()
+        if nxt is not None:
+            tf = hip.finish_input(nxt)
+        reducer.finish()
+    torch.cuda.synchronize()
+    return out, field, reducer
+
+
+def _stem_masks_of_hip_run(out, model):
+    """The stem ReLU's branch decisions as the HIP backward kernels take them.  The trunk keeps only the POOLED sum of the
+    stem's ReLU output, so its backward kernels recompute z = gamma * xhat + beta from the kept convolution output y and
+    the batch's (mean, 1 / std) -- and the two kernels that do so round xhat differently (both are valid fp32):
+      * gamma / beta gradients (csrc/elementwise.hip, colreduce / bn_relu_pool_bwd_kernel; also the forward's own
+        decision):                      xhat = fl(fl(y - mean) * invstd),        z = fma(xhat, gamma, beta)
+      * the weight gradient (csrc/conv.hip, wgrad_stream_kernel<.., FUSE>): xhat = fma(y, invstd, fl(-mean * invstd)), z = fma(xhat, gamma, beta)
+    Both are reproduced here in exact fp32 arithmetic on the CPU (an fma through float64: the product of two floats is exact
+    there).  -> (mask for bn1.*, mask for conv1.kernel), each [n0, C0] bool."""
+    import torch
+
+    node = trunk_node(out)
+    x, w0, arena0, nbr0, nbr_pool, i2o, pad, b16, _ = node.saved[0]
+    n0, n1, C0 = x.shape[0], nbr_pool.shape[0], w0.shape[-1]
+    a = arena0.detach().cpu()
+    ny = a.numel() - n1 * C0 - 2 * C0  # floats of the y (+ bf16 input copy) region (minkowski/trunk.py)
+    if b16:  # bf16 storage: y is kept as bf16 [n0][C0] at the head of the arena; the kernels widen it and go on in fp32
+        y = a[: n0 * C0 // 2].view(torch.bfloat16).view(n0, C0).float()
+    else:
+        assert ny == n0 * C0
+        y = a[: n0 * C0].view(n0, C0)
+    mean, invstd = a[ny + n1 * C0 : ny + n1 * C0 + C0], a[ny + n1 * C0 + C0 : ny + n1 * C0 + 2 * C0]
+    ga, be = model.bn1.bn.weight.detach().cpu(), model.bn1.bn.bias.detach().cpu()
+
+    def fma(p, q, r):
+        return (p.double() * q.double() + r.double()).float()
+
+    xh_bn = (y - mean) * invstd
+    xh_w = fma(y, invstd, -mean * invstd)
+    return fma(xh_bn, ga, be) > 0, fma(xh_w, ga, be) > 0
+
+
+def _bf16_operands(storage):
+    """oracle.me_cpu.OPERAND_HOOK for BASELINE config #4: every convolution GEMM operand rounded to bf16 (round to nearest even, what
+    `(__bf16)v` and the MFMA packers of csrc/conv.hip / stem16.hip do) exactly where the HIP path rounds it -- forward: rows and
+    weights; data gradient: dY and weights, EXCEPT the 1x1x1 strided shortcut, whose data gradient is the exact-fp32 dense GEMM
+    mink_dense_xwt (csrc/trunk.hip); weight gradient: rows and dY.  `storage`: the stem's convolution output is also STORED as
+    bf16 (set_conv_storage("bf16")): its forward value is rounded, the gradient passes unchanged."""
+    import torch
+
+    def rnd(t):
+        return t.to(torch.bfloat16).to(t.dtype)
+
+    def hook(t, role, shape):
+        K, cin = shape[0], shape[1]
+        if role == "fwd_y":
+            return rnd(t) if storage and K == 27 and cin <= 32 else t
+        if role.startswith("dgrad") and K == 1:
+            return t
+        return rnd(t)
+
+    return hook

@@ -1,0 +1,317 @@
+"""Teacher-forced, operator-by-operator float64 references of the Mink-ResNet trunk, and the comparators that judge a kernel's
+output against them (tests/test_gpu_layerwise.py on the GPU, tests/test_layerwise_cpu.py for the negative controls).
+
+Every reference is plain torch float64 on whatever device its inputs are on, fed with the operands the kernel itself read
+(the HIP run's own stored activations, gradients, statistics and ReLU decisions): no error carries over from one layer to
+the next, so each operator is held to what its own kernel test holds it to.
+
+Tables are the trunk's: nbr[n_out, K] = input row of output row o at offset k, or -1 (oracle/maps.py kernel_map_table);
+weights are [K, cin, cout]."""
+from dataclasses import dataclass
+
+import torch
+
+# ---------------------------------------------------------------------------------------------------------- bounds
+CONV_REL = 2e-5  # relative L2 per tensor (tests/test_gpu_ops.py)
+CONV_MAX = 1e-4  # max |err| / max |ref|: one bad row or element cannot hide in the norm
+NORM_BOUND = 1e-5  # batch-norm quantities, relative to their scale (fp32 rounding only)
+FLIP_Z = 1e-4  # a ReLU branch may differ from float64's own only where |z| <= FLIP_Z * sd(z)
+STORE_MAX = 2e-5  # bf16-stored values: half a bf16 ulp of the float64 value + STORE_MAX * max |ref|
+# "declared vs other" is asserted where the two rounding references sit more than DISCRIMINATE bounds apart.  Rounding one
+# operand to bf16 moves a product by 2^-9 / sqrt(3) = 1.1e-3 relative (RMS): 100 bounds (2e-3) would sit above that separation
+# and skip the check almost everywhere; 20 (4e-4) still leaves a kernel within the bound of one reference 19 bounds from the other.
+DISCRIMINATE = 20.0
+
+
+# ------------------------------------------------------------------------------------------------ rounding table
+def bf16_rne(t):
+    """Round to bf16, nearest even (`(__bf16)v` and the MFMA packers of csrc/conv.hip / stem16.hip), back in t's dtype."""
+    return t.float().to(torch.bfloat16).to(t.dtype)
+
+
+def bf16_trunc(t):
+    """Round to bf16 by truncation -- NOT what any kernel may do (negative control)."""
+    return (t.float().contiguous().view(torch.int32) & -65536).view(torch.float32).to(t.dtype)
+
+
+def rounded_operands(op, K, math):
+    """The operands a kernel rounds to bf16 before its fp32-accumulating products, by operator and math mode
+    (cf. test_gpu_parity_full._bf16_operands): forward rounds rows and weights; the data gradient rounds dY and weights
+    EXCEPT the 1x1x1 strided shortcut's (the exact-fp32 dense GEMM mink_dense_xwt); the weight gradient rounds rows and dY.
+    "bf16s" also STORES the stem's convolution output as bf16 (op "store": the y it keeps)."""
+    if math == "fp32":
+        return frozenset()
+    table = {"fwd": {"x", "w"}, "dgrad": set() if K == 1 else {"dy", "w"}, "wgrad": {"x", "dy"},
+             "store": {"y"} if math == "bf16s" else set()}
+    return frozenset(table[op])
+
+
+def apply_rounding(ops, rounded, rnd=bf16_rne):
+    """{name: tensor} -> the same, float64, with the names in `rounded` passed through `rnd` first (on their fp32 values)."""
+    return {k: (rnd(v.float()) if k in rounded else v).double() for k, v in ops.items()}
+
+
+# ------------------------------------------------------------------------------------------------ reference operators
+def check_table(nbr, n_in):
+    """Every entry of a table is -1 or a row of its n_in-row source: the references index with it on the device, where an
+    out-of-range index is a memory fault, not an exception."""
+    lo, hi = int(nbr.min()), int(nbr.max())
+    assert lo >= -1 and hi < n_in, f"table entries in [{lo}, {hi}], source has {n_in} rows"
+
+
+def _valid(nbr, k):
+    o = torch.nonzero(nbr[:, k] >= 0).squeeze(1)
+    return o, nbr[o, k].long()
+
+
+def scatter_rows(src, rows, n):
+    """out[rows[o]] += src[o] for rows[o] >= 0 (mink_rows_scatter_add: a 1x1x1 strided table's -1 entries are skipped)."""
+    check_table(rows[:, None], n)
+    o = torch.nonzero(rows >= 0).squeeze(1)
+    return torch.zeros(n, src.shape[1], dtype=torch.float64, device=src.device).index_add_(0, rows[o].long(), src[o].double())
+
+
+def conv_fwd(x, w, nbr):
+    """y[o] = sum_k x[nbr[o, k]] @ w[k]."""
+    check_table(nbr, x.shape[0])
+    y = torch.zeros(nbr.shape[0], w.shape[2], dtype=torch.float64, device=x.device)
+    for k in range(nbr.shape[1]):
+        o, i = _valid(nbr, k)
+        if o.numel():
+            y.index_add_(0, o, x[i].double() @ w[k].double())
+    return y
+
+
+def conv_dgrad(gy, w, nbr, n_in):
+    """dX of conv_fwd: gx[nbr[o, k]] += gy[o] @ w[k]^T (scattered through the FORWARD table: independent of the tables the
+    kernels gather through)."""
+    check_table(nbr, n_in)
+    assert gy.shape[0] == nbr.shape[0]
+    gx = torch.zeros(n_in, w.shape[1], dtype=torch.float64, device=gy.device)
+    for k in range(nbr.shape[1]):
+        o, i = _valid(nbr, k)
+        if o.numel():
+            gx.index_add_(0, i, gy[o].double() @ w[k].double().t())
+    return gx
+
+
+def conv_dgrad_gather(gy, w, table, flip_k=False, perm=None):
+    """dX in the form the kernels compute it, one row per table row: gx[i] = sum_k gy[table[i, k]] @ w[k']^T with
+    k' = K-1-k (`flip_k`: a centred odd stride-1 kernel through its own forward table) or k' = k (the transposed table of a
+    strided convolution).  `perm` (the class partition of the strided data gradient, -1 padded) must visit every row once."""
+    K = table.shape[1]
+    check_table(table, gy.shape[0])
+    if perm is not None:
+        p = perm[perm >= 0].long()
+        assert p.numel() == table.shape[0] and torch.equal(torch.sort(p).values, torch.arange(table.shape[0], device=p.device)), \
+            "class permutation does not visit every row exactly once"
+    gx = torch.zeros(table.shape[0], w.shape[1], dtype=torch.float64, device=gy.device)
+    for k in range(K):
+        r, o = _valid(table, k)
+        if r.numel():
+            gx.index_add_(0, r, gy[o].double() @ w[K - 1 - k if flip_k else k].double().t())
+    return gx
+
+
+def conv_wgrad(x, gy, nbr):
+    """dW[k] = x[nbr[:, k]]^T @ gy over the valid pairs."""
+    check_table(nbr, x.shape[0])
+    assert gy.shape[0] == nbr.shape[0]
+    K = nbr.shape[1]
+    gw = torch.zeros(K, x.shape[1], gy.shape[1], dtype=torch.float64, device=x.device)
+    for k in range(K):
+        o, i = _valid(nbr, k)
+        if o.numel():
+            gw[k] = x[i].double().t() @ gy[o].double()
+    return gw
+
+
+def bn_stats(y, eps=1e-5):
+    """Training-mode batch statistics: mean and 1 / sqrt(biased variance + eps), float64."""
+    y = y.double()
+    mean = y.mean(0)
+    return mean, (((y - mean) ** 2).mean(0) + eps).rsqrt()
+
+
+def _bn(y, gamma, beta, eps):
+    mean, invstd = bn_stats(y, eps)
+    return (y - mean) * invstd * gamma + beta
+
+
+def bn_fwd(y, gamma, beta, residual=None, eps=1e-5):
+    """z = gamma * (y - mean) * invstd + beta [+ residual] -- the pre-activation; the caller applies its ReLU decision."""
+    z = _bn(y.double(), gamma.double(), beta.double(), eps)
+    return z if residual is None else z + residual.double()
+
+
+def bn_bwd(g, y, gamma, beta, mask=None, eps=1e-5):
+    """Backward of out = [mask *] bn(y) (+ a residual, whose gradient is the masked g): autograd in float64.
+    `mask`: the KERNEL's ReLU decisions (out > 0 of the stored output), None = no ReLU.  -> (dy, d_residual, dgamma, dbeta)."""
+    y64 = y.double().detach().requires_grad_(True)
+    ga = gamma.double().detach().requires_grad_(True)
+    be = beta.double().detach().requires_grad_(True)
+    dz = g.double() if mask is None else g.double() * mask.double()
+    with torch.enable_grad():
+        z = _bn(y64, ga, be, eps)
+        dy, dga, dbe = torch.autograd.grad(z, (y64, ga, be), dz)
+    return dy, dz, dga, dbe
+
+
+def sum_pool(x, in2out, n_out):
+    """Sum pooling (2, 2): out[in2out[i]] += x[i]."""
+    assert in2out.shape[0] == x.shape[0]
+    check_table(in2out[:, None], n_out)
+    assert int(in2out.min()) >= 0
+    return torch.zeros(n_out, x.shape[1], dtype=torch.float64, device=x.device).index_add_(0, in2out.long(), x.double())
+
+
+def stem_bwd(g_pool, y, gamma, beta, in2out, mask, eps=1e-5):
+    """Backward of pool(relu(bn(y))) under the kernel's ReLU decisions `mask` [n, C]: -> (dy, dgamma, dbeta)."""
+    assert in2out.shape[0] == y.shape[0] and int(in2out.min()) >= 0 and int(in2out.max()) < g_pool.shape[0]
+    dy, _, dga, dbe = bn_bwd(g_pool.double()[in2out.long()], y, gamma, beta, mask, eps)
+    return dy, dga, dbe
+
+
+def fma32(a, b, c):
+    """fp32 fma(a, b, c), exactly (the product of two floats is exact in float64)."""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def stem_wgrad_operand(g_pool, y, mean, invstd, gamma, beta, dgamma, dbeta, in2out, n):
+    """The dY operand the stem's fused weight-gradient kernel recomputes in fp32 from the kernel's own (y, mean, invstd,
+    dgamma, dbeta) (csrc/conv.hip, wgrad_stream*_kernel<FUSE>) -- what it then rounds to bf16 under bf16 math:
+      xh = fma(y, invstd, fl(-mean * invstd)),  m = fma(xh, gamma, beta) > 0,
+      v  = fl(gamma * invstd) * fma(-fl(dgamma / n), xh, fma(dp, m, -fl(dbeta / n)))   (1 / n and the quotients as fl(x * fl(1 / n)))."""
+    assert in2out.shape[0] == y.shape[0] and int(in2out.min()) >= 0 and int(in2out.max()) < g_pool.shape[0]
+    f = torch.float32
+    y, mean, invstd, gamma, beta, dgamma, dbeta = (t.to(f) for t in (y, mean, invstd, gamma, beta, dgamma, dbeta))
+    inv_n = torch.tensor(1.0 / n, dtype=f, device=y.device)
+    xh = fma32(y, invstd, -mean * invstd)
+    m = (fma32(xh, gamma, beta) > 0).to(f)
+    dp = g_pool.to(f)[in2out.long()]
+    inner = fma32(dp, m, -(dbeta * inv_n))
+    return (gamma * invstd) * fma32(-(dgamma * inv_n), xh, inner)
+
+
+# ------------------------------------------------------------------------------------------------ comparators
+@dataclass
+class Record:
+    layer: str
+    op: str
+    rows: int
+    shape: tuple
+    rounding: str
+    err: float
+    bound: float
+    ok: bool
+    note: str = ""
+
+    def line(self):
+        return (f"{self.layer:10s} {self.op:22s} rows {self.rows:8d}  {str(tuple(self.shape)):16s} {self.rounding:8s} "
+                f"err {self.err:.2e}  bound {self.bound:.0e}  {'ok' if self.ok else 'FAIL'}" + (f"  {self.note}" if self.note else ""))
+
+
+def _rnd_name(rounded):
+    return "+".join(sorted(rounded)) if rounded else "fp32"
+
+
+def conv_errors(got, ref):
+    """(relative L2, max |err| / max |ref|)."""
+    got, ref = got.double(), ref.double()
+    d = got - ref
+    return float(d.norm() / ref.norm().clamp_min(1e-300)), float(d.abs().max() / ref.abs().max().clamp_min(1e-300))
+
+
+def check_conv(layer, op, got, ref, rounded=frozenset(), ref_other=None):
+    """A convolution output, data gradient or weight gradient against float64 on the DECLARED-rounded operands: relative L2
+    <= CONV_REL and max |err| <= CONV_MAX max |ref|.  `ref_other`: float64 on the other rounding (fp32 operands where the table
+    rounds, rounded where it does not); where the two references are more than DISCRIMINATE bounds apart, the kernel must
+    also sit OUTSIDE the bound of the other -- a kernel that silently rounds differently from the table fails here.
+    -> [Record] (the second one, "declared vs other", only when it applies)."""
+    rel, mx = conv_errors(got, ref)
+    ok = rel <= CONV_REL and mx <= CONV_MAX
+    recs = [Record(layer, op, got.shape[0], tuple(got.shape), _rnd_name(rounded), rel, CONV_REL, ok, f"max {mx:.1e}")]
+    if ref_other is not None:
+        sep, _ = conv_errors(ref_other, ref)
+        if sep > DISCRIMINATE * CONV_REL:
+            rel_o, mx_o = conv_errors(got, ref_other)
+            ok_o = ok and not (rel_o <= CONV_REL and mx_o <= CONV_MAX)
+            recs.append(Record(layer, op + " vs other", got.shape[0], tuple(got.shape), "other", rel_o, CONV_REL, ok_o,
+                               f"references {sep:.1e} apart; must exceed the bound"))
+        else:
+            recs.append(Record(layer, op + " vs other", got.shape[0], tuple(got.shape), "other", sep, CONV_REL, True,
+                               "references too close to discriminate"))
+    return recs
+
+
+def check_scaled(layer, op, got, ref, scale, bound=NORM_BOUND, rows=None, mask=None, note=""):
+    """max |got - ref| <= bound * scale (elements where `mask` is False excluded)."""
+    d = (got.double() - ref.double()).abs()
+    if mask is not None:
+        d = d[mask]
+    err = float(d.max() / max(float(scale), 1e-300)) if d.numel() else 0.0
+    return [Record(layer, op, rows if rows is not None else got.shape[0], tuple(got.shape), "fp32", err, bound, err <= bound, note)]
+
+
+def check_stats(layer, op, mean, invstd, y, eps=1e-5):
+    """Batch statistics of the kernel against bn_stats of the y it normalised: mean within NORM_BOUND of the rms of y, invstd
+    within NORM_BOUND relative, channel by channel."""
+    m64, is64 = bn_stats(y, eps)
+    rms = float((y.double() ** 2).mean(0).sqrt().max())
+    return (check_scaled(layer, op + " mean", mean, m64, rms, rows=y.shape[0])
+            + check_scaled(layer, op + " invstd", invstd.double() / is64, torch.ones_like(is64), 1.0, rows=y.shape[0]))
+
+
+def check_relu_out(layer, op, got, z):
+    """A ReLU output of the kernel against relu(z) of float64: where the kernel's branch (got > 0) differs from float64's,
+    |z| <= FLIP_Z sd(z) (a legitimate decision at zero to rounding); everywhere else max |err| <= NORM_BOUND max |ref|."""
+    z = z.double()
+    ref = z.clamp_min(0)
+    flip = (got > 0) != (z > 0)
+    nf = int(flip.sum())
+    zmax = float(z[flip].abs().max() / z.std()) if nf else 0.0
+    recs = check_scaled(layer, op, got, ref, float(ref.abs().max()), mask=~flip, note=f"{nf} branch(es) differ")
+    recs.append(Record(layer, op + " flips", got.shape[0], tuple(got.shape), "fp32", zmax, FLIP_Z, zmax <= FLIP_Z,
+                       f"{nf} element(s), largest |z|/sd(z)"))
+    return recs
+
+
+def reduction_scale(terms):
+    """Per-column sum of |terms| (the scale fp32 rounding of a column sum is proportional to), its max over columns."""
+    return float(terms.double().abs().sum(0).max())
+
+
+def check_bn_bwd(layer, op, got_dy, got_dga, got_dbe, g, y, gamma, beta, mask, got_dres=None, eps=1e-5):
+    """Batch-norm backward (+ ReLU under the kernel's `mask`, + residual) against autograd in float64: dx within NORM_BOUND
+    of max |ref|; dgamma / dbeta, column sums over all rows, within NORM_BOUND of the sum of |terms| of their worst column."""
+    dy, dz, dga, dbe = bn_bwd(g, y, gamma, beta, mask, eps)
+    mean, invstd = bn_stats(y, eps)
+    n = y.shape[0]
+    recs = check_scaled(layer, op + " dx", got_dy, dy, float(dy.abs().max()), rows=n)
+    recs += check_scaled(layer, op + " dgamma", got_dga, dga, reduction_scale(dz * (y.double() - mean) * invstd), rows=n)
+    recs += check_scaled(layer, op + " dbeta", got_dbe, dbe, reduction_scale(dz), rows=n)
+    if got_dres is not None:
+        recs += check_scaled(layer, op + " dresidual", got_dres, dz, float(dz.abs().max()), rows=n)
+    return recs
+
+
+def check_bf16_store(layer, op, got, ref):
+    """A value the kernel STORES as bf16: within half a bf16 ulp of the float64 value, plus STORE_MAX * max |ref|."""
+    ref = ref.double()
+    a = ref.abs().float().clamp_min(torch.finfo(torch.float32).tiny)
+    ulp = torch.ldexp(torch.ones_like(a), torch.frexp(a).exponent - 8).double()  # bf16: 8 significant bits
+    slack = (got.double() - ref).abs() - 0.5 * ulp
+    err = float(slack.max() / ref.abs().max())
+    return [Record(layer, op, got.shape[0], tuple(got.shape), "y", max(err, 0.0), STORE_MAX, err <= STORE_MAX, "beyond half an ulp")]
+
+
+def report(records, title="", force=False):
+    """One table line per operator; printed when something failed, when `force`, or with MINK_TEST_VERBOSE."""
+    import os
+
+    bad = [r for r in records if not r.ok]
+    if bad or force or os.environ.get("MINK_TEST_VERBOSE"):
+        print(f"\n[{title}] teacher-forced per-operator errors vs float64 ({len(records)} checks, {len(bad)} failed)")
+        for r in records:
+            print("  " + r.line())
+    return bad
