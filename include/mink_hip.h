@@ -498,6 +498,74 @@ int mink_augment_scenes(const void *coords, int32_t coords_are_int32, const floa
                         const uint32_t *streams, uint64_t seed, const int32_t *raw_cols, float *out_coords,
                         float *out_feats, int64_t ldo, int32_t *n_kept, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ segmentation scene augmentation
+ * The PeRFception-ScanNet recipe of the reference (configs/scannet_plenoxel.gin: RandomRotation, RandomCrop, RandomAffine,
+ * CoordinateDropout, RandomFeatureJitter, RandomHorizontalFlip, RandomTranslation, ElasticDistortion) as one device program
+ * per scene.  Its own parameter row: MINK_SEGAUG_PARAMS DOUBLES per scene (matrices row-major, applied as row-vector * M):
+ *     p = c * A0 + a0                          stages before the crop
+ *     crop (CROP != 0; transforms.py:194-244): n = p - min(p), range = max(max(n) - CROP_SIZE, 0) per axis, over every row
+ *         of the scene.  range == 0 on all axes: no crop.  Else box k < CROP_TRIES: lo = CROP_U[k] * range,
+ *         hi = lo + CROP_SIZE, keeps the rows with lo < n < hi on every axis; the first box that keeps a row wins; none: no crop
+ *     q = p * A1 + a1                          stages between the crop and the flip
+ *     kept = in crop && u >= DROPOUT           (the dropout coin u of MINK_AUG; crop first: dropout after the crop)
+ *     q_j = FLIP[j] ? max_j - q_j : q_j        max over the rows alive at the flip: in crop && u >= DROPOUT
+ *                                              (in crop only when FLIP_ALL != 0: dropout listed after the flip)
+ *     r = q * B + b                            stages after the flip
+ *     elastic pass e < MINK_SEGAUG_MAX_ELASTIC with g = ELASTIC[2e] > 0, m = ELASTIC[2e+1] (transforms.py:535-594), over the
+ *         kept rows: lo = min(r), dim = floor((max(r) - lo) / g) + 3 per axis; noise [dim][3] ~ N(0,1) blurred by
+ *         Bx^2 By^2 Bz^2 (B = 3-tap box 1/3, zero outside the grid); r += m * trilinear(noise; node i at lo - g + i g; 0 outside the grid's box)
+ *     feats[:, raw column in [FEAT_START, FEAT_START + FEAT_DIM)] += (normal - 0.5) * FEAT_STD     (as MINK_AUG)
+ * Coordinates are computed in double -- p, q and r with every product and sum rounded, in the order
+ * ((v0*M0j + v1*M1j) + v2*M2j) + t_j, so a float64 restatement reproduces the crop decision exactly -- and written as float.
+ * Every min / max is an order-preserving integer atomic: results are bitwise identical run to run.
+ * Philox4x32-10 with key = seed.  Per row: counter (row in scene, draw, streams[b], 0), as MINK_AUG (draw 0 -> dropout coin,
+ * draw 1+j/4 -> feature noise).  Grid node (ix, iy, iz) of elastic pass e: counter (ix | iy << 16, iz | e << 16, streams[b], 1);
+ * words (0,1) -> Box-Muller -> noise x, y; words (2,3) -> noise z (cosine branch); u1 = (w >> 8) + 1 over 2^24, so |noise| <= 5.77.
+ * The noise grids live in the workspace at capacities the caller sizes on the host: GRID_BOUND[3] per scene (a bound of dim
+ * over the scene's passes), grid_nodes = sum over the scenes of GRID_BOUND[0] * GRID_BOUND[1] * GRID_BOUND[2].  A pass whose
+ * dim exceeds its scene's bound stores no grid (nothing is written past the bound): the displacement of each point is then
+ * evaluated from the Philox noise of the 6^3 nodes around it -- the same values -- and the pass is counted in status[1].
+ * A dim over 65535 (nodes that cannot be keyed) or a non-finite extent: the pass is not applied, counted in status[2].
+ * EXTENT (the raw per-axis extent of the scene) is read by the host only, to compute GRID_BOUND. */
+enum {
+  MINK_SEGAUG_A0 = 0,          /* 9 */
+  MINK_SEGAUG_a0 = 9,          /* 3 */
+  MINK_SEGAUG_CROP = 12,       /* 1 = RandomCrop drawn */
+  MINK_SEGAUG_CROP_SIZE = 13,  /* 3 */
+  MINK_SEGAUG_CROP_TRIES = 16, /* boxes drawn, <= MINK_SEGAUG_MAX_TRIES */
+  MINK_SEGAUG_CROP_U = 17,     /* [MINK_SEGAUG_MAX_TRIES][3] uniform [0,1) */
+  MINK_SEGAUG_A1 = 65,         /* 9 */
+  MINK_SEGAUG_a1 = 74,         /* 3 */
+  MINK_SEGAUG_DROPOUT = 77,    /* dropout ratio, 0 = none */
+  MINK_SEGAUG_FLIP = 78,       /* 3 flags */
+  MINK_SEGAUG_FLIP_ALL = 81,
+  MINK_SEGAUG_B = 82,          /* 9 */
+  MINK_SEGAUG_b = 91,          /* 3 */
+  MINK_SEGAUG_FEAT_STD = 94,   /* 0 = none */
+  MINK_SEGAUG_FEAT_START = 95, /* raw-layout column; ScanNet: [xyzs 0:3 | dists 3 | density 4 | sh 5:32] */
+  MINK_SEGAUG_FEAT_DIM = 96,
+  MINK_SEGAUG_ELASTIC = 97,    /* [MINK_SEGAUG_MAX_ELASTIC][2] (granularity, magnitude); granularity 0 = no pass */
+  MINK_SEGAUG_GRID_BOUND = 101, /* 3 */
+  MINK_SEGAUG_EXTENT = 104,    /* 3, host only */
+  MINK_SEGAUG_PARAMS = 108,
+  MINK_SEGAUG_MAX_TRIES = 16,
+  MINK_SEGAUG_MAX_ELASTIC = 2
+};
+
+int64_t mink_augment_seg_workspace_bytes(int64_t n, int32_t n_scenes, int64_t grid_nodes);
+
+/* coords [n][4] (batch, x, y, z) sorted by batch, float32 or (coords_are_int32) int32; feats [n][ldf] (C columns used);
+ * scene_offsets [n_scenes+1], params [n_scenes][MINK_SEGAUG_PARAMS] (double), streams [n_scenes] on the device;
+ * raw_cols[C] a HOST array as for mink_augment_scenes.  n_elastic = elastic passes to run (the largest over the scenes),
+ * grid_nodes as above.  Writes the survivors, in order, to out_coords [>= n][4], out_feats [>= n][ldo] and the source row
+ * of every survivor to out_rows [>= n]; the device int32 status[3] receives (survivors, elastic passes evaluated without a
+ * stored grid, elastic passes not applied). */
+int mink_augment_seg_scenes(const void *coords, int32_t coords_are_int32, const float *feats, int64_t ldf, int32_t C, int64_t n,
+                            const int32_t *scene_offsets, int32_t n_scenes, const double *params, const uint32_t *streams,
+                            uint64_t seed, const int32_t *raw_cols, int32_t n_elastic, int64_t grid_nodes, float *out_coords,
+                            float *out_feats, int64_t ldo, int32_t *out_rows, int32_t *status, void *workspace,
+                            int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ optimizer step over flat buffers
  * torch.optim.SGD's update with momentum and weight decay (the reference's optimizer: co3d_3d/src/modules/optim.py:12-14,
  * co3d_3d/configs/co3d_cls.gin) for parameters w, gradients g and momentum buffers m that each live in ONE flat fp32 buffer of

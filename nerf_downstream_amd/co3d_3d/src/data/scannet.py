@@ -16,8 +16,11 @@ scale of every scene.  A sample, as in the reference (:585-653):
 * features selected by name from [dists | density (max-normalised when more than one feature) | sh | ones];
 * labels mapped from the 40 raw ids to the 20 evaluated classes, everything else to `ignore_label`.
 
-The reference's CPU augmentations for this data set (RandomCrop, ElasticDistortion, ...) are outside this path's scope;
-only an empty transformation list is accepted."""
+Augmentations (extension `device_augmentation=True`): the reference's recipe for this data set (RandomRotation,
+RandomCrop, RandomAffine, CoordinateDropout, RandomFeatureJitter, RandomHorizontalFlip, RandomTranslation,
+ElasticDistortion; data/seg_transforms.py) is drawn here, one program per scene with the scene's raw extent, and applied
+to the whole batch on the GPU (`MinkowskiBaseModel.process_input`, `mink_augment_seg_scenes`); the training step gathers
+the labels of the surviving rows.  Without it only an empty transformation list is accepted."""
 import os
 
 import numpy as np
@@ -26,6 +29,8 @@ from torch.utils.data import Dataset
 
 from nerf_downstream_amd import gin_lite as gin
 from nerf_downstream_amd.safe_load import load_plain_pickle
+
+from . import seg_transforms
 
 CLASS_LABELS = ("wall", "floor", "cabinet", "bed", "chair", "sofa", "table", "door", "window", "bookshelf", "picture", "counter",
                 "desk", "curtain", "refrigerator", "shower curtain", "toilet", "sink", "bathtub", "otherfurniture")
@@ -42,12 +47,23 @@ class PlenoxelScannetDataset(Dataset):
 
     def __init__(self, phase, data_root="co3d_3d/datasets/co3d", train_transformations=(), eval_transformations=(),
                  downsample_mode=1, downsample_stride=2, voxel_size=0.02, num_points=-1, features=("sh",), ignore_label=-100,
-                 void_label=None, valid_thres=0.05, ignore_thres=None):
+                 void_label=None, valid_thres=0.05, ignore_thres=None, device_augmentation=False):
         phase = "test" if phase in ("val", "test") else "train"
         names = list(train_transformations if phase == "train" else eval_transformations)
-        if names:
+        self.transformations = None
+        if names and not device_augmentation:
             raise NotImplementedError(f"augmentations {names} of the ScanNet recipe run on the CPU in the reference and are "
-                                      "outside the scope of this path: pass an empty transformation list")
+                                      "outside the scope of this path: pass an empty transformation list (or "
+                                      "device_augmentation=True to run them on the GPU)")
+        if names:
+            unknown = [t for t in names if t not in seg_transforms.SUPPORTED]
+            if unknown:
+                raise NotImplementedError(f"augmentations {unknown} have no GPU counterpart (supported: the classes of "
+                                          "data/seg_transforms.py)")
+            if "xyzs" in features:
+                raise NotImplementedError("the 'xyzs' feature of an augmented scene is its transformed coordinates (reference "
+                                          "scannet.py:633-640): not produced by the device program")
+            self.transformations = seg_transforms.SegCompose([getattr(seg_transforms, t)() for t in names])
         if downsample_mode != 1:
             raise NotImplementedError("downsample_mode 0 (average pooling in the loader) is not implemented; mode 1 sub-samples")
         self.phase, self.data_root, self.features = phase, data_root, list(features)
@@ -104,8 +120,14 @@ class PlenoxelScannetDataset(Dataset):
         raw = labels.reshape(-1)
         mapped = np.where((raw >= 0) & (raw < self.NUM_LABELS), self._lut[np.clip(raw, 0, self.NUM_LABELS - 1)],
                           np.where(raw == self.void_label, self.label_map.get(self.void_label, self.ignore_label), self.ignore_label))
-        return {"coordinates": torch.from_numpy(xyzs), "features": torch.from_numpy(features), "xyzs": torch.from_numpy(xyzs),
-                "labels": mapped.astype(np.int64), "dists": dists.reshape(-1, 1), "metadata": {"file": inst_id}}
+        sample = {"coordinates": torch.from_numpy(xyzs), "features": torch.from_numpy(features), "xyzs": torch.from_numpy(xyzs),
+                  "labels": mapped.astype(np.int64), "dists": dists.reshape(-1, 1), "metadata": {"file": inst_id}}
+        if self.transformations is not None:  # drawn here (DataLoader worker), applied on the GPU
+            extent = (xyzs.max(0) - xyzs.min(0)).astype(np.float64) if len(xyzs) else np.zeros(3)
+            params, stream = self.transformations.sample(extent)
+            sample["aug_params"], sample["aug_stream"] = torch.from_numpy(params), stream
+            sample["feature_names"] = tuple(self.features)
+        return sample
 
     def __len__(self):
         return len(self.files)

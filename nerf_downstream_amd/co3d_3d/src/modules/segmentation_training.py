@@ -53,8 +53,22 @@ class SegmentationTraining:
         return F.cross_entropy(logits, labels, weight=weight, ignore_index=self.ignore_label)
 
     def training_step(self, batch, field=None):
-        out = self.forward(field if field is not None else batch)
-        return self.loss(out, batch["labels"].long()), out
+        x = field if field is not None else self.model.process_input(batch)
+        if hasattr(x, "materialise"):  # (a deferred augmented batch not yet through finish_input)
+            x = x.materialise()
+        rows = getattr(x, "source_rows", None)
+        if rows is not None:  # augmented on the device: the field holds the surviving rows, in this order
+            batch["source_rows"] = rows
+        out = self.forward(x)
+        return self.loss(out, self.labels(batch)), out
+
+    @staticmethod
+    def labels(batch):
+        """The labels of the rows the model saw: gathered by `source_rows` when the batch was augmented on the device
+        (crop and dropout remove rows), the batch's own labels otherwise."""
+        labels = batch["labels"].long()
+        rows = batch.get("source_rows")
+        return labels if rows is None else labels[rows.long()]
 
     @staticmethod
     def check_finite(loss_float):
@@ -63,7 +77,7 @@ class SegmentationTraining:
 
     @torch.no_grad()
     def train_metrics(self, out, batch):
-        labels = batch["labels"].long()
+        labels = self.labels(batch)
         miou, macc, oa = iou_metrics(confusion(out.argmax(1), labels, out.shape[1]))
         return {"train/mIoU": miou, "train/mAcc": macc, "train/OA": oa,
                 "train/ignore_ratio": 100.0 * float((labels == self.ignore_label).float().mean())}

@@ -155,6 +155,9 @@ class TensorField:
             m.hand_over(cur)
             for t in (self._F, self._C):  # may have been produced on the build stream (GPU-side decode)
                 t.record_stream(cur)
+            rows = getattr(self, "source_rows", None)  # (augmented segmentation batch: the labels are gathered by it here)
+            if rows is not None:
+                rows.record_stream(cur)
             if m.xb is not None:
                 m.xb[1].record_stream(cur)
             self._ready = None

@@ -123,6 +123,80 @@ def augment_batch(coords, feats, scene_offsets, params, streams, seed, raw_cols,
     return out_c[:k], out_f[:k]
 
 
+class AugmentBoundError(RuntimeError):
+    """An elastic noise grid of `mink_augment_seg_scenes` has more than 65535 nodes along an axis (or a NaN extent):
+    its nodes cannot be keyed, and the pass was not applied to that scene."""
+
+
+def seg_status_check(status):
+    """Raise if the device reported elastic passes it could not apply (status = host int32 [survivors, passes evaluated
+    without a stored grid, passes not applied]).  A grid over its host-side bound is not an error: the device evaluates
+    it point by point (status[1], informational)."""
+    if int(status[2]) != 0:
+        raise AugmentBoundError(f"augment_seg_batch: {int(status[2])} elastic noise grid(s) with more than 65535 nodes along "
+                                "an axis (or a non-finite extent): the pass was not applied to those scenes")
+
+
+def augment_seg_batch(coords, feats, scene_offsets, params, streams, seed, raw_cols, count_async=False, grid_bound=None):
+    """Apply the drawn segmentation programs (data/seg_transforms.py, include/mink_hip.h MINK_SEGAUG_*) to a whole batch
+    with `mink_augment_seg_scenes`.
+
+    coords int32/f32 [N,4] sorted by batch, feats f32 [N,C], scene_offsets int32 [S+1], streams int32 [S] on the device;
+    params float64 [S, MINK_SEGAUG_PARAMS] on the HOST (its EXTENT columns size the noise grids: `grid_bounds`; a device
+    tensor is copied back first).  `grid_bound` int [S,3] replaces the computed bound.  Returns float coordinates,
+    features and the int32 source row of every survivor; the survivor count and the status are read back (one small
+    synchronisation) unless `count_async=True`, which returns (coords, feats, rows, (pinned int32 [3] status, event)) with
+    full-length buffers for the caller to slice once the event has completed (`seg_status_check` on the status)."""
+    import torch
+
+    from .._lib import check, lib
+    from ..co3d_3d.src.data.seg_transforms import SEG, elastic_passes, grid_bounds
+
+    if not coords.is_cuda:
+        raise RuntimeError("augment_seg_batch runs on the GPU: move the batch to cuda first")
+    n, C = coords.shape[0], feats.shape[1]
+    dev = coords.device
+    if coords.dtype not in (torch.int32, torch.float32) or feats.dtype != torch.float32:
+        raise TypeError("augment_seg_batch: coordinates int32 or float32, features float32")
+    coords, feats = coords.contiguous(), feats.contiguous()
+    n_scenes = scene_offsets.numel() - 1
+    P = params.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(params) else np.array(params, np.float64)
+    if P.shape != (n_scenes, SEG["PARAMS"]):
+        raise ValueError(f"augment_seg_batch: parameter rows {P.shape}, ({n_scenes}, {SEG['PARAMS']}) expected")
+    bound = grid_bounds(P) if grid_bound is None else np.asarray(grid_bound, np.int64).reshape(n_scenes, 3)
+    P[:, SEG["GRID_BOUND"]:SEG["GRID_BOUND"] + 3] = bound
+    grid_nodes = int(np.prod(bound, axis=1).sum())
+    n_elastic = elastic_passes(P)
+    dparams = torch.from_numpy(P).pin_memory().to(dev, non_blocking=True)
+    out_c = torch.empty(n, 4, dtype=torch.float32, device=dev)
+    out_f = torch.empty(n, C, dtype=torch.float32, device=dev)
+    rows = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(3, dtype=torch.int32, device=dev)
+    offs = scene_offsets.to(dev, torch.int32, non_blocking=True).contiguous()
+    strm = streams.to(dev, torch.int32, non_blocking=True).contiguous()
+    ws = torch.empty(max(1, lib().mink_augment_seg_workspace_bytes(n, n_scenes, grid_nodes)), dtype=torch.uint8, device=dev)
+    cols = (ctypes.c_int32 * C)(*[int(c) for c in raw_cols])
+    stream = torch._C._cuda_getCurrentRawStream(dev.index)
+    check(
+        lib().mink_augment_seg_scenes(
+            coords.data_ptr(), int(coords.dtype == torch.int32), feats.data_ptr(), C, C, n, offs.data_ptr(), n_scenes,
+            dparams.data_ptr(), strm.data_ptr(), int(seed) & (2 ** 64 - 1), ctypes.cast(cols, ctypes.c_void_p), n_elastic,
+            grid_nodes, out_c.data_ptr(), out_f.data_ptr(), C, rows.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+            stream,
+        )
+    )
+    if count_async:
+        host = torch.empty(3, dtype=torch.int32, pin_memory=True)
+        host.copy_(status, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return out_c, out_f, rows, (host, ev)
+    st = status.cpu()
+    seg_status_check(st)
+    k = int(st[0])
+    return out_c[:k], out_f[:k], rows[:k]
+
+
 def kaiming_normal_(tensor, a=0, mode="fan_in", nonlinearity="leaky_relu"):
     """ME.utils.kaiming_normal_ for convolution kernels laid out (K, Cin, Cout): fan_in = K * Cin, fan_out = K * Cout."""
     import math
