@@ -566,6 +566,63 @@ int mink_augment_seg_scenes(const void *coords, int32_t coords_are_int32, const 
                             float *out_feats, int64_t ldo, int32_t *out_rows, int32_t *status, void *workspace,
                             int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ point-cloud voxel down-sampling
+ * ME.utils.sparse_quantize(xyz, colours, labels=labels, quantization_size=Q, return_index=True, ignore_label=IGNORE) as the
+ * reference's ScannetDataset calls it on every scene (co3d_3d/src/data/scannet.py:233-247), for a whole batch.  One parameter
+ * row per scene, MINK_VOXDS_PARAMS doubles: Q (quantisation size; 0 = no down-sampling), VOXEL (voxel size), IGNORE (label).
+ * Within each scene:
+ *     key            (b, floor(f32(x) / f32(Q)), floor(f32(y) / f32(Q)), floor(f32(z) / f32(Q))); Q == 0: every row its own voxel
+ *     representative the FIRST row of each voxel in input-row order; the representatives are ordered by that first row
+ *     label          the common raw label of the voxel's rows, IGNORE as soon as two of them differ (int32 min / max atomics)
+ *     coordinates    (b, f32(x[rep]) / f32(VOXEL), ...)  -- continuous, as scannet.py:244
+ * ME leaves the representative and the row order unspecified (its CPU and GPU backends differ); first row, first-row
+ * order is this project's convention.  A spatial key outside [-32768, 32767] sets MINK_STATUS_RANGE in status[1] (that
+ * voxel's rows are then numbered with the clamped key: the output is not valid). */
+enum {
+  MINK_VOXDS_Q = 0,
+  MINK_VOXDS_VOXEL = 1,
+  MINK_VOXDS_IGNORE = 2,
+  MINK_VOXDS_PARAMS = 4
+};
+
+int64_t mink_voxel_downsample_workspace_bytes(int64_t n);
+
+/* coords [n][4] float32 (batch, x, y, z), sorted by batch; feats [n][ldf] (C columns used); labels [n] int32; scene_offsets
+ * [n_scenes+1] and params [n_scenes][MINK_VOXDS_PARAMS] on the device.  Writes the representatives, in order, to
+ * out_coords [n][4], out_feats [n][ldo], out_labels [n] and their input rows to out_rows [n]; out_offsets [n_scenes+2]
+ * receives the row range of every scene's representatives, with out_offsets[n_scenes+1] = n (the unused tail counts as one
+ * more scene); the device int32 status[2] receives (representatives, MINK_STATUS_* bits). */
+int mink_voxel_downsample_scenes(const float *coords, const float *feats, int64_t ldf, int32_t C, const int32_t *labels, int64_t n,
+                                 const int32_t *scene_offsets, int32_t n_scenes, const double *params, float *out_coords,
+                                 float *out_feats, int64_t ldo, int32_t *out_labels, int32_t *out_rows, int32_t *out_offsets,
+                                 int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------ colour program
+ * The reference's colour stages (co3d_3d/src/data/transforms.py:44-122: ChromaticTranslation, ChromaticJitter,
+ * NormalizeColor) as an ordered list of at most MINK_COLORAUG_MAX_OPS ops per scene, applied to the 3 colour columns
+ * cols[0..2] of rows [0, scene_offsets[n_scenes]) (scene_offsets [n_scenes+1] on the device; rows past it are not touched).
+ * Row of MINK_COLORAUG_PARAMS doubles: COUNT ops, op k at OPS + k * MINK_COLORAUG_OP_STRIDE = (kind, arguments...):
+ *     TRANSLATE (t0, t1, t2)             c = f32(clip(c + t_j, 0, 255))          (double sum)
+ *     JITTER    (sigma)                  c = f32(clip(c + sigma * N(0,1), 0, 255)) (double), sigma = std * 255
+ *     NORMALIZE (m0, m1, m2, s0, s1, s2) c = (c - f32(m_j)) / f32(s_j)            (float)
+ * The jitter normals are Philox4x32-10 with key = seed, counter (key_rows[i] - key_offsets[b], k, streams[b], 2) for op k
+ * of row i in scene b: words (0,1) -> Box-Muller -> N_0, N_1, words (2,3) -> N_2 (cosine branch), u1 = ((w >> 8) + 1) / 2^24.
+ * key_rows [n] (int32) names the row a jitter is keyed by, key_offsets [n_scenes+1] the first key row of every scene. */
+enum {
+  MINK_COLORAUG_COUNT = 0,
+  MINK_COLORAUG_OPS = 1,
+  MINK_COLORAUG_OP_STRIDE = 8,
+  MINK_COLORAUG_MAX_OPS = 4,
+  MINK_COLORAUG_PARAMS = 33,
+  MINK_COLORAUG_TRANSLATE = 1,
+  MINK_COLORAUG_JITTER = 2,
+  MINK_COLORAUG_NORMALIZE = 3
+};
+
+int mink_color_augment_scenes(float *feats, int64_t ldf, const int32_t *cols_host, int64_t n, const int32_t *scene_offsets,
+                              int32_t n_scenes, const double *params, const uint32_t *streams, uint64_t seed,
+                              const int32_t *key_rows, const int32_t *key_offsets, void *stream);
+
 /* ------------------------------------------------------------------ optimizer step over flat buffers
  * torch.optim.SGD's update with momentum and weight decay (the reference's optimizer: co3d_3d/src/modules/optim.py:12-14,
  * co3d_3d/configs/co3d_cls.gin) for parameters w, gradients g and momentum buffers m that each live in ONE flat fp32 buffer of

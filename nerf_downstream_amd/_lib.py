@@ -119,6 +119,12 @@ SIGNATURES = {
         ctypes.c_int,
         [_p, _i32, _p, _i64, _i32, _i64, _p, _i32, _p, _p, ctypes.c_uint64, _p, _i32, _i64, _p, _p, _i64, _p, _p, _p, _i64, _p],
     ),
+    "mink_voxel_downsample_workspace_bytes": (_i64, [_i64]),
+    "mink_voxel_downsample_scenes": (
+        ctypes.c_int,
+        [_p, _p, _i64, _i32, _p, _i64, _p, _i32, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p],
+    ),
+    "mink_color_augment_scenes": (ctypes.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _p, ctypes.c_uint64, _p, _p, _p]),
     "mink_conv_set_stagger": (ctypes.c_int, [ctypes.c_int]),
     "mink_conv_set_pipeline": (ctypes.c_int, [ctypes.c_int]),
     "mink_conv_trace": (ctypes.c_int, [_p, _i64]),

@@ -2,10 +2,10 @@
 from nerf_downstream_amd import gin_lite as gin
 
 from .co3d import Co3D10pDataset, Co3DDataset
-from .scannet import PlenoxelScannetDataset
+from .scannet import PlenoxelScannetDataset, ScannetDataset
 from .synthetic import SparseVoxelDataset, SparseVoxelSegDataset
 
-DATASETS = {c.__name__: c for c in (Co3DDataset, Co3D10pDataset, PlenoxelScannetDataset, SparseVoxelDataset, SparseVoxelSegDataset)}
+DATASETS = {c.__name__: c for c in (Co3DDataset, Co3D10pDataset, PlenoxelScannetDataset, ScannetDataset, SparseVoxelDataset, SparseVoxelSegDataset)}
 
 
 @gin.configurable

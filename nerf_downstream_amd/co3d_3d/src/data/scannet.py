@@ -31,6 +31,7 @@ from nerf_downstream_amd import gin_lite as gin
 from nerf_downstream_amd.safe_load import load_plain_pickle
 
 from . import seg_transforms
+from .ply import load_ply
 
 CLASS_LABELS = ("wall", "floor", "cabinet", "bed", "chair", "sofa", "table", "door", "window", "bookshelf", "picture", "counter",
                 "desk", "curtain", "refrigerator", "shower curtain", "toilet", "sink", "bathtub", "otherfurniture")
@@ -134,3 +135,102 @@ class PlenoxelScannetDataset(Dataset):
 
     def __repr__(self):
         return f"{self.__class__.__name__}(phase={self.phase}, length={len(self)})"
+
+
+@gin.configurable
+class ScannetDataset(Dataset):
+    """The original ScanNet point clouds (counterpart of the reference's `ScannetDataset`, co3d_3d/src/data/scannet.py:149-275;
+    configs/scannet_semseg.gin).  `<data_root>/<DATA_PATH_FILE[phase]>` lists the scenes; each entry names a PLY file under
+    `data_root`, with or without its `.ply` extension (data/ply.py reads it: x y z, red green blue, label).
+
+    The loader only reads and draws.  Each sample carries the raw points (coordinates = xyz in metres, features = colours
+    0..255, labels = raw ids), one down-sampling row (MINK_VOXDS_*: quantisation size, voxel size, ignore label), the
+    raw-label -> class table, and the drawn programs: the geometric one (MINK_SEGAUG_*) and the colour one
+    (MINK_COLORAUG_*).  `MinkowskiBaseModel.process_input` then runs on the GPU, per scene, what the reference runs in the
+    loader: ME.utils.sparse_quantize(xyz, colours, labels, quantization_size=downsample_voxel_size) with label voting,
+    coordinates = xyz[representative] / voxel_size, the recipe, and the map of the voted labels onto the 20 classes; the
+    field carries the labels of its rows."""
+
+    NUM_LABELS = PlenoxelScannetDataset.NUM_LABELS
+    IGNORE_LABELS = PlenoxelScannetDataset.IGNORE_LABELS
+    # (the reference's point-cloud split files, read from data_root itself: not the 256-scene plenoxel subset)
+    DATA_PATH_FILE = {"train": "scannetv2_train.txt", "val": "scannetv2_val.txt", "test": "scannetv2_test.txt"}
+    CLASS_LABELS = CLASS_LABELS
+    VALID_CLASS_IDS = VALID_CLASS_IDS
+
+    def __init__(self, phase, data_root="datasets/scannet", downsample_voxel_size=None, voxel_size=0.02,
+                 train_transformations=("ChromaticTranslation", "ChromaticJitter", "CoordinateDropout", "RandomHorizontalFlip",
+                                        "RandomAffine", "RandomTranslation", "NormalizeColor"),
+                 eval_transformations=("NormalizeColor",), ignore_label=-100, features=("colors",)):
+        self.phase, self.data_root, self.ignore_label = phase, data_root, ignore_label
+        self.features = list(features)
+        if self.features != ["colors"]:
+            if "xyzs" in self.features:
+                raise NotImplementedError("the 'xyzs' feature of an augmented scene is its transformed coordinates: not produced "
+                                          "by the device program")
+            raise NotImplementedError(f"features {self.features}: the point clouds provide ['colors']")
+        names = list(train_transformations if phase == "train" else eval_transformations)
+        if "RandomFeatureJitter" in names:
+            raise NotImplementedError("RandomFeatureJitter on point-cloud colours is not part of the device program")
+        self.transformations = seg_transforms.PointCompose([_transform(t) for t in names]) if names else None
+        if downsample_voxel_size is None:
+            downsample_voxel_size = voxel_size / 2
+        self.downsample_voxel_size, self.voxel_size = downsample_voxel_size, voxel_size
+        with open(os.path.join(self.data_root, self.DATA_PATH_FILE[phase])) as f:
+            self.files = [line.strip() for line in f if line.strip() and not line.startswith("#")]
+        label_map, lut = _label_map(self, ignore_label)
+        self.label_map, self._lut = label_map, lut
+        self.NUM_CLASSES = len(self.CLASS_LABELS)
+
+    def path(self, entry):
+        p = os.path.join(self.data_root, entry)
+        if not os.path.exists(p) and not entry.endswith(".ply") and os.path.exists(p + ".ply"):
+            p += ".ply"
+        return p
+
+    def __getitem__(self, index):
+        xyz, colors, labels = load_ply(self.path(self.files[index]))
+        ds = np.zeros(4, np.float64)  # MINK_VOXDS_*
+        ds[0], ds[1], ds[2] = max(float(self.downsample_voxel_size), 0.0), self.voxel_size, self.ignore_label
+        sample = {"coordinates": torch.from_numpy(xyz), "features": torch.from_numpy(colors), "labels": labels.astype(np.int64),
+                  "ds_params": torch.from_numpy(ds), "class_lut": torch.from_numpy(self._lut), "metadata": {"file": self.files[index]},
+                  "dataset": "scannet", "feature_names": tuple(self.features)}
+        if self.transformations is not None:  # drawn here (DataLoader worker), applied on the GPU
+            extent = ((xyz.max(0) - xyz.min(0)).astype(np.float64) / self.voxel_size) if len(xyz) else np.zeros(3)
+            geo, col, stream = self.transformations.sample(extent)
+            if geo is not None:
+                sample["aug_params"] = torch.from_numpy(geo)
+            if col is not None:
+                sample["color_params"] = torch.from_numpy(col)
+            sample["aug_stream"] = stream
+        return sample
+
+    def __len__(self):
+        return len(self.files)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(phase={self.phase}, length={len(self)})"
+
+
+def _transform(name):
+    cls = getattr(seg_transforms, name, None)
+    if cls is None or not (isinstance(cls, type) and (cls in seg_transforms.COLOR_STAGES or name in seg_transforms.SUPPORTED)):
+        if name in seg_transforms.UNSUPPORTED_COLOR:
+            raise NotImplementedError(f"colour stage {name} has no device counterpart (supported: "
+                                      f"{[c.__name__ for c in seg_transforms.COLOR_STAGES]})")
+        raise NotImplementedError(f"augmentation {name} has no GPU counterpart (supported: the classes of data/seg_transforms.py)")
+    return cls()
+
+
+def _label_map(ds, ignore_label):
+    """The reference's raw-id -> class map (scannet.py:205-214) and its table over 0..NUM_LABELS-1 (int64)."""
+    label_map, n_used = {}, 0
+    for raw in range(ds.NUM_LABELS):
+        if raw in ds.IGNORE_LABELS:
+            label_map[raw] = ignore_label
+        else:
+            label_map[raw] = n_used
+            n_used += 1
+    label_map[ignore_label] = ignore_label
+    lut = np.array([label_map[r] for r in range(ds.NUM_LABELS)], np.int64)
+    return label_map, lut

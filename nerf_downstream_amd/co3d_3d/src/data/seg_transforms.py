@@ -14,6 +14,11 @@ Differences from the reference, by design (beside the per-voxel coin dropout of 
   the scene).  The first box is the reference's first box; the rest of the recipe sees a numpy stream advanced further.
 * ElasticDistortion draws only its gate on the host; the noise grid is drawn on the device (Philox, keyed by grid node).
 
+The colour stages of the point-cloud recipe (configs/scannet_semseg.gin: ChromaticTranslation, ChromaticJitter,
+NormalizeColor) form a program of their own (MINK_COLORAUG_*, `mink_color_augment_scenes`): `PointCompose` draws every
+stage in list order and splits the stages before compiling, so colour stages may sit anywhere, after ElasticDistortion
+too.  ChromaticJitter draws only its gate on the host; its normals are Philox on the device, keyed by the raw point.
+
 The ScanNet raw feature layout RandomFeatureJitter indexes is [xyzs 0:3 | dists 3 | density 4 | sh 5:32] (reference
 scannet.py:623-635): RandomFeatureJitter(start_ind=4, feature_dim=27) jitters density and sh[0:26], as there."""
 import random
@@ -68,6 +73,114 @@ class ElasticDistortion:
     def draw(self, stages):
         if self.distortion_params is not None and random.random() < self.application_ratio:
             stages.append(("elastic", self.distortion_params))
+
+
+COLOR = dict(COUNT=0, OPS=1, OP_STRIDE=8, MAX_OPS=4, PARAMS=33, TRANSLATE=1, JITTER=2, NORMALIZE=3)  # MINK_COLORAUG_*
+# colour stages of the reference (transforms.py) that have no device counterpart here
+UNSUPPORTED_COLOR = ("ChromaticAutoContrast", "HueSaturationTranslation", "RandomDropout", "ChromaticJitterPerChannel")
+
+
+@gin.configurable()
+class ChromaticTranslation:
+    """Reference transforms.py:43-61: with probability application_ratio, add (rand(1, 3) - 0.5) * 255 * 2 * ratio to the
+    colours and clip them to [0, 255]."""
+
+    def __init__(self, translation_range_ratio=1e-1, application_ratio=0.9):
+        self.trans_range_ratio, self.application_ratio = translation_range_ratio, application_ratio
+
+    def draw(self, ops):
+        if random.random() < self.application_ratio:
+            ops.append(("translate", ((np.random.rand(1, 3) - 0.5) * 255 * 2 * self.trans_range_ratio).reshape(3)))
+
+
+@gin.configurable()
+class ChromaticJitter:
+    """Reference transforms.py:97-111: with probability application_ratio, add N(0, (std * 255)^2) to the colours and clip
+    them to [0, 255].  Only the gate is drawn here; the normals are Philox on the device, keyed by the row's raw point
+    (the reference draws np.random.randn(N, 3) on the host, which this stream does not)."""
+
+    def __init__(self, std=0.01, application_ratio=0.9):
+        self.std, self.application_ratio = std, application_ratio
+
+    def draw(self, ops):
+        if random.random() < self.application_ratio:
+            ops.append(("jitter", self.std * 255))
+
+
+@gin.configurable()
+class NormalizeColor:
+    """Reference transforms.py:114-122: (colours - mean) / std in float32.  Draws nothing."""
+
+    def __init__(self, mean=(128, 128, 128), std=(256, 256, 256)):
+        self.mean, self.std = np.array(mean, np.float32).reshape(3), np.array(std, np.float32).reshape(3)
+
+    def draw(self, ops):
+        ops.append(("normalize", self.mean, self.std))
+
+
+COLOR_STAGES = (ChromaticTranslation, ChromaticJitter, NormalizeColor)
+
+
+def compile_color_program(ops):
+    """Fold one scene's drawn colour ops into a MINK_COLORAUG_* row (float64 [PARAMS]), in list order."""
+    if len(ops) > COLOR["MAX_OPS"]:
+        raise NotImplementedError(f"{len(ops)} colour ops in one scene: the device program holds {COLOR['MAX_OPS']}")
+    P = np.zeros(COLOR["PARAMS"], np.float64)
+    P[COLOR["COUNT"]] = len(ops)
+    for k, op in enumerate(ops):
+        o = COLOR["OPS"] + k * COLOR["OP_STRIDE"]
+        if op[0] == "translate":
+            P[o], P[o + 1:o + 4] = COLOR["TRANSLATE"], np.asarray(op[1], np.float64).reshape(3)
+        elif op[0] == "jitter":
+            P[o], P[o + 1] = COLOR["JITTER"], op[1]
+        elif op[0] == "normalize":
+            P[o], P[o + 1:o + 4], P[o + 4:o + 7] = COLOR["NORMALIZE"], op[1], op[2]
+        else:
+            raise NotImplementedError(f"colour op {op[0]!r}")
+    return P
+
+
+def split_color_stages(transforms):
+    """-> (geometric transforms, colour transforms), each in list order.  Colour stages touch only the colour columns and
+    the geometric ones only move or select rows, so the two programs commute; only the order within each is kept.
+    A colour class of the reference without a device counterpart raises NotImplementedError naming it."""
+    geo, col = [], []
+    for t in transforms:
+        name = type(t).__name__ if not isinstance(t, str) else t
+        if name in UNSUPPORTED_COLOR:
+            raise NotImplementedError(f"colour stage {name} has no device counterpart (supported: "
+                                      f"{[c.__name__ for c in COLOR_STAGES]})")
+        (col if isinstance(t, COLOR_STAGES) else geo).append(t)
+    return geo, col
+
+
+class PointCompose:
+    """The recipe of the point-cloud dataset: every transform draws in list order, as the reference's Compose applies
+    them (colour stages draw their gates and values at their place in the list), then the stages are split into the
+    geometric program (a MINK_SEGAUG_* row, None without geometric stages) and the colour program (a MINK_COLORAUG_* row,
+    None without colour stages)."""
+
+    def __init__(self, transforms):
+        self.transforms = list(transforms)
+        geo, col = split_color_stages(self.transforms)
+        self.geometric = SegCompose(geo) if geo else None
+        self.color = bool(col)
+
+    def draw(self):
+        stages, ops = [], []
+        for t in self.transforms:
+            t.draw(ops if isinstance(t, COLOR_STAGES) else stages)
+        return stages, ops
+
+    def sample(self, extent):
+        """-> (geometric row or None, colour row or None, stream id) for one scene of raw per-axis extent `extent`."""
+        stages, ops = self.draw()
+        geo = compile_seg_program(stages, extent) if self.geometric is not None else None
+        col = compile_color_program(ops) if self.color else None
+        return geo, col, int(np.random.randint(0, 2 ** 32, dtype=np.uint64))
+
+    def __repr__(self):
+        return f"PointCompose({[type(t).__name__ for t in self.transforms]})"
 
 
 _KIND = {RandomRotation: "linear", RandomAffine: "linear", RandomScale: "linear", RandomTranslation: "translate",

@@ -48,7 +48,8 @@ def collate_mink(list_data):
     for key in ("metadata", "dataset", "colors"):
         if key in list_data[0]:
             package[key] = [d[key] for d in list_data]
-    return _with_programs(package, list_data, [int(d["coordinates"].shape[0]) for d in list_data])
+    n = [int(d["coordinates"].shape[0]) for d in list_data]
+    return _with_points(_with_programs(package, list_data, n), list_data, n)
 
 
 def _with_programs(package, list_data, n):
@@ -61,4 +62,20 @@ def _with_programs(package, list_data, n):
         package["aug_seed"] = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64))
         package.setdefault("scene_offsets", torch.tensor(np.concatenate([[0], np.cumsum(n)]), dtype=torch.int32))
         package.setdefault("feature_names", list_data[0].get("feature_names"))
+    return package
+
+
+def _with_points(package, list_data, n):
+    """Raw point clouds (data/scannet.py ScannetDataset): one down-sampling row per scene, the raw-label -> class table,
+    and the colour programs with their Philox stream ids when the recipe has colour stages; prepared on the GPU."""
+    if "ds_params" in list_data[0]:
+        package["ds_params"] = torch.stack([d["ds_params"] for d in list_data])
+        package["class_lut"] = list_data[0]["class_lut"]
+        package.setdefault("scene_offsets", torch.tensor(np.concatenate([[0], np.cumsum(n)]), dtype=torch.int32))
+        if "color_params" in list_data[0]:
+            package["color_params"] = torch.stack([d["color_params"] for d in list_data])
+        if "aug_stream" in list_data[0] and "aug_streams" not in package:
+            streams = np.array([d["aug_stream"] for d in list_data], dtype=np.uint32)
+            package["aug_streams"] = torch.from_numpy(streams.view(np.int32).copy())
+            package["aug_seed"] = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64))
     return package

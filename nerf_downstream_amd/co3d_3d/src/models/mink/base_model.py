@@ -36,6 +36,15 @@ class MinkowskiBaseModel(_HIP_ME.MinkowskiNetwork, InputInterface):
             with self._prepare_stream_ctx(batch["links"], fence=batch.get("h2d_event", True)):
                 coords, feats = ME.utils.decode_plenoxel_batch(batch)
             batch = dict(batch, coordinates=coords, features=feats)
+        if "ds_params" in batch:  # raw point clouds (ScannetDataset): down-sampled, then the drawn programs, all on the device
+            if not getattr(ME, "SUPPORTS_PREPARE_AHEAD", False):
+                raise RuntimeError("point clouds are prepared by the HIP backend (mink_voxel_downsample_scenes)")
+            with self._prepare_stream_ctx(batch["coordinates"], fence=batch.get("h2d_event", True)):
+                out = ME.utils.prepare_point_batch(batch, count_async=defer)
+            batch = {k: v for k, v in batch.items() if not k.startswith("aug_") and k not in ("ds_params", "color_params")}
+            batch["coordinates"], batch["features"], batch["row_labels"], batch["point_rows"] = out[:4]
+            if defer:  # the row count is still on its way to the host
+                return _PendingField(self, batch, out[4])
         if "aug_params" in batch:  # augmentation programs drawn by the loader: applied to the whole batch here
             with self._prepare_stream_ctx(batch["coordinates"], fence=batch.get("h2d_event", True)):
                 coords, feats, rows, pending = self._augment(batch, count_async=defer)
@@ -127,6 +136,8 @@ def _with_rows(field, batch):
     per-point tensors of the batch -- labels, dists -- are gathered by it."""
     if "source_rows" in batch:
         field.source_rows = batch["source_rows"]
+    if "row_labels" in batch:  # (point clouds: the voted class of every row, and its raw point)
+        field.row_labels, field.point_rows = batch["row_labels"], batch["point_rows"]
     return field
 
 
@@ -141,15 +152,20 @@ class _PendingField:
 
     def materialise(self):
         self.event.synchronize()
-        if self.count.numel() > 1:  # segmentation program: (survivors, direct elastic grids, elastic passes not applied)
+        if self.count.numel() > 3:  # point cloud: (survivors, direct elastic grids, passes not applied, down-sampling status)
+            from nerf_downstream_amd.minkowski.utils import points_status_check
+
+            points_status_check(self.count)
+        elif self.count.numel() > 1:  # segmentation program: (survivors, direct elastic grids, elastic passes not applied)
             from nerf_downstream_amd.minkowski.utils import seg_status_check
 
             seg_status_check(self.count)
         k = int(self.count[0])
         b = {key: v for key, v in self.batch.items() if not key.startswith("aug_") and key != "links"}
         b["coordinates"], b["features"] = b["coordinates"][:k], b["features"][:k]
-        if "source_rows" in b:
-            b["source_rows"] = b["source_rows"][:k]
+        for key in ("source_rows", "row_labels", "point_rows"):
+            if key in b:
+                b[key] = b[key][:k]
         return self.model.process_input(b, defer=False, _fence=False)  # the rows were produced on the prepare stream
 
     def sparse(self):

@@ -59,13 +59,19 @@ class SegmentationTraining:
         rows = getattr(x, "source_rows", None)
         if rows is not None:  # augmented on the device: the field holds the surviving rows, in this order
             batch["source_rows"] = rows
+        row_labels = getattr(x, "row_labels", None)
+        if row_labels is not None:  # point cloud prepared on the device: the voted class of every row of the field
+            batch["row_labels"] = row_labels
         out = self.forward(x)
         return self.loss(out, self.labels(batch)), out
 
     @staticmethod
     def labels(batch):
-        """The labels of the rows the model saw: gathered by `source_rows` when the batch was augmented on the device
-        (crop and dropout remove rows), the batch's own labels otherwise."""
+        """The labels of the rows the model saw: those the field carried (`row_labels`: point clouds, voted per voxel),
+        gathered by `source_rows` when the batch was augmented on the device (crop and dropout remove rows), the batch's
+        own labels otherwise."""
+        if "row_labels" in batch:
+            return batch["row_labels"].long()
         labels = batch["labels"].long()
         rows = batch.get("source_rows")
         return labels if rows is None else labels[rows.long()]
@@ -85,8 +91,12 @@ class SegmentationTraining:
     @torch.no_grad()
     def val_accumulate(self, batch):
         """-> float64 vector [loss * points, points, confusion matrix...] that validate() sums over batches and ranks."""
-        logits = self.forward(batch)
-        labels = batch["labels"].long()
+        x = self.model.process_input(batch)
+        if hasattr(x, "materialise"):
+            x = x.materialise()
+        row_labels = getattr(x, "row_labels", None)  # (point clouds: the metrics are taken over the representatives)
+        logits = self.forward(x)
+        labels = batch["labels"].long() if row_labels is None else row_labels.long()
         n = int(((labels >= 0) & (labels < logits.shape[1])).sum())
         loss = self.loss(logits, labels) if n else logits.sum() * 0
         hist = confusion(logits.argmax(1), labels, logits.shape[1])

@@ -155,9 +155,10 @@ class TensorField:
             m.hand_over(cur)
             for t in (self._F, self._C):  # may have been produced on the build stream (GPU-side decode)
                 t.record_stream(cur)
-            rows = getattr(self, "source_rows", None)  # (augmented segmentation batch: the labels are gathered by it here)
-            if rows is not None:
-                rows.record_stream(cur)
+            for name in ("source_rows", "row_labels", "point_rows"):  # (segmentation batches: the labels of the rows)
+                rows = getattr(self, name, None)
+                if rows is not None:
+                    rows.record_stream(cur)
             if m.xb is not None:
                 m.xb[1].record_stream(cur)
             self._ready = None

@@ -149,6 +149,23 @@ def augment_seg_batch(coords, feats, scene_offsets, params, streams, seed, raw_c
     full-length buffers for the caller to slice once the event has completed (`seg_status_check` on the status)."""
     import torch
 
+    out_c, out_f, rows, status = _augment_seg_launch(coords, feats, scene_offsets, params, streams, seed, raw_cols, grid_bound)
+    if count_async:
+        host = torch.empty(3, dtype=torch.int32, pin_memory=True)
+        host.copy_(status, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return out_c, out_f, rows, (host, ev)
+    st = status.cpu()
+    seg_status_check(st)
+    k = int(st[0])
+    return out_c[:k], out_f[:k], rows[:k]
+
+
+def _augment_seg_launch(coords, feats, scene_offsets, params, streams, seed, raw_cols, grid_bound=None):
+    """`mink_augment_seg_scenes` on the current stream -> full-length (coords, feats, rows) and the device status int32 [3]."""
+    import torch
+
     from .._lib import check, lib
     from ..co3d_3d.src.data.seg_transforms import SEG, elastic_passes, grid_bounds
 
@@ -185,16 +202,146 @@ def augment_seg_batch(coords, feats, scene_offsets, params, streams, seed, raw_c
             stream,
         )
     )
+    return out_c, out_f, rows, status
+
+
+class VoxelRangeError(RuntimeError):
+    """A voxel key of `mink_voxel_downsample_scenes` fell outside the packable range (|floor(xyz / q)| > 32767)."""
+
+
+def points_status_check(status):
+    """Raise on a failed point-cloud preparation (status = host int32 [survivors, elastic passes evaluated without a stored
+    grid, elastic passes not applied, MINK_STATUS_* bits of the down-sampling])."""
+    seg_status_check(status)
+    if int(status[3]) & 1:
+        raise VoxelRangeError("voxel_downsample: a voxel key outside [-32768, 32767] (coordinates / quantisation size too large)")
+
+
+def voxel_downsample_batch(coords, feats, labels, scene_offsets, params):
+    """`mink_voxel_downsample_scenes` (include/mink_hip.h MINK_VOXDS_*) on the current stream: ME.utils.sparse_quantize with
+    label voting, per scene.  coords f32 [N,4] (batch, x, y, z) sorted by batch, feats f32 [N,C], labels int [N],
+    scene_offsets int32 [S+1], params float64 [S, MINK_VOXDS_PARAMS], all on the device.  Nothing is read back: returns
+    full-length (coords f32 [N,4], feats [N,C], voted raw labels int32 [N], input row int32 [N] of every representative,
+    scene row ranges int32 [S+2] (the last range is the unused tail), device status int32 [2] = (representatives,
+    MINK_STATUS_* bits))."""
+    import torch
+
+    from .._lib import check, lib
+
+    if not coords.is_cuda:
+        raise RuntimeError("voxel_downsample_batch runs on the GPU: move the batch to cuda first")
+    if coords.dtype != torch.float32 or feats.dtype != torch.float32:
+        raise TypeError("voxel_downsample_batch: float32 coordinates and features")
+    dev, n, C = coords.device, coords.shape[0], feats.shape[1]
+    n_scenes = scene_offsets.numel() - 1
+    coords, feats = coords.contiguous(), feats.contiguous()
+    labels = labels.to(dev, torch.int32).contiguous()
+    offs = scene_offsets.to(dev, torch.int32).contiguous()
+    P = params.to(dev, torch.float64).contiguous()
+    if P.shape != (n_scenes, 4):
+        raise ValueError(f"voxel_downsample_batch: parameter rows {tuple(P.shape)}, ({n_scenes}, 4) expected")
+    out_c = torch.empty(n, 4, dtype=torch.float32, device=dev)
+    out_f = torch.empty(n, C, dtype=torch.float32, device=dev)
+    out_l = torch.empty(n, dtype=torch.int32, device=dev)
+    rows = torch.empty(n, dtype=torch.int32, device=dev)
+    out_offs = torch.empty(n_scenes + 2, dtype=torch.int32, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    ws = torch.empty(lib().mink_voxel_downsample_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    check(
+        lib().mink_voxel_downsample_scenes(
+            coords.data_ptr(), feats.data_ptr(), C, C, labels.data_ptr(), n, offs.data_ptr(), n_scenes, P.data_ptr(),
+            out_c.data_ptr(), out_f.data_ptr(), C, out_l.data_ptr(), rows.data_ptr(), out_offs.data_ptr(), status.data_ptr(),
+            ws.data_ptr(), ws.numel(), torch._C._cuda_getCurrentRawStream(dev.index),
+        )
+    )
+    return out_c, out_f, out_l, rows, out_offs, status
+
+
+def color_augment_batch(feats, scene_offsets, params, streams, seed, key_rows, key_offsets, cols=(0, 1, 2)):
+    """`mink_color_augment_scenes` (MINK_COLORAUG_*) IN PLACE on the colour columns `cols` of feats f32 [N,C], rows
+    [0, scene_offsets[S]); params float64 [S, MINK_COLORAUG_PARAMS], streams int32 [S]; the jitter of row i in scene b is
+    keyed by key_rows[i] - key_offsets[b].  All on the device; returns feats."""
+    import torch
+
+    from .._lib import check, lib
+
+    if not feats.is_cuda or feats.dtype != torch.float32 or not feats.is_contiguous():
+        raise TypeError("color_augment_batch: contiguous float32 features on the GPU")
+    dev, n = feats.device, feats.shape[0]
+    n_scenes = params.shape[0]
+    P = params.to(dev, torch.float64).contiguous()
+    offs = scene_offsets.to(dev, torch.int32).contiguous()
+    if offs.numel() < n_scenes + 1:
+        raise ValueError(f"color_augment_batch: {offs.numel()} scene offsets for {n_scenes} scenes")
+    strm = streams.to(dev, torch.int32).contiguous()
+    krows, koffs = key_rows.to(dev, torch.int32).contiguous(), key_offsets.to(dev, torch.int32).contiguous()
+    c = (ctypes.c_int32 * 3)(*[int(x) for x in cols])
+    check(
+        lib().mink_color_augment_scenes(
+            feats.data_ptr(), feats.shape[1], ctypes.cast(c, ctypes.c_void_p), n, offs.data_ptr(), n_scenes, P.data_ptr(),
+            strm.data_ptr(), int(seed) & (2 ** 64 - 1), krows.data_ptr(), koffs.data_ptr(),
+            torch._C._cuda_getCurrentRawStream(dev.index),
+        )
+    )
+    return feats
+
+
+def prepare_point_batch(batch, count_async=False):
+    """The point-cloud input of a batch of ScannetDataset (data/scannet.py), on the current stream: voxel down-sampling with
+    label voting, the colour programs, then the geometric programs (MINK_SEGAUG_*) when the loader drew them.  Colour ops
+    touch only colour columns and their noise is keyed by the raw row of the representative, so they commute with the
+    geometric stages, which only move or select rows: they run first, on the representatives.
+
+    batch (device): coordinates f32 [N,4] (metres), features f32 [N,3] (colours), labels int [N] (raw), scene_offsets int32
+    [S+1], ds_params f64 [S, MINK_VOXDS_PARAMS], class_lut int [NUM_LABELS] (raw label -> class); optional color_params f64
+    [S, MINK_COLORAUG_PARAMS], aug_params f64 [S, MINK_SEGAUG_PARAMS] (host), aug_streams, aug_seed.
+    Returns (coords f32 [k,4], feats f32 [k,3], labels int64 [k] (classes), raw row int32 [k] of every row); with
+    `count_async=True` full-length buffers and (pinned host status int32 [4], event) instead, for the caller to slice
+    (`points_status_check` on the status).  Rows past the representatives run through the geometric program as one more
+    scene whose dropout ratio (2) removes every row."""
+    import torch
+
+    from ..co3d_3d.src.data.seg_transforms import SEG
+
+    coords, feats = batch["coordinates"], batch["features"]
+    if not coords.is_cuda:
+        raise RuntimeError("the point-cloud input is prepared on the GPU: move the batch to cuda first")
+    n, dev = coords.shape[0], coords.device
+    offs = batch["scene_offsets"].to(dev, torch.int32)
+    n_scenes = offs.numel() - 1
+    c, f, raw, src, ds_offs, ds_status = voxel_downsample_batch(coords.float(), feats.float(), batch["labels"], offs, batch["ds_params"])
+    lut = batch["class_lut"].to(dev, torch.int64)
+    ignore = batch["ds_params"][0, 2]  # MINK_VOXDS_IGNORE
+    raw = raw.long()
+    labels = torch.where((raw >= 0) & (raw < lut.numel()), lut[raw.clamp(0, lut.numel() - 1)], ignore.to(dev, torch.int64))
+    if "color_params" in batch:
+        color_augment_batch(f, ds_offs, batch["color_params"], batch["aug_streams"], batch["aug_seed"], src, offs)
+    status = torch.zeros(4, dtype=torch.int32, device=dev)
+    status[3:] = ds_status[1:]
+    if "aug_params" in batch:
+        P = batch["aug_params"].detach().cpu().numpy().astype(np.float64) if torch.is_tensor(batch["aug_params"]) else np.array(batch["aug_params"], np.float64)
+        sink = np.zeros((1, SEG["PARAMS"]), np.float64)
+        for M in ("A0", "A1", "B"):
+            sink[0, SEG[M]:SEG[M] + 9] = np.eye(3).reshape(-1)
+        sink[0, SEG["DROPOUT"]] = 2.0  # (coins are < 1: the tail past the representatives is dropped)
+        streams = torch.cat([batch["aug_streams"].to(dev, torch.int32), torch.zeros(1, dtype=torch.int32, device=dev)])
+        c, f, rows, seg_status = _augment_seg_launch(c, f, ds_offs, np.concatenate([P, sink]), streams, batch["aug_seed"],
+                                                     [-1] * f.shape[1])
+        rows = rows.long().clamp_(0, max(n - 1, 0))  # (rows past the survivors are not written: any index will do there)
+        labels, src = labels[rows], src[rows]
+        status[:3] = seg_status
+    else:
+        status[0] = ds_status[0]
     if count_async:
-        host = torch.empty(3, dtype=torch.int32, pin_memory=True)
+        host = torch.empty(4, dtype=torch.int32, pin_memory=True)
         host.copy_(status, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        return out_c, out_f, rows, (host, ev)
+        return c, f, labels, src, (host, ev)
     st = status.cpu()
-    seg_status_check(st)
+    points_status_check(st)
     k = int(st[0])
-    return out_c[:k], out_f[:k], rows[:k]
+    return c[:k], f[:k], labels[:k], src[:k]
 
 
 def kaiming_normal_(tensor, a=0, mode="fan_in", nonlinearity="leaky_relu"):

@@ -1,0 +1,184 @@
+"""-m gpu: the ScanNet point-cloud input on the device (`mink_voxel_downsample_scenes`, `mink_color_augment_scenes`,
+data/scannet.py ScannetDataset) against the numpy restatement (tests/pc_restate.py): representatives, their order,
+coordinates, colours and voted labels bit for bit over 8 scenes (degenerate ones included), the colour ops, bitwise
+repeatability, the labels the training step sees under the full scannet_semseg.gin recipe, and two training steps plus a
+validation pass through `python -m nerf_downstream_amd.co3d_3d.train`."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from nerf_downstream_amd.co3d_3d.src.data import seg_transforms as ST
+from pc_restate import color_program, downsample, synthetic_scene, write_scannet_tree
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.join(os.path.dirname(__file__), "..")
+CFG = os.path.join(ROOT, "nerf_downstream_amd", "co3d_3d", "configs")
+SEED = 0x0DDC0FFEE1234567
+
+
+def _scenes():
+    """8 scenes: ordinary ones, an empty one, one that falls into a single voxel, one with negative coordinates and
+    conflicting labels on a coarse grid, one left un-down-sampled (q = 0)."""
+    rng = np.random.default_rng(4)
+    sc = [synthetic_scene(rng, int(rng.integers(20_000, 60_000))) for _ in range(4)]
+    sc.append((np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros(0, np.int32)))
+    n = 777
+    sc.append(((rng.random((n, 3)) * 0.0099).astype(np.float32), rng.integers(0, 256, (n, 3)).astype(np.float32),
+               np.full(n, 12, np.int32)))
+    xyz = (rng.random((5000, 3)) * 2 - 1.5).astype(np.float32)
+    sc.append((xyz, rng.integers(0, 256, (5000, 3)).astype(np.float32), rng.integers(0, 3, 5000).astype(np.int32)))
+    sc.append(synthetic_scene(rng, 3000))
+    q = [0.01, 0.01, 0.02, 0.005, 0.01, 0.01, 0.25, 0.0]
+    return sc, q
+
+
+def _batch(scenes, q, voxel=0.02, ignore=-100):
+    offs = np.concatenate([[0], np.cumsum([len(s[0]) for s in scenes])]).astype(np.int32)
+    coords = np.concatenate([np.concatenate([np.full((len(s[0]), 1), b, np.float32), s[0]], 1) for b, s in enumerate(scenes)])
+    P = np.zeros((len(scenes), 4))
+    P[:, 0], P[:, 1], P[:, 2] = q, voxel, ignore
+    dev = torch.device("cuda")
+    return {"coordinates": torch.from_numpy(coords).to(dev), "features": torch.from_numpy(np.concatenate([s[1] for s in scenes])).to(dev),
+            "labels": torch.from_numpy(np.concatenate([s[2] for s in scenes]).astype(np.int64)).to(dev),
+            "scene_offsets": torch.from_numpy(offs).to(dev), "ds_params": torch.from_numpy(P).to(dev)}, offs
+
+
+def _downsample(b):
+    from nerf_downstream_amd.minkowski.utils import voxel_downsample_batch
+
+    out = voxel_downsample_batch(b["coordinates"], b["features"], b["labels"], b["scene_offsets"], b["ds_params"])
+    torch.cuda.synchronize()
+    return [t.cpu().numpy() for t in out]
+
+
+def test_downsample_matches_restatement_bit_for_bit():
+    scenes, q = _scenes()
+    b, offs = _batch(scenes, q)
+    c, f, lab, rows, doffs, status = _downsample(b)
+    assert status[1] == 0
+    assert doffs[-1] == offs[-1] and doffs[-2] == status[0]
+    for s, (xyz, rgb, raw) in enumerate(scenes):
+        reps, rc, rl = downsample(xyz, raw, q[s], 0.02, -100)
+        lo, hi = doffs[s], doffs[s + 1]
+        assert hi - lo == len(reps), s
+        assert np.array_equal(rows[lo:hi] - offs[s], reps), s
+        assert np.array_equal(c[lo:hi, 0], np.full(len(reps), s, np.float32))
+        assert np.array_equal(c[lo:hi, 1:].view(np.uint32), rc.view(np.uint32)), s
+        assert np.array_equal(f[lo:hi], rgb[reps]) and np.array_equal(lab[lo:hi], rl), s
+    assert len(downsample(*scenes[5][0::2], 0.01, 0.02, -100)[0]) == 1  # (the single-voxel scene)
+    assert (lab[doffs[6]:doffs[7]] == -100).any()  # (conflicting labels voted away)
+
+
+def test_colour_ops_match_restatement():
+    from nerf_downstream_amd.minkowski.utils import color_augment_batch
+
+    scenes, q = _scenes()
+    b, offs = _batch(scenes, q)
+    c, f, lab, rows, doffs, status = _downsample(b)
+    rng = np.random.default_rng(9)
+    P = np.zeros((len(scenes), ST.COLOR["PARAMS"]))
+    for s in range(len(scenes)):
+        ops = [("translate", (rng.random(3) - 0.5) * 255 * 2 * 0.3), ("jitter", 0.05 * 255),
+               ("normalize", np.float32([128, 127, 126]), np.float32([256, 200, 255])), ("translate", rng.random(3))][: 1 + s % 4]
+        if s % 2:
+            ops = ops[::-1]
+        P[s] = ST.compile_color_program(ops)
+    streams = rng.integers(0, 2 ** 31, len(scenes)).astype(np.int32)
+    dev = torch.device("cuda")
+    feats = torch.from_numpy(f).to(dev)
+    color_augment_batch(feats, torch.from_numpy(doffs).to(dev), torch.from_numpy(P).to(dev), torch.from_numpy(streams).to(dev), SEED,
+                        torch.from_numpy(rows).to(dev), b["scene_offsets"])
+    got = feats.cpu().numpy()
+    jitter_err = 0
+    for s in range(len(scenes)):
+        lo, hi = doffs[s], doffs[s + 1]
+        want = color_program(f[lo:hi], P[s], rows[lo:hi] - offs[s], np.uint32(streams[s]), SEED)
+        if any(P[s][ST.COLOR["OPS"] + k * ST.COLOR["OP_STRIDE"]] == ST.COLOR["JITTER"] for k in range(int(P[s][0]))):
+            # (normals from the restated Philox draws; float64 log / cos may differ in the last bit from numpy's)
+            jitter_err = max(jitter_err, float(np.abs(got[lo:hi] - want).max(initial=0)))
+            assert np.allclose(got[lo:hi], want, rtol=0, atol=1e-4), s
+        else:
+            assert np.array_equal(got[lo:hi].view(np.uint32), want.view(np.uint32)), s
+    assert np.array_equal(got[doffs[-2]:], f[doffs[-2]:])  # rows past the representatives are not touched
+    assert jitter_err < 1e-4
+
+
+def _recipe_batch(root, n_scenes=4, seed=0):
+    """One collated training batch of ScannetDataset under scannet_semseg.gin (a 3 m crop, so that it cuts)."""
+    import random
+
+    from nerf_downstream_amd import gin_lite as gin
+    from nerf_downstream_amd.co3d_3d.src.data.scannet import ScannetDataset
+    from nerf_downstream_amd.co3d_3d.src.data.utils import collate_mink
+
+    rng = np.random.default_rng(seed)
+    scenes = [synthetic_scene(rng, int(rng.integers(30_000, 60_000))) for _ in range(n_scenes)]
+    write_scannet_tree(root, scenes)
+    gin.clear_config()
+    try:
+        gin.parse_config_files_and_bindings([f"{CFG}/scannet_semseg.gin"], ["RandomCrop.x=150", "RandomCrop.y=150", "RandomCrop.z=150"])
+        ds = ScannetDataset("train", data_root=root)
+        random.seed(seed), np.random.seed(seed)
+        batch = collate_mink([ds[i] for i in range(n_scenes)])
+    finally:
+        gin.clear_config()
+    return batch, scenes
+
+
+def _to_cuda(batch):
+    return {k: (v.cuda() if torch.is_tensor(v) and k != "aug_params" else v) for k, v in batch.items()}
+
+
+def test_full_recipe_is_repeatable_and_labels_follow_the_votes(tmp_path):
+    from nerf_downstream_amd.minkowski.utils import prepare_point_batch
+
+    batch, scenes = _recipe_batch(str(tmp_path))
+    out1 = [t.cpu() for t in prepare_point_batch(_to_cuda(batch))]
+    out2 = [t.cpu() for t in prepare_point_batch(_to_cuda(batch))]
+    for a, b in zip(out1, out2):
+        assert a.dtype == b.dtype and torch.equal(a.view(torch.uint8) if a.is_floating_point() else a, b.view(torch.uint8) if b.is_floating_point() else b)
+    coords, feats, labels, src = out1
+    offs = batch["scene_offsets"].numpy()
+    lut = batch["class_lut"].numpy()
+    assert 0 < len(labels) < offs[-1]
+    b_of = coords[:, 0].numpy().astype(np.int64)
+    assert (np.diff(b_of) >= 0).all()
+    for s, (xyz, rgb, raw) in enumerate(scenes):
+        reps, _, voted = downsample(xyz, raw, 0.01, 0.02, -100)
+        vote_of = dict(zip(reps.tolist(), voted.tolist()))
+        mine = b_of == s
+        rows = src.numpy()[mine] - offs[s]
+        want = np.array([vote_of[r] for r in rows.tolist()], np.int64)
+        want = np.where((want >= 0) & (want < 41), lut[np.clip(want, 0, 40)], -100)
+        assert np.array_equal(labels.numpy()[mine], want), s
+    assert torch.isfinite(feats).all() and feats.abs().max() <= 0.6  # (normalised colours)
+
+
+def test_train_two_steps_and_validate_with_scannet_semseg_config(tmp_path):
+    rng = np.random.default_rng(11)
+    scenes = [synthetic_scene(rng, 20_000) for _ in range(3)]
+    write_scannet_tree(str(tmp_path), scenes)
+    save = tmp_path / "run"
+    cmd = [sys.executable, "-m", "nerf_downstream_amd.co3d_3d.train", "--ginc", f"{CFG}/scannet_semseg.gin", "--ginc",
+           f"{CFG}/res16unet.gin", "--save_path", str(save), "--run_name", "pc", "--seed", "3"]
+    for b in ["train.max_steps=2", "train.val_every_n_steps=2", "train.log_every_n_steps=1", "train.batch_size=2",
+              "train.val_batch_size=1", "train.train_num_workers=0", "train.val_num_workers=0", "train.lr=0.01",
+              f"ScannetDataset.data_root='{tmp_path}'", "get_model.name='Res16UNet14A'"]:
+        cmd += ["--ginb", b]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    import csv
+    import glob
+
+    logs = glob.glob(str(save / "**" / "*.csv"), recursive=True)
+    assert logs, r.stderr[-2000:]
+    rows = [row for f in logs for row in csv.DictReader(open(f))]
+    losses = [float(row["train/loss"]) for row in rows if row.get("train/loss")]
+    assert len(losses) == 2 and all(np.isfinite(losses)), rows
+    vals = [row for row in rows if row.get("val/mIoU")]
+    assert vals and all(np.isfinite(float(v["val/loss"])) for v in vals), rows
