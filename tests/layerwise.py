@@ -1,5 +1,6 @@
-"""Teacher-forced, operator-by-operator float64 references of the Mink-ResNet trunk, and the comparators that judge a kernel's
-output against them (tests/test_gpu_layerwise.py on the GPU, tests/test_layerwise_cpu.py for the negative controls).
+"""Teacher-forced, operator-by-operator float64 references of the Mink-ResNet trunk and of Res16UNet, and the comparators that
+judge a kernel's output against them (tests/test_gpu_layerwise.py and tests/test_gpu_seg_layerwise.py on the GPU,
+tests/test_layerwise_cpu.py and tests/test_seg_layerwise_cpu.py for the negative controls).
 
 Every reference is plain torch float64 on whatever device its inputs are on, fed with the operands the kernel itself read
 (the HIP run's own stored activations, gradients, statistics and ReLU decisions): no error carries over from one layer to
@@ -193,6 +194,112 @@ def stem_wgrad_operand(g_pool, y, mean, invstd, gamma, beta, dgamma, dbeta, in2o
     return (gamma * invstd) * fma32(-(dgamma * inv_n), xh, inner)
 
 
+# ------------------------------------------------------------------------------------------------ segmentation (Res16UNet)
+# The transposed convolution is stated through the fine -> coarse table of the ordinary convolution it inverts:
+# nbr[n_coarse, K] = fine row of coarse row o at offset k (oracle/maps.py kernel_map_table(fine, coarse, offsets(2, ts))).
+def tconv_fwd(x, w, nbr, n_fine):
+    """y[nbr[o, k]] += x[o] @ w[k]: coarse rows x [n_coarse, cin] up-sampled onto the n_fine rows (scattered through nbr)."""
+    check_table(nbr, n_fine)
+    assert x.shape[0] == nbr.shape[0]
+    y = torch.zeros(n_fine, w.shape[2], dtype=torch.float64, device=x.device)
+    for k in range(nbr.shape[1]):
+        o, i = _valid(nbr, k)
+        if o.numel():
+            y.index_add_(0, i, x[o].double() @ w[k].double())
+    return y
+
+
+def tconv_dgrad(gy, w, nbr):
+    """dX of tconv_fwd: gx[o] = sum_k gy[nbr[o, k]] @ w[k]^T (gathered through nbr)."""
+    check_table(nbr, gy.shape[0])
+    gx = torch.zeros(nbr.shape[0], w.shape[1], dtype=torch.float64, device=gy.device)
+    for k in range(nbr.shape[1]):
+        o, i = _valid(nbr, k)
+        if o.numel():
+            gx.index_add_(0, o, gy[i].double() @ w[k].double().t())
+    return gx
+
+
+def tconv_wgrad(x, gy, nbr):
+    """dW of tconv_fwd: dW[k] = x[o]^T @ gy[nbr[o, k]] over the valid pairs."""
+    check_table(nbr, gy.shape[0])
+    assert x.shape[0] == nbr.shape[0]
+    gw = torch.zeros(nbr.shape[1], x.shape[1], gy.shape[1], dtype=torch.float64, device=x.device)
+    for k in range(nbr.shape[1]):
+        o, i = _valid(nbr, k)
+        if o.numel():
+            gw[k] = x[o].double().t() @ gy[i].double()
+    return gw
+
+
+def pointwise_fwd(x, w, bias=None):
+    """1x1x1 stride-1 convolution (kernel [cin, cout]) [+ bias [1, cout]]."""
+    y = x.double() @ w.double().reshape(x.shape[1], -1)
+    return y if bias is None else y + bias.double().reshape(1, -1)
+
+
+def pointwise_dgrad(gy, w):
+    return gy.double() @ w.double().reshape(-1, gy.shape[1]).t()
+
+
+def pointwise_wgrad(x, gy):
+    return x.double().t() @ gy.double()
+
+
+def bias_grad(gy):
+    """d bias of y = conv(x) + bias: the column sums of dY, [1, cout]."""
+    return gy.double().sum(0, keepdim=True)
+
+
+def cat_fwd(*parts):
+    """ME.cat: the feature columns of tensors on one coordinate map, side by side."""
+    assert len({p.shape[0] for p in parts}) == 1
+    return torch.cat([p.double() for p in parts], 1)
+
+
+def cat_bwd(g, widths):
+    """The gradient of each part of a cat: its own columns of g."""
+    assert g.shape[1] == sum(widths)
+    return list(g.double().split(list(widths), 1))
+
+
+def sparse_mean(f, inverse, n_unique):
+    """TensorField.sparse(): every voxel's feature is the mean of the field rows that fall into it (inverse[row] = voxel)."""
+    check_table(inverse[:, None], n_unique)
+    assert inverse.shape[0] == f.shape[0] and int(inverse.min()) >= 0
+    inv = inverse.long()
+    s = torch.zeros(n_unique, f.shape[1], dtype=torch.float64, device=f.device).index_add_(0, inv, f.double())
+    cnt = torch.zeros(n_unique, dtype=torch.float64, device=f.device).index_add_(0, inv, torch.ones_like(inv, dtype=torch.float64))
+    assert bool((cnt > 0).all()), "a voxel without field rows"
+    return s / cnt[:, None]
+
+
+def slice_fwd(y, inverse):
+    """SparseTensor.slice(field): every field row reads its voxel's features."""
+    check_table(inverse[:, None], y.shape[0])
+    return y.double()[inverse.long()]
+
+
+def slice_bwd(g, inverse, n_unique):
+    """dY of slice_fwd: the field rows' gradients summed onto their voxels."""
+    return sum_pool(g, inverse, n_unique)
+
+
+def bn_eval_fwd(y, running_mean, running_var, gamma, beta, residual=None, eps=1e-5):
+    """Eval-mode batch norm (running statistics) [+ residual]: the pre-activation."""
+    z = (y.double() - running_mean.double()) * (running_var.double() + eps).rsqrt() * gamma.double() + beta.double()
+    return z if residual is None else z + residual.double()
+
+
+def cross_entropy_grad(logits, labels, ignore_index=-100):
+    """d mean cross entropy / d logits over the rows whose label is not ignored, float64."""
+    keep = labels != ignore_index
+    p = torch.softmax(logits.double(), 1)
+    p[keep, labels[keep].long()] -= 1.0
+    p[~keep] = 0.0
+    return p / max(int(keep.sum()), 1)
+
+
 # ------------------------------------------------------------------------------------------------ comparators
 @dataclass
 class Record:
@@ -228,6 +335,9 @@ def check_conv(layer, op, got, ref, rounded=frozenset(), ref_other=None):
     rounds, rounded where it does not); where the two references are more than DISCRIMINATE bounds apart, the kernel must
     also sit OUTSIDE the bound of the other -- a kernel that silently rounds differently from the table fails here.
     -> [Record] (the second one, "declared vs other", only when it applies)."""
+    if tuple(got.shape) != tuple(ref.shape):  # (e.g. a padded channel's gradient handed back with the rest)
+        return [Record(layer, op, got.shape[0], tuple(got.shape), _rnd_name(rounded), float("inf"), CONV_REL, False,
+                       f"shape {tuple(got.shape)}, reference {tuple(ref.shape)}")]
     rel, mx = conv_errors(got, ref)
     ok = rel <= CONV_REL and mx <= CONV_MAX
     recs = [Record(layer, op, got.shape[0], tuple(got.shape), _rnd_name(rounded), rel, CONV_REL, ok, f"max {mx:.1e}")]
@@ -245,7 +355,10 @@ def check_conv(layer, op, got, ref, rounded=frozenset(), ref_other=None):
 
 
 def check_scaled(layer, op, got, ref, scale, bound=NORM_BOUND, rows=None, mask=None, note=""):
-    """max |got - ref| <= bound * scale (elements where `mask` is False excluded)."""
+    """max |got - ref| <= bound * scale (elements where `mask` is False excluded).  bound=0: bit for bit (copies)."""
+    if tuple(got.shape) != tuple(ref.shape):
+        return [Record(layer, op, rows if rows is not None else got.shape[0], tuple(got.shape), "fp32", float("inf"), bound, False,
+                       f"shape {tuple(got.shape)}, reference {tuple(ref.shape)}")]
     d = (got.double() - ref.double()).abs()
     if mask is not None:
         d = d[mask]

@@ -68,6 +68,44 @@ def synthetic_scene(rng, n, label_noise=0.05):
     return xyz, colors, labels.astype(np.int32)
 
 
+def room_scene(rng, n_points, other_labels=0.02):
+    """A ScanNet-like room sampled on SURFACES, not in a volume: a floor, three or four walls and boxes as furniture (axis-
+    aligned and turned about z; top and four sides).  Points are spread over the surfaces by area, so a 2 cm voxel has the
+    in-plane neighbours a scanned surface gives it.  Colours are smooth over each surface plus noise, raw labels 0..40 are
+    per surface, and a fraction `other_labels` of the points carries another label."""
+    X, Y, H = rng.uniform(4.5, 6.5), rng.uniform(4.0, 6.0), rng.uniform(2.4, 3.0)
+    quads = [((0, 0, 0), (X, 0, 0), (0, Y, 0), 2)]  # (origin, edge u, edge v, raw label): the floor
+    walls = [((0, 0, 0), (X, 0, 0)), ((0, Y, 0), (X, 0, 0)), ((0, 0, 0), (0, Y, 0)), ((X, 0, 0), (0, Y, 0))]
+    for j in rng.permutation(4)[: int(rng.integers(3, 5))]:
+        quads.append((walls[j][0], walls[j][1], (0, 0, H), 1))
+    for _ in range(int(rng.integers(5, 9))):  # furniture
+        w, d, h = rng.uniform(0.4, 1.8), rng.uniform(0.4, 1.2), rng.uniform(0.4, 1.6)
+        cx, cy = rng.uniform(0.6, X - 0.6), rng.uniform(0.6, Y - 0.6)
+        a = rng.uniform(0, np.pi / 2) if rng.random() < 0.5 else 0.0
+        u, v = np.array([np.cos(a), np.sin(a), 0.0]), np.array([-np.sin(a), np.cos(a), 0.0])
+        o = np.array([cx, cy, 0.0]) - 0.5 * w * u - 0.5 * d * v
+        lab = int(rng.integers(3, 41))
+        z = np.array([0.0, 0.0, h])
+        quads += [(o + z, w * u, d * v, lab), (o, w * u, z, lab), (o + d * v, w * u, z, lab), (o, d * v, z, lab),
+                  (o + w * u, d * v, z, lab)]
+    area = np.array([np.linalg.norm(np.cross(np.asarray(q[1], float), np.asarray(q[2], float))) for q in quads])
+    count = rng.multinomial(n_points, area / area.sum())
+    xyz, colors, labels = [], [], []
+    for (o, eu, ev, lab), k in zip(quads, count):
+        st = rng.random((k, 2))
+        xyz.append(np.asarray(o, float) + st[:, :1] * np.asarray(eu, float) + st[:, 1:] * np.asarray(ev, float))
+        base, grad = rng.uniform(40, 215, 3), rng.uniform(-30, 30, (2, 3))
+        colors.append(np.clip(base + st @ grad + rng.normal(0, 6, (k, 3)), 0, 255))
+        labels.append(np.full(k, lab, np.int64))
+    xyz = np.concatenate(xyz) + rng.normal(0, 0.002, (n_points, 3))  # (sensor noise off the surface)
+    labels = np.concatenate(labels)
+    other = rng.random(n_points) < other_labels
+    labels[other] = rng.integers(0, 41, int(other.sum()))
+    order = rng.permutation(n_points)
+    return (xyz[order].astype(np.float32), np.concatenate(colors)[order].astype(np.float32),
+            labels[order].astype(np.int32))
+
+
 def write_scannet_tree(root, scenes, phase_files=("scannetv2_train.txt", "scannetv2_val.txt"), with_ext=(False, True)):
     """Write scenes [(xyz, colours, labels)] as binary PLY files under root and list them, without and with `.ply`, in the
     split files."""

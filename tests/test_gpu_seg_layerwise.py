@@ -1,0 +1,500 @@
+"""-m gpu: teacher-forced per-operator parity of Res16UNet at ScanNet training shapes.
+
+tests/test_gpu_unet.py holds the segmentation network to the CPU oracle end to end on small shell scenes, where ReLU flips
+carried from layer to layer force loose gradient bounds and the planners pick other launch forms than training does.  Here
+one training batch is built as training builds it -- 8 surface-sampled rooms (pc_restate.room_scene) read through
+ScannetDataset under scannet_semseg.gin's train recipe, collated, prepared on the device by process_input -- and run through
+Res16UNet with res16unet.gin's LAYERS / PLANES (3 -> 20 channels): forward, slice, per-point cross entropy, backward.  Forward
+hooks and tensor hooks keep every module's input features, output features and the gradients of both; every operator is then
+recomputed in float64 from the tensors the HIP run itself read (tests/layerwise.py), over the oracle's own tables
+(oracle/maps.py), which are first compared bit for bit with every table the network used.
+
+Composites: where one tensor feeds several consumers (a block input: conv1 and the residual or the 1x1 shortcut; an encoder
+output: the next down-sampling convolution and a cat), the gradient autograd accumulated is checked against the float64 sum
+of every consumer's share, each computed from that consumer's own output gradient."""
+import os
+import random
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import layerwise as LW
+from pc_restate import room_scene, write_scannet_tree
+
+pytestmark = [pytest.mark.gpu, pytest.mark.long]
+
+ROOT = os.path.join(os.path.dirname(__file__), "..")
+CFG = os.path.join(ROOT, "nerf_downstream_amd", "co3d_3d", "configs")
+POINTS = 300_000  # per scene: ~2 x 10^5 voxels of 2 cm before the crop
+BK, BN = 32, 64  # csrc/conv.hip:23-24 (reduction chunk, output columns per workgroup)
+CKP = 9  # csrc/conv.hip:826 (offsets per workgroup of the row-compacted kernel)
+# the 4 cats: (block that consumes it, the up-sampling unit, the encoder output it is joined with)
+CATS = [("block5", "convtr4p16s2", "block3"), ("block6", "convtr5p8s2", "block2"), ("block7", "convtr6p4s2", "block1"),
+        ("block8", "convtr7p2s2", "conv0p1s1")]
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+# ------------------------------------------------------------------------------------------------ inputs
+def _scannet_batch(root, phase, n_scenes, seed):
+    """One collated batch of ScannetDataset under scannet_semseg.gin (train: the full recipe, crop 250^3 included)."""
+    from nerf_downstream_amd import gin_lite as gin
+    from nerf_downstream_amd.co3d_3d.src.data.scannet import ScannetDataset
+    from nerf_downstream_amd.co3d_3d.src.data.utils import collate_mink
+
+    os.makedirs(root, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    write_scannet_tree(root, [room_scene(rng, POINTS) for _ in range(n_scenes)])
+    gin.clear_config()
+    try:
+        gin.parse_config_files_and_bindings([f"{CFG}/scannet_semseg.gin"], [])
+        ds = ScannetDataset(phase, data_root=root)
+        random.seed(seed), np.random.seed(seed)
+        batch = collate_mink([ds[i] for i in range(n_scenes)])
+    finally:
+        gin.clear_config()
+    return {k: (v.cuda() if torch.is_tensor(v) and k != "aug_params" else v) for k, v in batch.items()}
+
+
+def _model(fused):
+    from nerf_downstream_amd import gin_lite as gin
+    from nerf_downstream_amd.co3d_3d.src.models import get_model
+
+    gin.clear_config()
+    try:
+        gin.parse_config_files_and_bindings([f"{CFG}/scannet_semseg.gin", f"{CFG}/res16unet.gin"], [])
+        torch.manual_seed(5)
+        model = get_model("Res16UNet", 3, 20).cuda()
+    finally:
+        gin.clear_config()
+    assert model.LAYERS == (1, 1, 2, 2, 2, 2, 1, 1) and model.PLANES == (32, 48, 64, 96, 96, 96, 64, 64)
+    if not fused:
+        for m in model.modules():
+            for attr in ("_fused", "fused"):
+                if hasattr(m, attr):
+                    setattr(m, attr, False)
+    return model
+
+
+# ------------------------------------------------------------------------------------------------ capture
+class Capture:
+    """Forward hooks on every convolution, batch norm, ReLU, residual block and unit (a module called twice -- a block's
+    ReLU in the plain path -- keeps one record per call), and a tensor hook on every input / output feature matrix: the
+    gradient autograd accumulated for it, all consumers summed."""
+
+    def __init__(self, model):
+        from nerf_downstream_amd import minkowski as ME
+        from nerf_downstream_amd.co3d_3d.src.models.mink.modules.resnet_block import BasicBlock
+        from nerf_downstream_amd.co3d_3d.src.models.mink.res16unet import _Unit
+
+        self.rec, self.grads, self.keep, self.names = {}, {}, {}, {}
+        kinds = (ME.MinkowskiConvolution, ME.MinkowskiBatchNorm, ME.MinkowskiReLU, BasicBlock, _Unit)
+        self.handles = [m.register_forward_hook(self._hook(n), with_kwargs=True) for n, m in model.named_modules()
+                        if isinstance(m, kinds)]
+        self.handles.append(model.register_forward_hook(self._top, with_kwargs=True))
+
+    def watch(self, t, name):
+        if id(t) not in self.keep:
+            self.keep[id(t)], self.names[id(t)] = t, name
+            if t.requires_grad:
+                t.register_hook(lambda g, k=id(t): self.grads.__setitem__(k, g.detach().clone()))
+
+    def _hook(self, name):
+        def hook(m, args, kwargs, out):
+            x = args[0]
+            r = {"x": x.F, "y": out.F, "ts_in": x.tensor_stride[0], "ts_out": out.tensor_stride[0], "kw": kwargs}
+            res = kwargs.get("residual")
+            if res is not None:
+                r["res"] = res.F
+            fn = out.F.grad_fn
+            if fn is not None and type(fn).__name__ == "BatchNormFunctionBackward":
+                r["saved"] = fn.saved_tensors  # (x, y, mean, invstd, gamma): the statistics the kernel normalised with
+            self.watch(r["x"], name + " in"), self.watch(r["y"], name + " out")
+            self.rec.setdefault(m, []).append(r)
+
+        return hook
+
+    def _top(self, m, args, kwargs, out):
+        self.field, self.logits = args[0], out
+        self.watch(out, "logits")
+
+    def close(self):
+        for h in self.handles:
+            h.remove()
+
+
+# ------------------------------------------------------------------------------------------------ maps
+def _oracle_tables(maps, field):
+    """Every coordinate level, stride map, neighbour table (+ transposed), class permutation and the field's inverse map,
+    bit for bit against oracle/mink_maps.c from the field's own coordinates.  -> (oracle tables on the device keyed as the
+    manager keys them, levels {ts: rows}, inverse)."""
+    m = field.coordinate_manager
+    q = maps.quantize(field.C.cpu().numpy())
+    ui, inv = maps.unique(q)
+    want = {1: q[ui]}
+    assert np.array_equal(m.field_inverse.cpu().numpy(), inv)
+    ts = 1
+    while 2 * ts in m.levels:
+        want[2 * ts], i2o = maps.stride_map(want[ts], 2 * ts)
+        assert np.array_equal(m.in2out[(ts, 2 * ts)].cpu().numpy(), i2o), ts
+        ts *= 2
+    assert sorted(want) == sorted(m.levels) == [1, 2, 4, 8, 16], sorted(m.levels)
+    for t, c in want.items():
+        assert m.levels[t].n == c.shape[0] and np.array_equal(m.levels[t].coords.cpu().numpy(), c), t
+    tabs, seen = {}, set()
+    for key, ent in m.tables.items():
+        if key[0] == "perm":
+            _, t, pad = key
+            want_p = maps.class_partition(want[t], t, pad)
+            assert np.array_equal(ent.cpu().numpy(), want_p), key
+            tabs[key] = torch.from_numpy(want_p).cuda()
+        elif key[0] == "ident":
+            assert torch.equal(ent.view(-1).cpu(), torch.arange(ent.shape[0], dtype=torch.int32)), key
+        else:
+            ts_in, ts_out, ks, dil = key
+            nbr = maps.kernel_map_table(want[ts_in], want[ts_out], maps.kernel_offsets(ks, ts_in, dil))
+            assert np.array_equal(ent[0].cpu().numpy(), nbr), key
+            nbr_t = None
+            if ent[1] is not None:
+                nbr_t = maps.transpose_table(nbr, want[ts_in].shape[0])
+                assert np.array_equal(ent[1].cpu().numpy(), nbr_t), key
+                seen.add(("transposed",) + key)
+            tabs[key] = (torch.from_numpy(nbr).cuda(), None if nbr_t is None else torch.from_numpy(nbr_t).cuda())
+        seen.add(key)
+    levels = {t: c.shape[0] for t, c in want.items()}
+    return tabs, levels, torch.from_numpy(inv).cuda(), seen
+
+
+# ------------------------------------------------------------------------------------------------ launch forms
+def _launch_forms(L, n_rows, K, cin, cout, perm, wt, stats):
+    """The launch form gather_gemm_impl (csrc/conv.hip) takes for one gather-GEMM under fp32 math, restated from its shapes
+    (torch allocations are 16-byte aligned and rows contiguous, so the alignment terms hold).  cin / cout are the GEMM's:
+    a data gradient's are the convolution's cout / cin."""
+    ks = int(L.mink_conv_plan(n_rows, K, cin, cout, int(perm)))  # (functional.py _plan_ksplit: n_rows = the permutation's length)
+    vec = cin % 4 == 0 and (wt or cout % 4 == 0)  # conv.hip:3037-3038
+    # compact_perm_shape (conv.hip:2965) and the class-permuted branch (conv.hip:3046)
+    if perm and not stats and vec and K >= 8 and cin >= 64 and cin % BK == 0 and cout % BN == 0:
+        ncc = cin // BK
+        return {"class-permuted compact"} | ({"split-K"} if _cdiv(ncc, _cdiv(ncc, ks)) > 1 else set())
+    kper = _cdiv(K, ks)
+    zs = _cdiv(K, kper)  # conv.hip:3034
+    forms = {"split-K"} if zs > 1 else set()
+    if vec and not perm and K >= 8 and kper <= CKP and cin >= 64 and cin % BK == 0 and cout % BN == 0:  # conv.hip:3092
+        forms.add("row-compacted")
+    elif vec:  # gather_gemm2_kernel: `stage` = a row permutation (conv.hip:3138)
+        forms.add("staged gather_gemm2" if perm else "dense gather_gemm2")
+        if cin % BK:
+            forms.add("channel tail")
+    else:
+        forms.add("scalar gather_gemm")
+    if stats:  # conv.hip:3042-3045
+        if zs == 1 and vec:
+            forms.add("stats direct")
+        elif zs > 1 and cout % 4 == 0 and cout <= 1024:
+            forms.add("stats split")
+        else:
+            forms.add("stats by reduction")
+    return forms
+
+
+# ------------------------------------------------------------------------------------------------ checks
+def _other(rounded, names):
+    return frozenset() if rounded else frozenset(names)
+
+
+def _conv_recs(layer, op, got, fn, ops):
+    """fp32 math: float64 on the operands as stored, with every operand rounded to bf16 as the discriminator."""
+    r = LW.rounded_operands("fwd", 27, "fp32")
+    return LW.check_conv(layer, op, got, fn(**LW.apply_rounding(ops, r)), r, fn(**LW.apply_rounding(ops, _other(r, ops))))
+
+
+class Contrib:
+    """The float64 share of every consumer in the gradient of a tensor, for the composite check."""
+
+    def __init__(self):
+        self.parts = {}
+
+    def add(self, t, label, g, conv=False):
+        self.parts.setdefault(id(t), []).append((label, g, conv))
+
+
+def _check(model, cap, tabs, levels, inverse, L, training, labels=None):
+    from nerf_downstream_amd import minkowski as ME
+    from nerf_downstream_amd.co3d_3d.src.models.mink.modules.resnet_block import BasicBlock
+
+    recs, reach, contrib = [], set(), Contrib()
+    names = {m: n for n, m in model.named_modules()}
+    checked_params, bn_inputs = set(), set()
+    g = cap.grads.get if training else (lambda k: None)
+
+    def one(m):
+        r = cap.rec[m]
+        assert len(r) == 1, names[m]
+        return r[0]
+
+    # ---- field -> sparse tensor (duplicate rows averaged) and slice() back
+    n1 = levels[1]
+    fF = cap.field.F
+    x0 = one(model.conv0p1s1[0])["x"]
+    assert fF.shape[0] > n1, "the batch must carry duplicate rows (.sparse() averages them)"
+    reach.add("segment_mean")
+    ref = LW.sparse_mean(fF, inverse, n1)
+    recs += LW.check_scaled("field", ".sparse() fwd", x0, ref, float(ref.abs().max()), rows=fF.shape[0])
+    yfin = one(model.final)["y"]
+    recs += LW.check_scaled("field", "slice() fwd", cap.logits, LW.slice_fwd(yfin, inverse), 1.0, bound=0.0)
+    reach.add("slice")
+    if training:
+        gl = g(id(cap.logits))
+        ref = LW.cross_entropy_grad(cap.logits, labels)
+        recs += LW.check_scaled("loss", "cross entropy dlogits", gl, ref, float(ref.abs().max()))
+        contrib.add(yfin, "slice() bwd", LW.slice_bwd(gl, inverse, n1))
+
+    # ---- convolutions
+    for m in model.modules():
+        if not isinstance(m, ME.MinkowskiConvolution):
+            continue
+        lay = names[m]
+        r = one(m)
+        x, y, ts_in, ts_out = r["x"], r["y"], r["ts_in"], r["ts_out"]
+        W = m.kernel.detach()
+        gy = g(id(y))
+        cin, cout = m.in_channels, m.out_channels
+        stats = bool(r["kw"].get("bn_stats")) and training and m.bias is None and not m.use_mm
+        if m.use_mm:  # 1x1 shortcuts and the classifier: torch mm forward, streaming weight gradient over an identity table
+            b = None if m.bias is None else m.bias.detach()
+            recs += _conv_recs(lay, "pointwise fwd" + (" + bias" if b is not None else ""), y,
+                               lambda x, w: LW.pointwise_fwd(x, w, b), {"x": x, "w": W})
+            if training:
+                assert x.shape[0] >= 4096
+                reach.add("pointwise")
+                contrib.add(x, lay + " dgrad", LW.pointwise_dgrad(gy, W), conv=True)
+                recs += _conv_recs(lay, "pointwise wgrad", m.kernel.grad, lambda x, dy: LW.pointwise_wgrad(x, dy), {"x": x, "dy": gy})
+                checked_params.add(lay + ".kernel")
+                if b is not None:
+                    ref = LW.bias_grad(gy)
+                    recs += LW.check_scaled(lay, "bias grad", m.bias.grad, ref, LW.reduction_scale(gy), rows=gy.shape[0])
+                    checked_params.add(lay + ".bias")
+            continue
+        assert m.bias is None
+        if isinstance(m, ME.MinkowskiConvolutionTranspose):
+            nbr = tabs[(ts_out, ts_in, m.kernel_size, 1)][0]  # the fine -> coarse table of the convolution it inverts
+            n_fine = levels[ts_out]
+            recs += _conv_recs(lay, "tconv fwd", y, lambda x, w: LW.tconv_fwd(x, w, nbr, n_fine), {"x": x, "w": W})
+            perm = tabs[("perm", ts_out, 128)]
+            f = _launch_forms(L, perm.numel(), 8, cin, cout, True, False, False)
+            reach |= {"class-permuted compact (transposed fwd)" if "class-permuted compact" in f else
+                      "staged gather_gemm2 (transposed fwd)" if "staged gather_gemm2" in f else "transposed fwd: other"}
+            if training:
+                f |= _launch_forms(L, levels[ts_in], 8, cout, cin, False, True, False)
+                contrib.add(x, lay + " tconv dgrad", LW.tconv_dgrad(gy, W, nbr), conv=True)
+                recs += _conv_recs(lay, "tconv wgrad", m.kernel.grad, lambda x, dy: LW.tconv_wgrad(x, dy, nbr), {"x": x, "dy": gy})
+                checked_params.add(lay + ".kernel")
+        else:
+            nbr = tabs[(ts_in, ts_out, m.kernel_size, 1)][0]
+            n_in = levels[ts_in]
+            cin_eff = cin
+            if cin % 4 and not x.requires_grad:  # functional.py ConvolutionFunction.forward: one zero column
+                cin_eff = cin + 4 - cin % 4
+                reach.add(f"stem padded {cin}->{cin_eff}")
+            recs += _conv_recs(lay, "conv fwd", y, lambda x, w: LW.conv_fwd(x, w, nbr), {"x": x, "w": W})
+            f = _launch_forms(L, y.shape[0], W.shape[0], cin_eff, cout, False, False, stats)
+            if training:
+                if x.requires_grad:
+                    if ts_out == ts_in:  # flip_k through the forward table
+                        f |= _launch_forms(L, n_in, W.shape[0], cout, cin, False, True, False)
+                    else:  # the transposed table in parity-class order
+                        ent, perm = tabs[(ts_in, ts_out, m.kernel_size, 1)], tabs[("perm", ts_in, 128)]
+                        assert ent[1] is not None, "the strided data gradient did not get its transposed table"
+                        fd = _launch_forms(L, perm.numel(), W.shape[0], cout, cin, True, True, False)
+                        f |= fd
+                        reach.add("class-permuted dgrad" if fd & {"class-permuted compact", "staged gather_gemm2"} else "strided dgrad: other")
+                        gy64 = gy.double()
+                        a = LW.conv_dgrad(gy64, W, nbr, n_in)
+                        e = LW.conv_errors(LW.conv_dgrad_gather(gy64, W, ent[1], perm=perm), a)[0]
+                        recs.append(LW.Record(lay, "dgrad tables", n_in, tuple(a.shape), "float64", e, 1e-12, e <= 1e-12,
+                                              "transposed + perm vs scatter"))
+                    contrib.add(x, lay + " dgrad", LW.conv_dgrad(gy, W, nbr, n_in), conv=True)
+                recs += _conv_recs(lay, "conv wgrad", m.kernel.grad, lambda x, dy: LW.conv_wgrad(x, dy, nbr), {"x": x, "dy": gy})
+                checked_params.add(lay + ".kernel")
+        if "row-compacted" in f and lay.startswith("conv4p8s2"):
+            reach.add("row-compacted (conv4p8s2)")
+        if "row-compacted" in f and ts_out == ts_in and m.kernel_size == 3:
+            reach.add("row-compacted, stride 1")
+        if "dense gather_gemm2" in f and "split-K" not in f and ts_out == 1 and lay.startswith("block8"):
+            reach.add("dense unsplit at ts 1")
+        if "channel tail" in f and "dense gather_gemm2" in f and lay.startswith(("block5", "block6")):
+            reach.add("dense with channel tail")
+        if "split-K" in f and max(ts_in, ts_out) >= 8:
+            reach.add("split-K at ts 8 / 16")
+        reach |= f & {"stats direct", "stats split"}
+
+    # ---- batch norms (+ ReLU, + residual)
+    for m in model.modules():
+        if not isinstance(m, ME.MinkowskiBatchNorm):
+            continue
+        lay = names[m]
+        r = one(m)
+        y, out, bn = r["x"], r["y"], m.bn
+        relu, res = bool(r["kw"].get("relu")), r.get("res")
+        gamma, beta = bn.weight.detach(), bn.bias.detach()
+        if training:
+            mean, invstd = r["saved"][2], r["saved"][3]
+            recs += LW.check_stats(lay, "norm", mean, invstd, y, bn.eps)
+            z = LW.bn_fwd(y, gamma, beta, res, eps=bn.eps)
+        else:
+            z = LW.bn_eval_fwd(y, bn.running_mean, bn.running_var, gamma, beta, res, eps=bn.eps)
+        op = "norm" + ("+res" if res is not None else "") + ("+relu" if relu else "") + " fwd"
+        if relu:
+            recs += LW.check_relu_out(lay, op, out, z)
+        else:
+            recs += LW.check_scaled(lay, op, out, z, float(z.abs().max()))
+        if training:
+            gout = g(id(out))
+            mask = (out > 0) if relu else None
+            recs += LW.check_bn_bwd(lay, "norm bwd", g(id(y)), bn.weight.grad, bn.bias.grad, gout, y, gamma, beta, mask, eps=bn.eps)
+            bn_inputs.add(id(y))
+            checked_params |= {lay + ".bn.weight", lay + ".bn.bias"}
+            if res is not None:
+                contrib.add(res, lay + " residual", gout.double() * mask.double() if relu else gout.double())
+
+    # ---- ReLU modules and residual adds of the plain path
+    for m in model.modules():
+        if isinstance(m, ME.MinkowskiReLU) and m in cap.rec:
+            for j, r in enumerate(cap.rec[m]):
+                recs += LW.check_scaled(names[m], f"relu fwd [{j}]", r["y"], r["x"].double().clamp_min(0), 1.0, bound=0.0)
+                if training:
+                    contrib.add(r["x"], names[m] + f" relu bwd [{j}]", g(id(r["y"])).double() * (r["y"] > 0).double())
+        if isinstance(m, BasicBlock) and not m._fused:
+            a = one(m.norm2)["y"]
+            sc = one(m)["x"] if m.downsample is None else one(m.downsample[1])["y"]
+            s = cap.rec[m.nonlinearity][1]["x"]  # the second call of the block's ReLU reads the sum
+            ref = a.double() + sc.double()
+            recs += LW.check_scaled(names[m], "residual add fwd", s, ref, float(ref.abs().max()))
+            if training:
+                gs = g(id(s)).double()
+                contrib.add(a, names[m] + " add bwd", gs)
+                contrib.add(sc, names[m] + " residual", gs)
+
+    # ---- cats
+    for blk, up, enc in CATS:
+        out = one(getattr(model, blk)[0])["x"]
+        e = getattr(model, enc)
+        a, b = one(getattr(model, up))["y"], one(e if e in cap.rec else e[-1])["y"]  # (a stage's output: its last block's)
+        recs += LW.check_scaled(blk, "cat fwd", out, LW.cat_fwd(a, b), 1.0, bound=0.0)
+        if training:
+            ga, gb = LW.cat_bwd(g(id(out)), (a.shape[1], b.shape[1]))
+            contrib.add(a, blk + " cat bwd [0]", ga)
+            contrib.add(b, blk + " cat bwd [1]", gb)
+
+    # ---- composites: the accumulated gradient of every tensor against the float64 sum of its consumers' shares
+    if training:
+        for k, parts in contrib.parts.items():
+            got = g(k)
+            ref = sum(p[1] for p in parts)
+            label = "grad = " + " + ".join(p[0] for p in parts) if len(parts) > 1 else "grad (" + parts[0][0] + ")"
+            name = cap.names[k]
+            if any(p[2] for p in parts):
+                recs += LW.check_conv(name, label, got, ref, frozenset())
+            else:
+                recs += LW.check_scaled(name, label, got, ref, float(ref.abs().max()))
+            if len(parts) > 1:
+                reach.add("composite gradient")
+        # every gradient autograd delivered was checked: by its consumers' sum, a norm's backward or the loss
+        have = {k for k, v in cap.grads.items() if v is not None}
+        unchecked = have - set(contrib.parts) - bn_inputs - {id(cap.logits)}
+        assert not unchecked, sorted(cap.names[k] for k in unchecked)
+        params = {n for n, p in model.named_parameters()}
+        assert checked_params == params, sorted(params ^ checked_params)
+    return recs, reach
+
+
+# ------------------------------------------------------------------------------------------------ the test
+# Against the launch table the segmentation network was expected to take, the planner differs in one place: block7 / block8
+# (96 -> 64, 64 -> 64, stride 1, ~10^6 rows at ts 1) do NOT take the row-compacted kernel.  That kernel holds at most CKP = 9
+# offsets per workgroup, so 27 offsets need >= 3 slabs, and compact_shape (conv.hip:2936) admits a shape only while those
+# slabs fit 128 MB (3 x 4 B x 10^6 x 64 = 768 MB does not); mink_conv_plan then answers with mink_conv_plan_ksplit, which has
+# no split for >= 768 row tiles, and un-split 27 offsets exceed CKP: gather_gemm_impl takes dense gather_gemm2 (conv.hip:3092).
+# The row-compacted stride-1 form is reached at the coarse levels (block3, 64 -> 64), and conv4p8s2 (K = 8) takes it too.
+EXPECT = {"stem padded 3->4", "row-compacted (conv4p8s2)", "row-compacted, stride 1", "dense unsplit at ts 1",
+          "class-permuted compact (transposed fwd)",
+          "staged gather_gemm2 (transposed fwd)", "dense with channel tail", "split-K at ts 8 / 16", "class-permuted dgrad",
+          "pointwise", "segment_mean", "slice", "composite gradient"}
+
+
+@pytest.mark.timeout(90)  # measured: 13 s (fused, first in the process) and 9 s on one MI355X
+@pytest.mark.parametrize("fused", [True, False])
+def test_res16unet_every_operator_teacher_forced_at_scannet_shapes(oracle_maps, tmp_path, fused):
+    """One scannet_semseg.gin training batch (8 rooms, train.batch_size), one training-mode forward + slice + cross
+    entropy + backward: every map bit for bit, every operator and parameter gradient against float64; then one eval-mode
+    forward on 2 uncropped validation scenes, every operator's forward."""
+    import time
+
+    from nerf_downstream_amd._lib import lib
+    from nerf_downstream_amd.minkowski import functional as Fn
+
+    t0 = time.time()
+    assert Fn.conv_math() == "fp32"
+    L = lib()
+    model = _model(fused)
+    model.train()
+    batch = _scannet_batch(str(tmp_path / "train"), "train", 8, seed=21)
+    field = model.process_input(batch)
+    labels = field.row_labels.long()
+    cap = Capture(model)
+    try:
+        logits = model(field)
+        loss = F.cross_entropy(logits, labels, ignore_index=-100)
+        loss.backward()
+        torch.cuda.synchronize()
+    finally:
+        cap.close()
+    t_run = time.time() - t0
+    tabs, levels, inverse, seen = _oracle_tables(oracle_maps, field)
+    for key in [(ts, ts, 3, 1) for ts in (1, 2, 4, 8, 16)] + [(ts, 2 * ts, 2, 1) for ts in (1, 2, 4, 8)]:
+        assert key in seen, f"table {key} was not used"
+    for ts in (1, 2, 4, 8):
+        assert ("transposed", ts, 2 * ts, 2, 1) in seen and ("perm", ts, 128) in seen, ts
+    nbr1 = tabs[(1, 1, 3, 1)][0]
+    live = float((nbr1 >= 0).sum(1).double().mean())
+    print(f"\n[Res16UNet fused={fused}] field rows {field.F.shape[0]}, rows per tensor stride {levels}, "
+          f"live offsets per row at ts 1: {live:.2f} of 27; {len(seen)} tables / permutations bit-exact")
+    assert levels[1] > 400_000 and live > 4.0, "the batch must look like ScanNet's: many rows, several live offsets per row"
+    with torch.no_grad():
+        recs, reach = _check(model, cap, tabs, levels, inverse, L, True, labels)
+    expect = EXPECT | ({"stats direct", "stats split"} if fused else set())
+    n_wgrad = sum(1 for r in recs if r.op.endswith("wgrad") and not r.op.endswith("vs other"))
+    assert n_wgrad == sum(1 for n, _ in model.named_parameters() if n.endswith(".kernel"))
+    bad = LW.report(recs, f"Res16UNet train fused={fused}", force=True)
+    worst = {}
+    for r in recs:
+        if not r.op.endswith("vs other") and np.isfinite(r.err):
+            kind = r.op.split(" [")[0].split(" (")[0]
+            worst[kind] = max(worst.get(kind, 0.0), r.err / r.bound if r.bound else r.err)
+    print(f"[Res16UNet train fused={fused}] {len(recs)} checks; launch forms reached: {sorted(reach)}")
+    print("  worst error / bound per operator kind: " + ", ".join(f"{k} {v:.2f}" for k, v in sorted(worst.items())))
+    assert not bad, [r.line() for r in bad]
+    assert expect <= reach, ("launch forms this configuration must reach", sorted(expect - reach))
+    del cap, logits, loss, tabs
+
+    # ---- validation path: eval mode (running statistics), 2 uncropped scenes, forward only
+    model.eval()
+    vb = _scannet_batch(str(tmp_path / "val"), "val", 2, seed=22)
+    vfield = model.process_input(vb)
+    cap = Capture(model)
+    try:
+        with torch.no_grad():
+            model(vfield)
+        torch.cuda.synchronize()
+    finally:
+        cap.close()
+    tabs, levels, inverse, _ = _oracle_tables(oracle_maps, vfield)
+    with torch.no_grad():
+        erecs, _ = _check(model, cap, tabs, levels, inverse, L, False)
+    bad = LW.report(erecs, f"Res16UNet eval fused={fused}", force=True)
+    print(f"[Res16UNet eval fused={fused}] {len(erecs)} forward checks over {levels[1]} rows; {time.time() - t0:.1f} s in all "
+          f"(training step {t_run:.1f} s)")
+    assert not bad, [r.line() for r in bad]
