@@ -85,14 +85,16 @@ def _baseline_batch(batch=16, grid=128, cin=28):
     return collate_mink([ds[i] for i in range(batch)])  # exactly bench.py's first batch
 
 
-def _bench_like_step(hip, batch, labels, passes=3):
+def _bench_like_step(hip, batch, labels, passes=3, before_last_pass=None):
     """The training step exactly as bench.py queues it: flat gradient buffer as the gradient sink of the backward kernels,
     coordinate pyramid launched ahead (defer=True) and finished after the previous pass, map plan replayed on the prepare
     stream (so the shortcut branch forks onto its own stream and the weight gradients run on theirs).  The first pass
     records the plan, the second runs while the third batch's maps are replayed from it (the pyramid of pass p+1 is
     launched before forward p, as in bench.py, so it takes two passes to reach the steady state); gradients and logits
     are those of the LAST pass (train-mode batch norm: neither depends on the
-    running statistics that move between passes)."""
+    running statistics that move between passes).  `before_last_pass()`, when given, is called right before the last
+    pass's forward (e.g. to snapshot the running statistics that pass moves, or to attach hooks to that pass only); it only
+    queues work and never synchronises the device, so the last pass overlaps the tail of the one before as in bench.py."""
     import torch
     import torch.nn.functional as F
 
@@ -102,6 +104,8 @@ def _bench_like_step(hip, batch, labels, passes=3):
     tf = hip.process_input(batch)
     out = field = None
     for p in range(passes):
+        if p + 1 == passes and before_last_pass is not None:
+            before_last_pass()
         nxt = hip.process_input(batch, defer=True) if p + 1 < passes else None
         reducer.zero_grad()
         field = tf

@@ -418,6 +418,85 @@ def check_bf16_store(layer, op, got, ref):
     return [Record(layer, op, got.shape[0], tuple(got.shape), "y", max(err, 0.0), STORE_MAX, err <= STORE_MAX, "beyond half an ulp")]
 
 
+def running_snapshot(model):
+    """{nn.BatchNorm1d: (name, running_mean, running_var, num_batches_tracked)}, copied by clones queued on the current stream
+    (no device sync: a pass that follows keeps the schedule it would have had).  A forked shortcut's norm moves its statistics
+    on the branch stream, which the current stream joins before the pass ends, so the clones read every earlier pass's update
+    and none of a later one's."""
+    return {m: (n, m.running_mean.detach().clone(), m.running_var.detach().clone(), m.num_batches_tracked.detach().clone())
+            for n, m in model.named_modules() if isinstance(m, torch.nn.BatchNorm1d)}
+
+
+def running_update(r0, v0, y, momentum=0.1):
+    """nn.BatchNorm1d's update of its running statistics by a batch y [n, C], float64:
+    (1 - momentum) r0 + momentum mean(y), (1 - momentum) v0 + momentum var(y) n / (n - 1)  (the UNBIASED variance).
+    -> (running mean, running var, batch mean, biased batch variance)."""
+    y = y.double()
+    n = y.shape[0]
+    mean = y.mean(0)
+    var = ((y - mean) ** 2).mean(0)
+    return ((1 - momentum) * r0.double() + momentum * mean, (1 - momentum) * v0.double() + momentum * var * n / max(n - 1, 1),
+            mean, var)
+
+
+# The fp32 update fl(fl(keep r0) + fl(momentum fl(m))) rounds three times, and keep = fl(1 - 0.1f), 0.1f miss 0.9 / 0.1 by
+# under half a rounding each: it sits within 4 unit roundoffs (2 ulps) of |keep r0| + |momentum m| of the exact update --
+# the slack the running-statistics check allows on top of NORM_BOUND, whatever the size of r0 next to the batch's spread.
+RUN_SLACK = 4 * 2.0 ** -24
+
+
+def check_running(layer, before, bn, y, passes=1):
+    """The running statistics a batch norm left after `passes` training passes, the last of which normalised y, against
+    running_update of the values it held before that pass (`before`: an entry of running_snapshot), channel by channel:
+    |err| of the mean <= NORM_BOUND sd(y), of the var <= NORM_BOUND var(y), each beyond RUN_SLACK of the update's own terms
+    (the fp32 rounding of the update itself); num_batches_tracked advanced by exactly one per pass."""
+    _, r0, v0, t0 = before
+    mom = bn.momentum
+    rm, rv, mean, var = running_update(r0, v0, y, mom)
+    n = y.shape[0]
+    slack_m = RUN_SLACK * ((1 - mom) * r0.double().abs() + mom * mean.abs())
+    slack_v = RUN_SLACK * ((1 - mom) * v0.double().abs() + mom * var * n / max(n - 1, 1))
+    em = float((((bn.running_mean.double() - rm).abs() - slack_m).clamp_min(0) / var.sqrt().clamp_min(1e-300)).max())
+    ev = float((((bn.running_var.double() - rv).abs() - slack_v).clamp_min(0) / var.clamp_min(1e-300)).max())
+    steps = int(bn.num_batches_tracked) - int(t0)
+    return [Record(layer, "running mean", n, tuple(rm.shape), "fp32", em, NORM_BOUND, em <= NORM_BOUND, "of sd, beyond the slack"),
+            Record(layer, "running var", n, tuple(rv.shape), "fp32", ev, NORM_BOUND, ev <= NORM_BOUND,
+                   "unbiased; of var, beyond the slack"),
+            Record(layer, "batches tracked", n, (), "int", float(abs(steps - passes)), 0.0, steps == passes,
+                   f"+{steps} over {passes} pass(es)")]
+
+
+def far_running_stats(model, seed=91):
+    """Seed every batch norm's running statistics far from (0, 1) and from any batch's own: mean +-[0.2, 0.6], var in
+    [1.5, 3]; one channel in eight with its variance near eps (5e-6 .. 5e-5) and gamma = sqrt(var + eps), so that its output
+    keeps its scale while dropping eps moves it by 10-40 %; beta N(0, 0.1).  An eval-mode kernel that normalises with the
+    batch's statistics, swaps mean and variance or drops eps is then an O(1) error."""
+    g = torch.Generator().manual_seed(seed)
+    for m in model.modules():
+        if isinstance(m, torch.nn.BatchNorm1d):
+            C = m.num_features
+            sign = torch.where(torch.rand(C, generator=g) < 0.5, -1.0, 1.0)
+            rm = sign * (0.2 + 0.4 * torch.rand(C, generator=g))
+            rv = 1.5 + 1.5 * torch.rand(C, generator=g)
+            tiny = torch.arange(C) % 8 == 3
+            rv[tiny] = 5e-6 + 4.5e-5 * torch.rand(int(tiny.sum()), generator=g)
+            gamma = torch.ones(C)
+            gamma[tiny] = (rv[tiny] + m.eps).sqrt()
+            with torch.no_grad():
+                m.running_mean.copy_(rm), m.running_var.copy_(rv), m.weight.copy_(gamma)
+                m.bias.copy_(0.1 * torch.randn(C, generator=g))
+                m.num_batches_tracked.fill_(1234)
+
+
+def check_running_unchanged(before, model):
+    """After an eval-mode pass: every running statistic and step counter bit for bit as before."""
+    recs = []
+    for m, (name, r0, v0, t0) in before.items():
+        same = torch.equal(m.running_mean, r0) and torch.equal(m.running_var, v0) and torch.equal(m.num_batches_tracked, t0)
+        recs.append(Record(name, "running stats kept", 0, tuple(r0.shape), "eval", 0.0 if same else float("inf"), 0.0, same))
+    return recs
+
+
 def report(records, title="", force=False):
     """One table line per operator; printed when something failed, when `force`, or with MINK_TEST_VERBOSE."""
     import os

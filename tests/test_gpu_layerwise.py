@@ -44,7 +44,7 @@ def _conv_recs(layer, op, got, fn, ops, rounded):
     return LW.check_conv(layer, op, got, ref, rounded, other)
 
 
-def _stem_records(saved, model, out, math):
+def _stem_records(saved, model, out, math, before):
     """Stem: conv -> y (bf16-stored under bf16s), norm statistics, relu + pool -> out; backward: bn1.* and conv1.kernel."""
     recs = []
     x, w0, arena0, nbr0, nbr_pool, i2o, pad, b16, _ = saved.stem
@@ -70,6 +70,7 @@ def _stem_records(saved, model, out, math):
     else:
         recs += _conv_recs("stem", "conv fwd", y, lambda x, w: LW.conv_fwd(x, w, nbr0), ops, r_fwd)
     recs += LW.check_stats("stem", "norm", mean, invstd, y, bn.eps)
+    recs += LW.check_running("stem", before[bn], bn, y)
     # relu + pool: the forward's own ReLU decisions are those of the norm-gradient kernel (_stem_masks_of_hip_run)
     sm_bn, sm_w = (m.cuda() for m in _stem_masks_of_hip_run(out, model))
     z = LW.bn_fwd(y, gamma, beta, eps=bn.eps)
@@ -98,7 +99,7 @@ def _stem_records(saved, model, out, math):
     return recs
 
 
-def _block_records(i, st, saved, m, math, reach, L):
+def _block_records(i, st, saved, m, math, reach, L, before):
     recs = []
     arena, nbr1, nbr2, nbrd, ts_in, ts_out, n_in, n_out = saved[1 + i]
     C, cin = st.C, st.cin
@@ -131,15 +132,18 @@ def _block_records(i, st, saved, m, math, reach, L):
     # ---- forward
     recs += _conv_recs(lay, "conv1 fwd", y1, lambda x, w: LW.conv_fwd(x, w, nbr1), {"x": x, "w": W1}, fwd3)
     recs += LW.check_stats(lay, "norm1", m1, is1, y1, n1m.eps)
+    recs += LW.check_running(lay + " norm1", before[n1m], n1m, y1)
     recs += LW.check_relu_out(lay, "norm1+relu fwd", h1, LW.bn_fwd(y1, n1m.weight, n1m.bias, eps=n1m.eps))
     recs += _conv_recs(lay, "conv2 fwd", y2, lambda x, w: LW.conv_fwd(x, w, nbr2), {"x": h1, "w": W2}, fwd3)
     recs += LW.check_stats(lay, "norm2", m2, is2, y2, n2m.eps)
+    recs += LW.check_running(lay + " norm2", before[n2m], n2m, y2)
     if down:
         yd, sd = arena[4 * cnt : 5 * cnt].view(n_out, C), arena[5 * cnt : 6 * cnt].view(n_out, C)
         Wd, ndm = st.down.kernel.detach(), st.normd.bn
         recs += _conv_recs(lay, "down fwd", yd, lambda x, w: LW.conv_fwd(x, w, nbrd), {"x": x, "w": Wd},
                            LW.rounded_operands("fwd", 1, cm))
         recs += LW.check_stats(lay, "normd", md, isd, yd, ndm.eps)
+        recs += LW.check_running(lay + " normd", before[ndm], ndm, yd)
         ref = LW.bn_fwd(yd, ndm.weight, ndm.bias, eps=ndm.eps)
         recs += LW.check_scaled(lay, "normd fwd", sd, ref, float(ref.abs().max()))
         shortcut = sd
@@ -211,9 +215,10 @@ def test_every_operator_teacher_forced_against_float64(name, batch, math, expect
     hip = _pair(name)
     old = Fn.set_conv_math("bf16" if math == "bf16s" else math), Fn.set_conv_storage("bf16" if math == "bf16s" else "fp32")
     trunk.KEEP_GRAD_ARENA = True
+    before = {}  # every batch norm's running statistics before the last pass (layerwise.check_running)
     try:
         out, field, reducer = _bench_like_step(hip, {"coordinates": b["coordinates"].cuda(), "features": b["features"].cuda()},
-                                               b["labels"].long().cuda())
+                                               b["labels"].long().cuda(), before_last_pass=lambda: before.update(LW.running_snapshot(hip)))
     finally:
         trunk.KEEP_GRAD_ARENA = False
         Fn.set_conv_math(old[0]), Fn.set_conv_storage(old[1])
@@ -228,9 +233,10 @@ def test_every_operator_teacher_forced_against_float64(name, batch, math, expect
     L = lib()
     reach = set()
     with torch.no_grad():
-        recs = _stem_records(saved, hip, out, math)
+        recs = _stem_records(saved, hip, out, math, before)
         for i, st in enumerate(node.plan.stages):
-            recs += _block_records(i, st, saved, field.coordinate_manager, math, reach, L)
+            recs += _block_records(i, st, saved, field.coordinate_manager, math, reach, L, before)
+    assert len(before) == sum(1 for r in recs if r.op == "running var"), "a batch norm's running statistics went unchecked"
     # every parameter gradient of the trunk was checked against its operator's float64 backward
     checked = {r.op for r in recs}
     n_blocks = len(node.plan.stages)

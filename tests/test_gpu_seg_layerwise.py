@@ -222,7 +222,7 @@ class Contrib:
         self.parts.setdefault(id(t), []).append((label, g, conv))
 
 
-def _check(model, cap, tabs, levels, inverse, L, training, labels=None):
+def _check(model, cap, tabs, levels, inverse, L, training, labels=None, before=None):
     from nerf_downstream_amd import minkowski as ME
     from nerf_downstream_amd.co3d_3d.src.models.mink.modules.resnet_block import BasicBlock
 
@@ -344,6 +344,7 @@ def _check(model, cap, tabs, levels, inverse, L, training, labels=None):
         if training:
             mean, invstd = r["saved"][2], r["saved"][3]
             recs += LW.check_stats(lay, "norm", mean, invstd, y, bn.eps)
+            recs += LW.check_running(lay, before[bn], bn, y)
             z = LW.bn_fwd(y, gamma, beta, res, eps=bn.eps)
         else:
             z = LW.bn_eval_fwd(y, bn.running_mean, bn.running_var, gamma, beta, res, eps=bn.eps)
@@ -409,6 +410,7 @@ def _check(model, cap, tabs, levels, inverse, L, training, labels=None):
         assert not unchecked, sorted(cap.names[k] for k in unchecked)
         params = {n for n, p in model.named_parameters()}
         assert checked_params == params, sorted(params ^ checked_params)
+        assert len(before) == sum(1 for r in recs if r.op == "running var"), "a batch norm's running statistics went unchecked"
     return recs, reach
 
 
@@ -444,6 +446,7 @@ def test_res16unet_every_operator_teacher_forced_at_scannet_shapes(oracle_maps, 
     batch = _scannet_batch(str(tmp_path / "train"), "train", 8, seed=21)
     field = model.process_input(batch)
     labels = field.row_labels.long()
+    before = LW.running_snapshot(model)
     cap = Capture(model)
     try:
         logits = model(field)
@@ -464,7 +467,7 @@ def test_res16unet_every_operator_teacher_forced_at_scannet_shapes(oracle_maps, 
           f"live offsets per row at ts 1: {live:.2f} of 27; {len(seen)} tables / permutations bit-exact")
     assert levels[1] > 400_000 and live > 4.0, "the batch must look like ScanNet's: many rows, several live offsets per row"
     with torch.no_grad():
-        recs, reach = _check(model, cap, tabs, levels, inverse, L, True, labels)
+        recs, reach = _check(model, cap, tabs, levels, inverse, L, True, labels, before)
     expect = EXPECT | ({"stats direct", "stats split"} if fused else set())
     n_wgrad = sum(1 for r in recs if r.op.endswith("wgrad") and not r.op.endswith("vs other"))
     assert n_wgrad == sum(1 for n, _ in model.named_parameters() if n.endswith(".kernel"))
@@ -484,6 +487,7 @@ def test_res16unet_every_operator_teacher_forced_at_scannet_shapes(oracle_maps, 
     model.eval()
     vb = _scannet_batch(str(tmp_path / "val"), "val", 2, seed=22)
     vfield = model.process_input(vb)
+    before = LW.running_snapshot(model)
     cap = Capture(model)
     try:
         with torch.no_grad():
@@ -494,6 +498,7 @@ def test_res16unet_every_operator_teacher_forced_at_scannet_shapes(oracle_maps, 
     tabs, levels, inverse, _ = _oracle_tables(oracle_maps, vfield)
     with torch.no_grad():
         erecs, _ = _check(model, cap, tabs, levels, inverse, L, False)
+    erecs += LW.check_running_unchanged(before, model)
     bad = LW.report(erecs, f"Res16UNet eval fused={fused}", force=True)
     print(f"[Res16UNet eval fused={fused}] {len(erecs)} forward checks over {levels[1]} rows; {time.time() - t0:.1f} s in all "
           f"(training step {t_run:.1f} s)")
