@@ -2940,7 +2940,7 @@ static bool compact_shape(int64_t n_rows, int K, int cin, int cout, int row_clas
   return zmin == 1 || zmin * 4 * n_rows * cout <= (128ll << 20);
 }
 static int compact_plan(int64_t n_rows, int K, int cout) {
-  if (g_compact_p3 & 8) {  // stream-K: the slab count of its plan
+  if ((g_compact_p3 & 8) && !(g_stagger & 0xFC) && !g_trace_buf) {  // stream-K (the gate of gather_gemm_impl): the slab count of its plan
     const SkPlan sk = sk_plan(n_rows, K, cout);
     if (sk.G) return sk.S;
   }
@@ -3025,17 +3025,23 @@ static int gather_gemm_impl(const float *x, int64_t n_in, int32_t ldx, int32_t c
   p.swz_x = p.swz_y = p.swz_z = 0;
   p.trace = nullptr;
   p.sk_q = p.sk_r = 0, p.sk_X = 0, p.sk_S = 0;
-  // stream-K (compact_gemm_kernel<.., SK>): a split stride-1 launch whose caller planned at least the slabs the plan needs
+  const bool al = (((uintptr_t)x | (uintptr_t)w) & 15) == 0 && (ldx & 3) == 0 && (cin & 3) == 0;
+  const bool vec = al && (w_transposed ? true : (cout & 3) == 0);
+  // every condition of the row-compacted form (compact_gemm_kernel) except its slice length, which depends on the split below
+  const bool compact_ok = g_compact && g_math == 0 && vec && !row_perm && !p.accumulate && K >= 8 && cin >= 64 && cin % BK == 0 &&
+                          cout % BN == 0 && (ldy & 3) == 0 && 4ll * K * cin * cout < (1ll << 31) && 4ll * n_in * ldx < (1ll << 32) &&
+                          (((uintptr_t)y | (uintptr_t)workspace | (uintptr_t)bias) & 15) == 0;
+  // stream-K (compact_gemm_kernel<.., SK>): a split stride-1 launch whose caller planned at least the slabs the plan needs.  Only
+  // where the launch takes the row-compacted kernel: any other kernel splits by kper = cdiv(K, ksplit), and the `ksplit` slabs of
+  // the stream-K plan would give it trailing slices that start at or past K.
   SkPlan sk = {0, 0};
-  if ((g_compact_p3 & 8) && ksplit > 1 && !row_perm && !(g_stagger & 0xFC) && !g_trace_buf && compact_shape(n_out, K, cin, cout, 0)) {
+  if ((g_compact_p3 & 8) && ksplit > 1 && compact_ok && !(g_stagger & 0xFC) && !g_trace_buf && compact_shape(n_out, K, cin, cout, 0)) {
     sk = sk_plan(n_out, K, cout);
     if (sk.G == 0 || sk.S > ksplit) sk = {0, 0};
   }
   const int zs = sk.G ? ksplit : (int)cdiv(K, p.kper);  // (stream-K: exactly the slabs the caller planned; the spare ones are zeroed)
   const dim3 grid((unsigned)cdiv(n_virtual, BM), (unsigned)cdiv(cout, BN), (unsigned)zs);
   hipStream_t st = (hipStream_t)stream;
-  const bool al = (((uintptr_t)x | (uintptr_t)w) & 15) == 0 && (ldx & 3) == 0 && (cin & 3) == 0;
-  const bool vec = al && (w_transposed ? true : (cout & 3) == 0);
   MINK_REQUIRE(!p.accumulate || (zs == 1 && vec && !stats_out),
                "gather_gemm: accumulation needs an un-split launch of the pipelined kernel (16-byte aligned operands)");
   flip_k &= 1;
@@ -3090,9 +3096,7 @@ static int gather_gemm_impl(const float *x, int64_t n_in, int32_t ldx, int32_t c
   unsigned tiles_x = grid.x;  // row tiles that wrote statistics partials
   // (--math bf16 keeps the stride-1 mid layers on the dense bf16 kernel: the row-compacted form with one bf16 MFMA per block and item,
   //  measured round 5, is no faster there -- l1.conv2 57 / 60 us against 56 / 56 forward / data gradient, l3 48 / 58 against 44 / 46)
-  const bool compact = g_compact && g_math == 0 && vec && !row_perm && !p.accumulate && K >= 8 && (p.kper <= CKP || sk.G) && cin >= 64 &&
-                       cin % BK == 0 && cout % BN == 0 && (ldy & 3) == 0 && 4ll * K * cin * cout < (1ll << 31) &&
-                       4ll * n_in * ldx < (1ll << 32) && (((uintptr_t)y | (uintptr_t)workspace | (uintptr_t)bias) & 15) == 0;
+  const bool compact = compact_ok && (p.kper <= CKP || sk.G);
   if (compact) {  // row-compacted offsets, C tile in LDS (compact_gemm_kernel)
     constexpr int CMT = 64;
     constexpr int smem = compact_smem(CMT);

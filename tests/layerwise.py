@@ -35,16 +35,150 @@ def bf16_trunc(t):
     return (t.float().contiguous().view(torch.int32) & -65536).view(torch.float32).to(t.dtype)
 
 
-def rounded_operands(op, K, math):
-    """The operands a kernel rounds to bf16 before its fp32-accumulating products, by operator and math mode
-    (cf. test_gpu_parity_full._bf16_operands): forward rounds rows and weights; the data gradient rounds dY and weights
-    EXCEPT the 1x1x1 strided shortcut's (the exact-fp32 dense GEMM mink_dense_xwt); the weight gradient rounds rows and dY.
+# csrc/conv.hip constants the dispatch below depends on
+BK, BN = 32, 64  # conv.hip:23-24: reduction chunk, output columns per workgroup of the gather-GEMMs
+WT, WROWS = 64, 128  # conv.hip:1606-1607: weight-gradient super-tile, rows per tile
+CONV_MATH = {"fp32": 0, "bf16": 1, "bf16s": 1, "bf16x3": 3}  # "bf16s": bf16 math + bf16 storage of the stem (functional.set_conv_storage)
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def wgrad_plan(n_out, K, cin, cout, force=0):
+    """(G, nsplit) of wgrad_plan (conv.hip:2538-2566): offsets per workgroup and row splits.  `force`: set_stagger bits 12-26
+    (g_wgrad_force: bits 0-3 of it the G code 1 / 2 / 3 -> G = 1 / 3 / 9, bits 4.. a forced row-split count)."""
+    tiles = _cdiv(cin, WT) * _cdiv(cout, WT)
+    row_tiles = _cdiv(n_out, WROWS)
+    G = 1
+    if K >= 9 and tiles * _cdiv(K, 9) * row_tiles >= 1024:
+        G = 9
+    elif K >= 3 and tiles * _cdiv(K, 3) * row_tiles >= 1024:
+        G = 3
+    tiny = row_tiles <= 4 and tiles * K >= 512
+    if tiny:
+        G = 1
+    if force & 0xF:
+        G = {1: 1, 2: 3}.get(force & 0xF, 9)
+    z = _cdiv(512, tiles * _cdiv(K, G))
+    if tiny:
+        z = 1
+    if force >> 4:
+        z = force >> 4
+    z = max(1, min(z, row_tiles))
+    streamed = G == 9 and K == 27 and cin <= 32 and tiles == 1 and z >= 16
+    if streamed:
+        z = z // 8 * 8
+    rows = _cdiv(_cdiv(n_out, z), WROWS) * WROWS
+    nsplit = max(1, _cdiv(n_out, rows))
+    if streamed:
+        nsplit = _cdiv(nsplit, 8) * 8
+    return G, nsplit
+
+
+@dataclass(frozen=True)
+class ConvForm:
+    """What one convolution launch computes: the kernel it reaches, the operands it rounds to bf16 before its fp32-accumulating
+    products, and whether the rounding is the split-bf16 one (v = hi + lo, products hi*hi + hi*lo + lo*hi: form_reference)."""
+    form: str
+    rounded: frozenset
+    split: bool = False
+
+
+def conv_form(op, K, cin, cout, math, n_out=1, ldx=None, ldy=None, row_perm=False, aligned=True, ksplit=1, force_g=0, perm16=True,
+              shortcut_dense=True):
+    """The launch form and operand rounding of one convolution operator, restated from the dispatchers of csrc/conv.hip
+    (gather_gemm_impl, conv.hip:2992-3184; wgrad_impl, conv.hip:3234-3300) with the default switches and within their 32-bit
+    size limits.
+
+    op: "fwd" (W as [K][cin][cout]), "dgrad" (the same-map or class-permuted gather with the forward weights read transposed),
+    "wgrad" (dW[k] = X[nbr[:, k]]^T dY) or "store" (the stem's y under "bf16s").  cin / cout are the CONVOLUTION's; ldx is the
+    row stride of the gathered operand (x, or dY for "dgrad"; default: contiguous), ldy that of dY for "wgrad".  row_perm: the
+    launch goes through a class permutation (a strided data gradient, or the forward of a transposed convolution).  aligned:
+    the operand pointers are 16-byte aligned (torch allocations are).  ksplit: the split the launch is asked for.  force_g:
+    set_stagger bits 12-26 (wgrad_plan's hook).  perm16: set_stagger bit 27 clear (the class-permuted bf16 data gradient on
+    compact_gemm_kernel).  shortcut_dense: a K = 1 class-permuted data gradient is the exact-fp32 dense GEMM mink_dense_xwt +
+    a scatter (functional.py ConvolutionFunction.backward, trunk.hip), not a gather."""
+    m = CONV_MATH[math]
+    if op == "store":
+        return ConvForm("bf16 store" if math == "bf16s" else "fp32 store", frozenset({"y"}) if math == "bf16s" else frozenset())
+    if op == "wgrad":
+        ldx = cin if ldx is None else ldx
+        ldy = cout if ldy is None else ldy
+        G, nsplit = wgrad_plan(n_out, K, cin, cout, force_g)
+        tag = f" G{G}" + (" split" if nsplit > 1 else "")
+        # the streaming kernels take the stem shape (wgrad_stream_ok, conv.hip:3229)
+        stream_ok = K == 27 and cin <= 32 and ldx < 64
+        if G == 9 and stream_ok:
+            if m == 1:  # conv.hip:3265 (bf16_stream)
+                return ConvForm("wgrad_stream_bf16" + tag, frozenset({"x", "dy"}))
+            return ConvForm("wgrad_stream" + tag, frozenset())
+        if m == 1 and G != 9 and cin % WT == 0 and cout % WT == 0 and aligned and (ldx | ldy) % 4 == 0:  # conv.hip:3285-3289
+            return ConvForm(f"wgrad16<{3 if G == 3 else 1}>" + tag, frozenset({"x", "dy"}))
+        return ConvForm("wgrad fp32" + tag, frozenset())  # launch_wgrad<G>: exact fp32 under every math (bf16x3 included)
+    assert op in ("fwd", "dgrad"), op
+    wt = op == "dgrad"
+    if wt and row_perm and K == 1 and cin % 4 == 0 and cout % 4 == 0 and shortcut_dense:
+        return ConvForm("dense_xwt", frozenset())
+    gin, gout = (cout, cin) if wt else (cin, cout)  # the GEMM's reduction / output widths
+    names = {"dy", "w"} if wt else {"x", "w"}
+    ldx = gin if ldx is None else ldx
+    vec = aligned and ldx % 4 == 0 and gin % 4 == 0 and (wt or gout % 4 == 0)  # conv.hip:3028-3029 (al, vec)
+    if m == 0:
+        return ConvForm("fp32", frozenset())
+    # the class-permuted branch (compact_perm_shape, conv.hip:2965; conv.hip:3052): bf16 math takes it for the data gradient only
+    if (row_perm and wt and m == 1 and perm16 and K >= 8 and gin >= 64 and gin % BK == 0 and gout % BN == 0 and vec
+            and gout % 4 == 0):
+        return ConvForm("class-permuted compact bf16", frozenset(names))
+    if not vec:  # gather_gemm_kernel (conv.hip:3156): operands that are not 16-byte rows -- no MATH parameter, exact fp32
+        return ConvForm("scalar gather_gemm", frozenset())
+    # gather_gemm2_kernel<W_T, STAGE, FLAT, MATH> (conv.hip:3142-3154; the row-compacted forms need fp32 math, conv.hip:3031)
+    if row_perm:
+        form = "staged gather_gemm2" + (" (transposed weights)" if wt else " (transposed-conv fwd)")
+    elif wt:
+        form = "dense gather_gemm2 (transposed weights)"
+    elif gin == 28 and ldx <= 32 and _cdiv(K, _cdiv(K, ksplit)) == 1:
+        form = "flat gather_gemm2 (cin 28)"  # FLAT = 28: un-split forward launches only
+    else:
+        form = "dense gather_gemm2"
+    if gin % BK and "flat" not in form:
+        form += " + channel tail"
+    return ConvForm(form + (" bf16x3" if m == 3 else " bf16"), frozenset(names), split=m == 3)
+
+
+def rounded_operands(op, K, cin, cout, math, **shape):
+    """The operands a kernel rounds to bf16 before its fp32-accumulating products (conv_form: shape-aware -- a scalar-form
+    gather and a weight gradient whose widths are not multiples of 64 stay exact fp32 under bf16 math, the K = 1 strided
+    data gradient is the exact-fp32 dense GEMM mink_dense_xwt, and bf16x3 math splits instead of rounding: conv_form.split).
     "bf16s" also STORES the stem's convolution output as bf16 (op "store": the y it keeps)."""
-    if math == "fp32":
-        return frozenset()
-    table = {"fwd": {"x", "w"}, "dgrad": set() if K == 1 else {"dy", "w"}, "wgrad": {"x", "dy"},
-             "store": {"y"} if math == "bf16s" else set()}
-    return frozenset(table[op])
+    return conv_form(op, K, cin, cout, math, **shape).rounded
+
+
+def form_reference(fn, ops, cf, rnd=bf16_rne):
+    """float64 fn(**ops) on the operands as the form `cf` (conv_form) multiplies them: rounded where it rounds, and for split-bf16
+    the three products hi*hi + hi*lo + lo*hi of its two operands.  fn must be bilinear in them up to a constant term (a residual
+    added to a data gradient): that term is fn at zero operands, counted once."""
+    if not cf.split:
+        return fn(**apply_rounding(ops, cf.rounded, rnd))
+    (p, a), (q, b) = ops.items()
+    ah, al = (t.double() for t in bf16_split(a))
+    bh, bl = (t.double() for t in bf16_split(b))
+    c = fn(**{p: torch.zeros_like(ah), q: torch.zeros_like(bh)})
+    return fn(**{p: ah, q: bh}) + fn(**{p: ah, q: bl}) + fn(**{p: al, q: bh}) - 2 * c
+
+
+def other_reference(fn, ops, cf):
+    """The other rounding of check_conv: the fp32 operands where the form rounds or splits, every operand rounded to bf16 where
+    it multiplies them exactly."""
+    return fn(**apply_rounding(ops, frozenset() if cf.rounded else frozenset(ops)))
+
+
+def bf16_split(t, rnd=None):
+    """(hi, lo) of split-bf16 (conv.hip pack_bf16 / bf16_residual): hi = rne(v), lo = rne(v - hi), both taken in fp32."""
+    rnd = rnd or bf16_rne
+    v = t.float()
+    hi = bf16_rne(v)
+    return hi, rnd(v - hi)
 
 
 def apply_rounding(ops, rounded, rnd=bf16_rne):

@@ -167,9 +167,21 @@ def _global_avg_bwd(g, boff, n):
 
 
 # ------------------------------------------------------------------------------------------------ checks
-def _conv_recs(layer, op, got, fn, ops):
-    """fp32 math: float64 on the operands as stored, with every operand rounded to bf16 as the discriminator."""
-    return LW.check_conv(layer, op, got, fn(**LW.apply_rounding(ops, frozenset())), frozenset(), fn(**LW.apply_rounding(ops, set(ops))))
+def _conv_recs(layer, op, got, fn, ops, cf=None, reach=None, K=None):
+    """float64 on the operands as the launch form `cf` (layerwise.conv_form; None: fp32 math, the operands as stored) multiplies
+    them, with the other rounding as the discriminator.  Under reduced math the form joins `reach` ("form: <kernel>", weight
+    gradients with their kernel volume)."""
+    cf = cf or LW.conv_form("fwd", 27, 64, 64, "fp32")
+    if reach is not None and MATH[0] != "fp32":
+        reach.add("form: " + cf.form.split(" G")[0].split("<")[0] + (f" K={K}" if op.endswith("wgrad") else ""))
+    return LW.check_conv(layer, op, got, LW.form_reference(fn, ops, cf), cf.rounded, LW.other_reference(fn, ops, cf))
+
+
+MATH = ["fp32"]  # the conv math of the run _check judges
+
+
+def _form(op, K, cin, cout, n_out, **kw):
+    return LW.conv_form(op, K, cin, cout, MATH[0], n_out=n_out, **kw)
 
 
 class Contrib:
@@ -316,7 +328,9 @@ def _check(model, cap, tabs, levels, boffs, i2o, L, training, labels=None, befor
                 recs.append(LW.Record(lay, "pointwise form as planned", n, tuple(x.shape), "plan", float(form != want), 0.0,
                                       form == want, f"{form}, planned {want}"))
                 contrib.add(x, lay + " dgrad", LW.pointwise_dgrad(gy, W), conv=True)
-                recs += _conv_recs(lay, "pointwise wgrad", m.kernel.grad, lambda x, dy: LW.pointwise_wgrad(x, dy), {"x": x, "dy": gy})
+                cw = _form("wgrad", 1, cin, cout, n) if form == "streaming wgrad" else None  # (mm: a library GEMM, fp32)
+                recs += _conv_recs(lay, "pointwise wgrad", m.kernel.grad, lambda x, dy: LW.pointwise_wgrad(x, dy), {"x": x, "dy": gy},
+                                   cw, reach if cw else None, 1)
                 checked.add(lay + ".kernel")
                 if b is not None:
                     ref = LW.bias_grad(gy)
@@ -332,7 +346,8 @@ def _check(model, cap, tabs, levels, boffs, i2o, L, training, labels=None, befor
         assert cin_eff in launched, (lay, cin, launched)
         if cin_eff != cin:  # functional.py ConvolutionFunction.forward: zero columns up to a multiple of 4
             reach.add(f"stem padded {cin}->{cin_eff}")
-        recs += _conv_recs(lay, "conv fwd", y, lambda x, w: LW.conv_fwd(x, w, nbr), {"x": x, "w": W})
+        recs += _conv_recs(lay, "conv fwd", y, lambda x, w: LW.conv_fwd(x, w, nbr), {"x": x, "w": W},
+                           _form("fwd", K, cin_eff, cout, y.shape[0]), reach)
         want_stats = bool(r["kw"].get("bn_stats"))
         f = _launch_forms(L, y.shape[0], K, cin_eff, cout, False, False, want_stats)
         if want_stats:  # the forms the planner restates must be the ones the launch took: partials came back iff "stats *"
@@ -364,8 +379,13 @@ def _check(model, cap, tabs, levels, boffs, i2o, L, training, labels=None, befor
                     e = LW.conv_errors(LW.conv_dgrad_gather(gy64, W, ent[1], perm=perm), a)[0]
                     recs.append(LW.Record(lay, "dgrad tables", n_in, tuple(a.shape), "float64", e, 1e-12, e <= 1e-12,
                                           "transposed + perm vs scatter"))
-                contrib.add(x, lay + " dgrad", LW.conv_dgrad(gy, W, nbr, n_in), conv=True)
-            recs += _conv_recs(lay, "conv wgrad", m.kernel.grad, lambda x, dy: LW.conv_wgrad(x, dy, nbr), {"x": x, "dy": gy})
+                cfd = _form("dgrad", K, cin, cout, n_in, row_perm=ts_out != ts_in)
+                if MATH[0] != "fp32":
+                    reach.add("form: " + cfd.form)
+                contrib.add(x, lay + " dgrad", LW.form_reference(lambda dy, w: LW.conv_dgrad(dy, w, nbr, n_in), {"dy": gy, "w": W}, cfd),
+                            conv=True)
+            recs += _conv_recs(lay, "conv wgrad", m.kernel.grad, lambda x, dy: LW.conv_wgrad(x, dy, nbr), {"x": x, "dy": gy},
+                               _form("wgrad", K, cin_eff, cout, y.shape[0]), reach, K)
             checked.add(lay + ".kernel")
         if "split-K" in f and K == 27:
             reach.add("split-K 3^3")
@@ -492,12 +512,48 @@ def test_bottleneck_every_operator_teacher_forced_at_bench_shapes(oracle_maps, n
     """bench.py --model ResNet50/101's own step on its first batch (16 scenes, grid 128, 28 channels): from its last pass every
     map bit for bit, every forward and backward operator, every composite gradient, every parameter gradient as it sits in the
     flat buffer and every batch norm's running statistics, against float64."""
+    from nerf_downstream_amd.minkowski import functional as Fn
+
+    assert Fn.conv_math() == "fp32"
+    _bottleneck_run(oracle_maps, name, fused, "fp32", EXPECT | (EXPECT_FUSED if fused else set()))
+
+
+# Under --math bf16 (un-fused: every convolution goes through ConvolutionFunction / PointwiseConvolutionFunction) each convolution
+# is judged on what its launch form multiplies (layerwise.conv_form), and the forms reached are asserted: the 3^3 stride-1 layers
+# on the dense bf16 gather_gemm2, the stride-2 data gradients on the class-permuted compact bf16 kernel, the K = 1 shortcut's
+# data gradient on the exact-fp32 dense GEMM, the stem's forward on the flat cin = 28 form, weight gradients on wgrad16 at K = 1
+# and K = 27 and the stem's on the streaming bf16 kernel.  (The entries of the fp32 restatement, _launch_forms, are
+# not asserted under bf16.)
+EXPECT_BF16 = {"pointwise streaming wgrad @ 173012", "pointwise streaming wgrad @ 36754", "pointwise mm @ 512",
+               "K=1 stride-2 shortcut 1024->2048", "K=1 shortcut dgrad: dense + scatter (2048->1024)", "norm C=2048", "head C=2048",
+               "composite gradient", "form: dense gather_gemm2 bf16", "form: dense gather_gemm2 (transposed weights) bf16",
+               "form: class-permuted compact bf16", "form: dense_xwt", "form: flat gather_gemm2 (cin 28) bf16", "form: wgrad16 K=1",
+               "form: wgrad16 K=27", "form: wgrad_stream_bf16 K=27"}
+# (entries of the fp32 restatement _launch_forms: dropped from a reduced-math run's list, where they do not apply)
+FP32_PLAN = ("split-K", "class-permuted 3^3", "3^3 stride-2 dgrad: other", "stats partials")
+
+
+@pytest.mark.timeout(120)
+def test_bottleneck_every_operator_teacher_forced_under_bf16_math(oracle_maps):
+    """The same step of ResNet50 (un-fused) under set_conv_math("bf16")."""
+    from nerf_downstream_amd.minkowski import functional as Fn
+
+    old = Fn.set_conv_math("bf16")
+    try:
+        _bottleneck_run(oracle_maps, "ResNet50", False, "bf16", EXPECT_BF16)
+    finally:
+        Fn.set_conv_math(old)
+        MATH[0] = "fp32"
+
+
+def _bottleneck_run(oracle_maps, name, fused, math, expect):
     from nerf_downstream_amd._lib import lib
     from nerf_downstream_amd.co3d_3d.src.models.mink.modules.resnet_block import BasicBlock
     from nerf_downstream_amd.minkowski import functional as Fn
 
     t0 = time.time()
-    assert Fn.conv_math() == "fp32"
+    assert Fn.conv_math() == math
+    MATH[0] = math
     L = lib()
     b = _baseline_batch(16, 128, 28)
     hip = _model(name, 28, fused)
@@ -545,9 +601,11 @@ def test_bottleneck_every_operator_teacher_forced_at_bench_shapes(oracle_maps, n
         assert ("transposed", ts, 2 * ts, 3, 1) in seen and ("perm", ts, 128) in seen, ts
     with torch.no_grad():
         recs, reach = _check(hip, cap, tabs, levels, boffs, i2o, L, True, b["labels"].long().cuda(), before)
+    if math != "fp32":
+        reach = {r for r in reach if not r.startswith(FP32_PLAN)}
     n_wgrad = sum(1 for r in recs if r.op.endswith("wgrad") and not r.op.endswith("vs other"))
     assert n_wgrad == sum(1 for n, _ in hip.named_parameters() if n.endswith(".kernel"))
-    tag = f"{name} {'fused' if fused else 'un-fused'}"
+    tag = f"{name} {'fused' if fused else 'un-fused'} {math}"
     bad = LW.report(recs, f"{tag} train", force=False)
     print(f"\n[{tag} train] {len(recs)} checks ({len(before)} batch norms' running statistics, {len(seen)} tables bit-exact); "
           f"{time.time() - t0:.1f} s (step {t_run:.1f} s)")
@@ -555,7 +613,6 @@ def test_bottleneck_every_operator_teacher_forced_at_bench_shapes(oracle_maps, n
     print(f"  launch forms reached: {sorted(reach)}")
     assert not bad, [r.line() for r in bad]
     # (un-fused: the stem and the head go module by module, and no convolution hands statistics to its norm)
-    expect = EXPECT | (EXPECT_FUSED if fused else set())
     assert expect <= reach, ("launch forms this configuration must reach", sorted(expect - reach))
 
 

@@ -32,16 +32,12 @@ def _pair(name, seed=777):
     return get_model(name, 28, 51).cuda()
 
 
-def _other(rounded, names):
-    """The rounding opposite to the declared one: every operand rounded where the table rounds none, none where it rounds any."""
-    return frozenset() if rounded else frozenset(names)
-
-
-def _conv_recs(layer, op, got, fn, ops, rounded):
-    """check_conv of `got` against fn(**operands) on the declared rounding, with the other rounding as the discriminator."""
-    ref = fn(**LW.apply_rounding(ops, rounded))
-    other = fn(**LW.apply_rounding(ops, _other(rounded, ops)))
-    return LW.check_conv(layer, op, got, ref, rounded, other)
+def _conv_recs(layer, op, got, fn, ops, cf, reach=None):
+    """check_conv of `got` against fn(**operands) as the launch form `cf` (layerwise.conv_form) multiplies them, with the other
+    rounding as the discriminator; the form joins `reach`."""
+    if reach is not None:
+        reach.add("form: " + cf.form.split(" G")[0])
+    return LW.check_conv(layer, op, got, LW.form_reference(fn, ops, cf), cf.rounded, LW.other_reference(fn, ops, cf))
 
 
 def _stem_records(saved, model, out, math, before):
@@ -56,19 +52,20 @@ def _stem_records(saved, model, out, math, before):
     mean, invstd = arena0[ny + n1 * C0 : ny + n1 * C0 + C0], arena0[ny + n1 * C0 + C0 : ny + n1 * C0 + 2 * C0]
     bn = model.bn1.bn
     gamma, beta = bn.weight.detach(), bn.bias.detach()
-    conv_math = "fp32" if math == "fp32" else "bf16"
-    r_fwd = LW.rounded_operands("fwd", 27, conv_math)
+    conv_math = "bf16" if math == "bf16s" else math
+    f_fwd = LW.conv_form("fwd", 27, x.shape[1], C0, conv_math, n_out=n0, ldx=x.stride(0))
+    r_fwd = f_fwd.rounded
     ops = {"x": x, "w": w0.detach()}
     if b16:  # y is STORED as bf16: half an ulp of the float64 value on the rounded operands, and not of the unrounded one
         ref = LW.conv_fwd(nbr=nbr0, **LW.apply_rounding(ops, r_fwd))
         other = LW.conv_fwd(nbr=nbr0, **LW.apply_rounding(ops, frozenset()))
-        assert LW.rounded_operands("store", 27, math) == {"y"}
+        assert LW.rounded_operands("store", 27, x.shape[1], C0, math) == {"y"}
         recs += LW.check_bf16_store("stem", "conv fwd (bf16 y)", y, ref)
         o = LW.check_bf16_store("stem", "conv fwd vs other", y, other)[0]
         o.ok, o.note = not o.ok, "must exceed the bound"
         recs.append(o)
     else:
-        recs += _conv_recs("stem", "conv fwd", y, lambda x, w: LW.conv_fwd(x, w, nbr0), ops, r_fwd)
+        recs += _conv_recs("stem", "conv fwd", y, lambda x, w: LW.conv_fwd(x, w, nbr0), ops, f_fwd)
     recs += LW.check_stats("stem", "norm", mean, invstd, y, bn.eps)
     recs += LW.check_running("stem", before[bn], bn, y)
     # relu + pool: the forward's own ReLU decisions are those of the norm-gradient kernel (_stem_masks_of_hip_run)
@@ -87,7 +84,7 @@ def _stem_records(saved, model, out, math, before):
     recs += LW.check_scaled("stem", "norm bwd dgamma", bn.weight.grad, dga, LW.reduction_scale(dz * (y.double() - m64) * is64), rows=n0)
     recs += LW.check_scaled("stem", "norm bwd dbeta", bn.bias.grad, dbe, LW.reduction_scale(dz), rows=n0)
     # conv1.kernel: dY is what the fused kernel recomputes (under its own ReLU decisions) -- fp32 values, rounded where declared
-    r_w = LW.rounded_operands("wgrad", 27, conv_math)
+    r_w = LW.rounded_operands("wgrad", 27, x.shape[1], C0, conv_math, n_out=n0, ldx=x.stride(0))
     xs = x
     dy_w = LW.stem_bwd(g, y, gamma, beta, i2o, sm_w, bn.eps)[0]
     v = LW.stem_wgrad_operand(g, y, mean, invstd, gamma, beta, bn.weight.grad, bn.bias.grad, i2o, n0)
@@ -120,8 +117,10 @@ def _block_records(i, st, saved, m, math, reach, L, before):
     W1, W2 = st.conv1.kernel.detach(), st.conv2.kernel.detach()
     n1m, n2m = st.norm1.bn, st.norm2.bn
     lay = f"block{i}"
-    cm = "fp32" if math == "fp32" else "bf16"
-    fwd3, dg3, wg3 = (LW.rounded_operands(o, 27, cm) for o in ("fwd", "dgrad", "wgrad"))
+    cm = "bf16" if math == "bf16s" else math
+    fwd1, wg1 = (LW.conv_form(o, 27, cin, C, cm, n_out=n_out) for o in ("fwd", "wgrad"))
+    dg1 = LW.conv_form("dgrad", 27, cin, C, cm, n_out=n_out, row_perm=down)
+    fwd3, dg3, wg3 = (LW.conv_form(o, 27, C, C, cm, n_out=n_out) for o in ("fwd", "dgrad", "wgrad"))
     # ---- which launch forms this block's row counts reach (the planners decide by rows)
     ks1 = int(L.mink_conv_plan(n_out, 27, cin, C, 0))
     ks2 = int(L.mink_conv_plan(n_out, 27, C, C, 0))
@@ -130,18 +129,18 @@ def _block_records(i, st, saved, m, math, reach, L, before):
     if n_out <= L.mink_bn_small_rows() and C % 16 == 0:
         reach.add("few-row")
     # ---- forward
-    recs += _conv_recs(lay, "conv1 fwd", y1, lambda x, w: LW.conv_fwd(x, w, nbr1), {"x": x, "w": W1}, fwd3)
+    recs += _conv_recs(lay, "conv1 fwd", y1, lambda x, w: LW.conv_fwd(x, w, nbr1), {"x": x, "w": W1}, fwd1, reach)
     recs += LW.check_stats(lay, "norm1", m1, is1, y1, n1m.eps)
     recs += LW.check_running(lay + " norm1", before[n1m], n1m, y1)
     recs += LW.check_relu_out(lay, "norm1+relu fwd", h1, LW.bn_fwd(y1, n1m.weight, n1m.bias, eps=n1m.eps))
-    recs += _conv_recs(lay, "conv2 fwd", y2, lambda x, w: LW.conv_fwd(x, w, nbr2), {"x": h1, "w": W2}, fwd3)
+    recs += _conv_recs(lay, "conv2 fwd", y2, lambda x, w: LW.conv_fwd(x, w, nbr2), {"x": h1, "w": W2}, fwd3, reach)
     recs += LW.check_stats(lay, "norm2", m2, is2, y2, n2m.eps)
     recs += LW.check_running(lay + " norm2", before[n2m], n2m, y2)
     if down:
         yd, sd = arena[4 * cnt : 5 * cnt].view(n_out, C), arena[5 * cnt : 6 * cnt].view(n_out, C)
         Wd, ndm = st.down.kernel.detach(), st.normd.bn
         recs += _conv_recs(lay, "down fwd", yd, lambda x, w: LW.conv_fwd(x, w, nbrd), {"x": x, "w": Wd},
-                           LW.rounded_operands("fwd", 1, cm))
+                           LW.conv_form("fwd", 1, cin, C, cm, n_out=n_out), reach)
         recs += LW.check_stats(lay, "normd", md, isd, yd, ndm.eps)
         recs += LW.check_running(lay + " normd", before[ndm], ndm, yd)
         ref = LW.bn_fwd(yd, ndm.weight, ndm.bias, eps=ndm.eps)
@@ -160,14 +159,14 @@ def _block_records(i, st, saved, m, math, reach, L, before):
         recs += LW.check_bn_bwd(lay, "normd bwd", gs["g_yd"], ndm.weight.grad, ndm.bias.grad, gs["g_res"], yd, ndm.weight, ndm.bias, None,
                                 eps=ndm.eps)
         recs += _conv_recs(lay, "down dgrad", gs["g_sc"], lambda dy, w: dy @ w[0].t(), {"dy": gs["g_yd"], "w": Wd},
-                           LW.rounded_operands("dgrad", 1, cm))
+                           LW.conv_form("dgrad", 1, cin, C, cm, n_out=n_out, row_perm=True), reach)
         recs += _conv_recs(lay, "down wgrad", st.down.kernel.grad, lambda x, dy: LW.conv_wgrad(x, dy, nbrd), {"x": x, "dy": gs["g_yd"]},
-                           LW.rounded_operands("wgrad", 1, cm))
-    recs += _conv_recs(lay, "conv2 dgrad", gs["g_h1"], lambda dy, w: LW.conv_dgrad(dy, w, nbr2, n_out), {"dy": gs["g_y2"], "w": W2}, dg3)
-    recs += _conv_recs(lay, "conv2 wgrad", st.conv2.kernel.grad, lambda x, dy: LW.conv_wgrad(x, dy, nbr2), {"x": h1, "dy": gs["g_y2"]}, wg3)
+                           LW.conv_form("wgrad", 1, cin, C, cm, n_out=n_out), reach)
+    recs += _conv_recs(lay, "conv2 dgrad", gs["g_h1"], lambda dy, w: LW.conv_dgrad(dy, w, nbr2, n_out), {"dy": gs["g_y2"], "w": W2}, dg3, reach)
+    recs += _conv_recs(lay, "conv2 wgrad", st.conv2.kernel.grad, lambda x, dy: LW.conv_wgrad(x, dy, nbr2), {"x": h1, "dy": gs["g_y2"]}, wg3, reach)
     recs += LW.check_bn_bwd(lay, "norm1 bwd", gs["g_y1"], n1m.weight.grad, n1m.bias.grad, gs["g_h1"], y1, n1m.weight, n1m.bias, h1 > 0,
                             eps=n1m.eps)
-    recs += _conv_recs(lay, "conv1 wgrad", st.conv1.kernel.grad, lambda x, dy: LW.conv_wgrad(x, dy, nbr1), {"x": x, "dy": gs["g_y1"]}, wg3)
+    recs += _conv_recs(lay, "conv1 wgrad", st.conv1.kernel.grad, lambda x, dy: LW.conv_wgrad(x, dy, nbr1), {"x": x, "dy": gs["g_y1"]}, wg1, reach)
     if down:
         # the class-permuted strided data gradient: the kernel gathers through the transposed table in class order -- that form
         # of the reference must agree with the forward-table scatter (tables and permutation), then g_x as the composite
@@ -181,7 +180,7 @@ def _block_records(i, st, saved, m, math, reach, L, before):
         recs.append(LW.Record(lay, "conv1 dgrad tables", n_in, tuple(a.shape), "float64", e, 1e-12, e <= 1e-12, "transposed + perm vs scatter"))
         sc = LW.scatter_rows(gs["g_sc"], nbrd[:, 0], n_in)
         recs += _conv_recs(lay, "conv1 dgrad + down", gs["g_x"], lambda dy, w: LW.conv_dgrad(dy, w, nbr1, n_in) + sc,
-                           {"dy": gs["g_y1"], "w": W1}, dg3)
+                           {"dy": gs["g_y1"], "w": W1}, dg1, reach)
     else:
         stages = saved.plan.stages
         may_defer = i > 0 and stages[i - 1].level == st.level and stages[i - 1].C == cin
@@ -189,24 +188,29 @@ def _block_records(i, st, saved, m, math, reach, L, before):
         if deferred:
             reach.add("deferred identity")
         else:
-            recs += _conv_recs(lay, "conv1 dgrad", gs["g_xa"], lambda dy, w: LW.conv_dgrad(dy, w, nbr1, n_in), {"dy": gs["g_y1"], "w": W1}, dg3)
+            recs += _conv_recs(lay, "conv1 dgrad", gs["g_xa"], lambda dy, w: LW.conv_dgrad(dy, w, nbr1, n_in), {"dy": gs["g_y1"], "w": W1}, dg1, reach)
         res = gs["g_res"].double()
         recs += _conv_recs(lay, "conv1 dgrad + res" + (" (deferred)" if deferred else ""), gs["g_x"],
-                           lambda dy, w: LW.conv_dgrad(dy, w, nbr1, n_in) + res, {"dy": gs["g_y1"], "w": W1}, dg3)
+                           lambda dy, w: LW.conv_dgrad(dy, w, nbr1, n_in) + res, {"dy": gs["g_y1"], "w": W1}, dg1, reach)
     return recs
 
 
 @pytest.mark.timeout(60)
 @pytest.mark.parametrize("name,batch,math,expect", [
     ("ResNet14", 16, "fp32", {"few-row", "split-K", "class-permuted strided dgrad"}),
-    ("ResNet14", 16, "bf16", {"few-row", "split-K", "class-permuted strided dgrad"}),
-    ("ResNet14", 16, "bf16s", {"few-row", "split-K", "class-permuted strided dgrad"}),
+    ("ResNet14", 16, "bf16", {"few-row", "split-K", "class-permuted strided dgrad", "form: dense gather_gemm2 bf16",
+                              "form: class-permuted compact bf16", "form: dense_xwt", "form: wgrad16<1>"}),
+    ("ResNet14", 16, "bf16s", {"few-row", "split-K", "class-permuted strided dgrad", "form: class-permuted compact bf16"}),
     ("ResNet34", 4, "fp32", {"few-row", "split-K", "class-permuted strided dgrad", "deferred identity"}),
+    ("ResNet14", 16, "bf16x3", {"few-row", "split-K", "class-permuted strided dgrad", "form: dense gather_gemm2 bf16x3",
+                                "form: staged gather_gemm2 (transposed weights) bf16x3", "form: dense_xwt", "form: wgrad fp32"}),
 ])
 def test_every_operator_teacher_forced_against_float64(name, batch, math, expect):
     """Bench.py's own step (three passes, maps prepared ahead, forked shortcut, flat gradient sink) at BASELINE's shapes; from its
     last pass every forward and backward operator of the stem and of every block, and every parameter gradient as it sits in
-    the flat buffer, against float64 fed with that pass's own stored inputs (bounds: tests/layerwise.py)."""
+    the flat buffer, against float64 fed with that pass's own stored inputs (bounds: tests/layerwise.py).  Each convolution is
+    judged on what its launch form multiplies (layerwise.conv_form: bf16-rounded, split-bf16 or exact fp32 operands), and the
+    forms reached ("form: ...") are part of what each configuration must reach."""
     from nerf_downstream_amd._lib import lib
     from nerf_downstream_amd.minkowski import functional as Fn
     from nerf_downstream_amd.minkowski import trunk

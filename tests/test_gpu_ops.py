@@ -875,6 +875,49 @@ def test_stream_k_launch_of_the_mid_layer_kernel(n_out, cin, cout):
         Fn._PLAN_CACHE.clear()
 
 
+@pytest.mark.parametrize("ldx,ksplit", [(66, 20), (66, 8), (66, 0), (64, 20)])
+def test_stream_k_gate_with_operands_the_compacted_kernel_cannot_take(ldx, ksplit):
+    """Stream-K on (mink_conv_set_pipeline bit 3) for a shape whose plan takes it, with a row stride that is not a multiple of four
+    (ldx = 66: the launch falls to the scalar gather_gemm_kernel) and a split of `ksplit` slabs (0: the plan's) -- 20 and 8 are splits
+    for which cdiv(K, cdiv(K, ksplit)) < ksplit.  gather_gemm_impl enables stream-K only where the row-compacted kernel runs: any other
+    kernel splits by kper = cdiv(K, ksplit), and the stream-K slab count would hand it trailing slices that start at or past K (at
+    20 slabs past offset 31, where the offset mask's shifts wrap).  The aligned operands (ldx = 64) take the stream-K kernel itself
+    with spare slabs.  Forward against float64 on a sample of rows, at the bound of the stream-K test above."""
+    from nerf_downstream_amd._lib import lib
+    from nerf_downstream_amd.minkowski import functional as Fn
+
+    dev = torch.device("cuda", 0)
+    n_out, K, cin, cout = 12800, 27, 64, 64
+    g = torch.Generator().manual_seed(ldx + ksplit)
+    nbr = torch.randint(0, n_out, (n_out, K), generator=g, dtype=torch.int32)
+    nbr[torch.rand(n_out, K, generator=g) < 0.48] = -1
+    nbr[:, 13] = -1
+    x = torch.randn(n_out, ldx, generator=g).to(dev)[:, :cin]
+    w = (torch.randn(K, cin, cout, generator=g) * 0.1).to(dev)
+    nd = nbr.to(dev)
+    L = lib()
+    sel = torch.cat([torch.arange(0, n_out, 97), torch.tensor([0, 63, 64, n_out - 1])]).unique().to(dev)
+    ref = torch.zeros(len(sel), cout, dtype=torch.float64, device=dev)
+    for k in range(K):
+        col = nd[sel, k].long()
+        ok = col >= 0
+        ref[ok] += x[col[ok]].double() @ w[k].double()
+    scale = float(ref.abs().max())
+    try:
+        L.mink_conv_set_pipeline(8)
+        Fn._PLAN_CACHE.clear()
+        assert Fn._plan_ksplit(L, n_out, K, cin, cout, 0) > 1, "the plan must take stream-K at this shape"
+        Fn._FORCE_KSPLIT = ksplit
+        y = Fn.gather_gemm(x, w, nd, cout)
+        torch.cuda.synchronize()
+    finally:
+        Fn._FORCE_KSPLIT = 0
+        L.mink_conv_set_pipeline(0)
+        Fn._PLAN_CACHE.clear()
+    err = float((y[sel].double() - ref).abs().max()) / scale
+    assert err < 3e-6, (ldx, ksplit, err)
+
+
 @pytest.mark.parametrize("n_out,K,cin,cout,perm_rows", [(130, 27, 64, 64, False), (1000, 27, 128, 128, False), (517, 27, 256, 64, False),
                                                          (64, 27, 64, 64, False), (700, 27, 128, 64, True), (300, 9, 512, 64, True),
                                                          (2100, 27, 64, 64, True)])

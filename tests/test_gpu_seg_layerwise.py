@@ -202,14 +202,22 @@ def _launch_forms(L, n_rows, K, cin, cout, perm, wt, stats):
 
 
 # ------------------------------------------------------------------------------------------------ checks
-def _other(rounded, names):
-    return frozenset() if rounded else frozenset(names)
+def _conv_recs(layer, op, got, fn, ops, cf=None, reach=None, K=None):
+    """float64 on the operands as the launch form `cf` (layerwise.conv_form; None: fp32 math, the operands as stored) multiplies
+    them, with the other rounding as the discriminator.  Under reduced math the form joins `reach` ("form: <kernel>", weight
+    gradients with their kernel volume)."""
+    cf = cf or LW.conv_form("fwd", 27, 64, 64, "fp32")  # (fp32 math rounds nothing, whatever the shape)
+    if reach is not None and LW.CONV_MATH[LW_MATH[0]]:
+        fam = cf.form.split(" G")[0].split("<")[0]
+        reach.add(f"form: {fam}" + (f" K={K}" if op.endswith("wgrad") else ""))
+    return LW.check_conv(layer, op, got, LW.form_reference(fn, ops, cf), cf.rounded, LW.other_reference(fn, ops, cf))
 
 
-def _conv_recs(layer, op, got, fn, ops):
-    """fp32 math: float64 on the operands as stored, with every operand rounded to bf16 as the discriminator."""
-    r = LW.rounded_operands("fwd", 27, "fp32")
-    return LW.check_conv(layer, op, got, fn(**LW.apply_rounding(ops, r)), r, fn(**LW.apply_rounding(ops, _other(r, ops))))
+LW_MATH = ["fp32"]  # the conv math of the run _check judges (set by _res16unet_run)
+
+
+def _form(op, K, cin, cout, n_out, **kw):
+    return LW.conv_form(op, K, cin, cout, LW_MATH[0], n_out=n_out, **kw)
 
 
 class Contrib:
@@ -267,12 +275,13 @@ def _check(model, cap, tabs, levels, inverse, L, training, labels=None, before=N
         if m.use_mm:  # 1x1 shortcuts and the classifier: torch mm forward, streaming weight gradient over an identity table
             b = None if m.bias is None else m.bias.detach()
             recs += _conv_recs(lay, "pointwise fwd" + (" + bias" if b is not None else ""), y,
-                               lambda x, w: LW.pointwise_fwd(x, w, b), {"x": x, "w": W})
+                               lambda x, w: LW.pointwise_fwd(x, w, b), {"x": x, "w": W})  # (a library GEMM: fp32 under every math)
             if training:
                 assert x.shape[0] >= 4096
                 reach.add("pointwise")
                 contrib.add(x, lay + " dgrad", LW.pointwise_dgrad(gy, W), conv=True)
-                recs += _conv_recs(lay, "pointwise wgrad", m.kernel.grad, lambda x, dy: LW.pointwise_wgrad(x, dy), {"x": x, "dy": gy})
+                recs += _conv_recs(lay, "pointwise wgrad", m.kernel.grad, lambda x, dy: LW.pointwise_wgrad(x, dy), {"x": x, "dy": gy},
+                                   _form("wgrad", 1, cin, cout, x.shape[0]), reach, 1)
                 checked_params.add(lay + ".kernel")
                 if b is not None:
                     ref = LW.bias_grad(gy)
@@ -283,15 +292,21 @@ def _check(model, cap, tabs, levels, inverse, L, training, labels=None, before=N
         if isinstance(m, ME.MinkowskiConvolutionTranspose):
             nbr = tabs[(ts_out, ts_in, m.kernel_size, 1)][0]  # the fine -> coarse table of the convolution it inverts
             n_fine = levels[ts_out]
-            recs += _conv_recs(lay, "tconv fwd", y, lambda x, w: LW.tconv_fwd(x, w, nbr, n_fine), {"x": x, "w": W})
+            recs += _conv_recs(lay, "tconv fwd", y, lambda x, w: LW.tconv_fwd(x, w, nbr, n_fine), {"x": x, "w": W},
+                               _form("fwd", 8, cin, cout, n_fine, row_perm=True), reach)
             perm = tabs[("perm", ts_out, 128)]
             f = _launch_forms(L, perm.numel(), 8, cin, cout, True, False, False)
             reach |= {"class-permuted compact (transposed fwd)" if "class-permuted compact" in f else
                       "staged gather_gemm2 (transposed fwd)" if "staged gather_gemm2" in f else "transposed fwd: other"}
             if training:
                 f |= _launch_forms(L, levels[ts_in], 8, cout, cin, False, True, False)
-                contrib.add(x, lay + " tconv dgrad", LW.tconv_dgrad(gy, W, nbr), conv=True)
-                recs += _conv_recs(lay, "tconv wgrad", m.kernel.grad, lambda x, dy: LW.tconv_wgrad(x, dy, nbr), {"x": x, "dy": gy})
+                cfd = _form("dgrad", 8, cin, cout, levels[ts_in])
+                contrib.add(x, lay + " tconv dgrad", LW.form_reference(lambda dy, w: LW.tconv_dgrad(dy, w, nbr), {"dy": gy, "w": W}, cfd),
+                            conv=True)
+                if LW_MATH[0] != "fp32":
+                    reach.add("form: " + cfd.form)
+                recs += _conv_recs(lay, "tconv wgrad", m.kernel.grad, lambda x, dy: LW.tconv_wgrad(x, dy, nbr), {"x": x, "dy": gy},
+                                   _form("wgrad", 8, cin, cout, n_fine), reach, 8)
                 checked_params.add(lay + ".kernel")
         else:
             nbr = tabs[(ts_in, ts_out, m.kernel_size, 1)][0]
@@ -300,7 +315,8 @@ def _check(model, cap, tabs, levels, inverse, L, training, labels=None, before=N
             if cin % 4 and not x.requires_grad:  # functional.py ConvolutionFunction.forward: one zero column
                 cin_eff = cin + 4 - cin % 4
                 reach.add(f"stem padded {cin}->{cin_eff}")
-            recs += _conv_recs(lay, "conv fwd", y, lambda x, w: LW.conv_fwd(x, w, nbr), {"x": x, "w": W})
+            recs += _conv_recs(lay, "conv fwd", y, lambda x, w: LW.conv_fwd(x, w, nbr), {"x": x, "w": W},
+                               _form("fwd", W.shape[0], cin_eff, cout, y.shape[0]), reach)
             f = _launch_forms(L, y.shape[0], W.shape[0], cin_eff, cout, False, False, stats)
             if training:
                 if x.requires_grad:
@@ -317,8 +333,14 @@ def _check(model, cap, tabs, levels, inverse, L, training, labels=None, before=N
                         e = LW.conv_errors(LW.conv_dgrad_gather(gy64, W, ent[1], perm=perm), a)[0]
                         recs.append(LW.Record(lay, "dgrad tables", n_in, tuple(a.shape), "float64", e, 1e-12, e <= 1e-12,
                                               "transposed + perm vs scatter"))
-                    contrib.add(x, lay + " dgrad", LW.conv_dgrad(gy, W, nbr, n_in), conv=True)
-                recs += _conv_recs(lay, "conv wgrad", m.kernel.grad, lambda x, dy: LW.conv_wgrad(x, dy, nbr), {"x": x, "dy": gy})
+                    cfd = _form("dgrad", W.shape[0], cin, cout, n_in, row_perm=ts_out != ts_in)
+                    if LW_MATH[0] != "fp32":
+                        reach.add("form: " + cfd.form)
+                    contrib.add(x, lay + " dgrad", LW.form_reference(lambda dy, w: LW.conv_dgrad(dy, w, nbr, n_in), {"dy": gy, "w": W}, cfd),
+                                conv=True)
+                # (the stem's input is padded to cin_eff channels for its kernels; the gradient of the padding is dropped)
+                recs += _conv_recs(lay, "conv wgrad", m.kernel.grad, lambda x, dy: LW.conv_wgrad(x, dy, nbr), {"x": x, "dy": gy},
+                                   _form("wgrad", W.shape[0], cin_eff, cout, y.shape[0]), reach, W.shape[0])
                 checked_params.add(lay + ".kernel")
         if "row-compacted" in f and lay.startswith("conv4p8s2"):
             reach.add("row-compacted (conv4p8s2)")
@@ -433,13 +455,51 @@ def test_res16unet_every_operator_teacher_forced_at_scannet_shapes(oracle_maps, 
     """One scannet_semseg.gin training batch (8 rooms, train.batch_size), one training-mode forward + slice + cross
     entropy + backward: every map bit for bit, every operator and parameter gradient against float64; then one eval-mode
     forward on 2 uncropped validation scenes, every operator's forward."""
+    from nerf_downstream_amd.minkowski import functional as Fn
+
+    assert Fn.conv_math() == "fp32"
+    _res16unet_run(oracle_maps, tmp_path, fused, "fp32", EXPECT | ({"stats direct", "stats split"} if fused else set()))
+
+
+# Under --math bf16 every convolution is judged on what its launch form multiplies (layerwise.conv_form), and the forms reached
+# are asserted: the transposed convolution's forward on the staged bf16 gather_gemm2 (class permutation, forward weights), the
+# strided data gradients on the class-permuted compact bf16 kernel (the staged one below 64 channels, with a channel tail at 48),
+# weight gradients on wgrad16 at K = 8 (the k2s2 down convolutions) and K = 27 beside the exact-fp32 kernel of the 32 / 48 /
+# 96-wide layers (K = 1, 8 and 27), and the stem's on the streaming bf16 kernel.
+EXPECT_BF16 = {"stem padded 3->4", "pointwise", "segment_mean", "slice", "composite gradient",
+               "form: staged gather_gemm2 (transposed-conv fwd) bf16", "form: class-permuted compact bf16",
+               "form: staged gather_gemm2 (transposed weights) bf16", "form: staged gather_gemm2 (transposed weights) + channel tail bf16",
+               "form: dense gather_gemm2 bf16", "form: dense gather_gemm2 + channel tail bf16",
+               "form: dense gather_gemm2 (transposed weights) bf16", "form: dense gather_gemm2 (transposed weights) + channel tail bf16",
+               "form: wgrad16 K=8", "form: wgrad16 K=27", "form: wgrad fp32 K=1", "form: wgrad fp32 K=8", "form: wgrad fp32 K=27",
+               "form: wgrad_stream_bf16 K=27"}
+# (entries of the fp32 restatement _launch_forms: dropped from a reduced-math run's list, where they do not apply)
+FP32_PLAN = ("row-compacted", "class-permuted compact (transposed fwd)", "staged gather_gemm2 (transposed fwd)", "transposed fwd: other",
+             "class-permuted dgrad", "strided dgrad: other", "dense unsplit", "dense with channel tail", "split-K", "stats ")
+
+
+@pytest.mark.timeout(90)
+def test_res16unet_every_operator_teacher_forced_under_bf16_math(oracle_maps, tmp_path):
+    """The same batch, forward and backward under set_conv_math("bf16") (fused stem and blocks)."""
+    from nerf_downstream_amd.minkowski import functional as Fn
+
+    old = Fn.set_conv_math("bf16")
+    try:
+        _res16unet_run(oracle_maps, tmp_path, True, "bf16", EXPECT_BF16)
+    finally:
+        Fn.set_conv_math(old)
+        LW_MATH[0] = "fp32"
+
+
+def _res16unet_run(oracle_maps, tmp_path, fused, math, expect):
     import time
 
     from nerf_downstream_amd._lib import lib
     from nerf_downstream_amd.minkowski import functional as Fn
 
     t0 = time.time()
-    assert Fn.conv_math() == "fp32"
+    assert Fn.conv_math() == math
+    LW_MATH[0] = math
     L = lib()
     model = _model(fused)
     model.train()
@@ -463,21 +523,22 @@ def test_res16unet_every_operator_teacher_forced_at_scannet_shapes(oracle_maps, 
         assert ("transposed", ts, 2 * ts, 2, 1) in seen and ("perm", ts, 128) in seen, ts
     nbr1 = tabs[(1, 1, 3, 1)][0]
     live = float((nbr1 >= 0).sum(1).double().mean())
-    print(f"\n[Res16UNet fused={fused}] field rows {field.F.shape[0]}, rows per tensor stride {levels}, "
+    print(f"\n[Res16UNet fused={fused} {math}] field rows {field.F.shape[0]}, rows per tensor stride {levels}, "
           f"live offsets per row at ts 1: {live:.2f} of 27; {len(seen)} tables / permutations bit-exact")
     assert levels[1] > 400_000 and live > 4.0, "the batch must look like ScanNet's: many rows, several live offsets per row"
     with torch.no_grad():
         recs, reach = _check(model, cap, tabs, levels, inverse, L, True, labels, before)
-    expect = EXPECT | ({"stats direct", "stats split"} if fused else set())
+    if math != "fp32":
+        reach = {r for r in reach if not r.startswith(FP32_PLAN)}
     n_wgrad = sum(1 for r in recs if r.op.endswith("wgrad") and not r.op.endswith("vs other"))
     assert n_wgrad == sum(1 for n, _ in model.named_parameters() if n.endswith(".kernel"))
-    bad = LW.report(recs, f"Res16UNet train fused={fused}", force=True)
+    bad = LW.report(recs, f"Res16UNet train fused={fused} {math}", force=True)
     worst = {}
     for r in recs:
         if not r.op.endswith("vs other") and np.isfinite(r.err):
             kind = r.op.split(" [")[0].split(" (")[0]
             worst[kind] = max(worst.get(kind, 0.0), r.err / r.bound if r.bound else r.err)
-    print(f"[Res16UNet train fused={fused}] {len(recs)} checks; launch forms reached: {sorted(reach)}")
+    print(f"[Res16UNet train fused={fused} {math}] {len(recs)} checks; launch forms reached: {sorted(reach)}")
     print("  worst error / bound per operator kind: " + ", ".join(f"{k} {v:.2f}" for k, v in sorted(worst.items())))
     assert not bad, [r.line() for r in bad]
     assert expect <= reach, ("launch forms this configuration must reach", sorted(expect - reach))
@@ -499,7 +560,7 @@ def test_res16unet_every_operator_teacher_forced_at_scannet_shapes(oracle_maps, 
     with torch.no_grad():
         erecs, _ = _check(model, cap, tabs, levels, inverse, L, False)
     erecs += LW.check_running_unchanged(before, model)
-    bad = LW.report(erecs, f"Res16UNet eval fused={fused}", force=True)
-    print(f"[Res16UNet eval fused={fused}] {len(erecs)} forward checks over {levels[1]} rows; {time.time() - t0:.1f} s in all "
+    bad = LW.report(erecs, f"Res16UNet eval fused={fused} {math}", force=True)
+    print(f"[Res16UNet eval fused={fused} {math}] {len(erecs)} forward checks over {levels[1]} rows; {time.time() - t0:.1f} s in all "
           f"(training step {t_run:.1f} s)")
     assert not bad, [r.line() for r in bad]

@@ -47,6 +47,12 @@ def T(a):
     return torch.from_numpy(np.ascontiguousarray(a))
 
 
+def table(op, K, math):
+    """The rounding table of a 64-wide Mink-ResNet14 mid layer (the block convolutions, a K = 1 strided shortcut) -- applied to
+    this scene's 16-wide operands: these tests judge the comparators, tests/test_reduced_math_cpu.py the table itself."""
+    return LW.rounded_operands(op, K, 64, 64, math, n_out=1000, row_perm=K == 1)
+
+
 def oracle_conv(x, w, nbr, gy, rounded=None, rnd=LW.bf16_rne):
     """The oracle's fp32 convolution (oracle.me_cpu._ConvFn) as the "kernel": -> (y, dx, dw).  `rounded` = {op: operands}:
     what it rounds (with `rnd`) before its fp32 products, through oracle.me_cpu.OPERAND_HOOK."""
@@ -80,7 +86,7 @@ def conv_checks(sc, y, dx, dw, math="fp32", nbr=None, w=None):
         ("dgrad", dx, lambda dy, w: LW.conv_dgrad(dy, w, nbr_t, sc.n), {"dy": sc.gy, "w": w}),
         ("wgrad", dw, lambda x, dy: LW.conv_wgrad(x, dy, nbr_t), {"x": sc.x, "dy": sc.gy}),
     ]:
-        r = LW.rounded_operands(op, 27, math)
+        r = table(op, 27, math)
         other = frozenset() if r else frozenset(ops)
         recs += LW.check_conv("L", op, got, fn(**LW.apply_rounding(ops, r)), r, fn(**LW.apply_rounding(ops, other)))
     return recs
@@ -92,7 +98,7 @@ def failed(recs):
 
 @pytest.mark.parametrize("math", ["fp32", "bf16"])
 def test_clean_convolution_passes(sc, math):
-    rounded = {op: LW.rounded_operands(op, 27, math) for op in ("fwd", "dgrad", "wgrad")}
+    rounded = {op: table(op, 27, math) for op in ("fwd", "dgrad", "wgrad")}
     y, dx, dw = oracle_conv(sc.x, sc.w, sc.nbr, sc.gy, rounded if math != "fp32" else None)
     recs = conv_checks(sc, y, dx, dw, math)
     assert not failed(recs), [r.line() for r in recs]
@@ -167,7 +173,7 @@ def test_missing_splitk_slab_is_flagged(sc):
 
 
 def test_bf16_truncation_is_flagged(sc):
-    rounded = {op: LW.rounded_operands(op, 27, "bf16") for op in ("fwd", "dgrad", "wgrad")}
+    rounded = {op: table(op, 27, "bf16") for op in ("fwd", "dgrad", "wgrad")}
     y, dx, dw = oracle_conv(sc.x, sc.w, sc.nbr, sc.gy, rounded, rnd=LW.bf16_trunc)
     assert {"fwd", "dgrad", "wgrad"} <= failed(conv_checks(sc, y, dx, dw, "bf16"))
 
@@ -180,7 +186,7 @@ def test_rounding_table_mismatch_is_flagged(sc):
     # ... or rounds where the table says it does not (the 1x1x1 shortcut's data gradient is exact fp32)
     gd = LW.bf16_rne(sc.gy2) @ LW.bf16_rne(sc.wd[0]).t()
     ops = {"dy": sc.gy2, "w": sc.wd}
-    r = LW.rounded_operands("dgrad", 1, "bf16")
+    r = table("dgrad", 1, "bf16")
     assert r == frozenset()
     fn = lambda dy, w: dy @ w[0].t()  # noqa: E731
     recs = LW.check_conv("L", "down dgrad", gd, fn(**LW.apply_rounding(ops, r)), r, fn(**LW.apply_rounding(ops, {"dy", "w"})))
