@@ -348,6 +348,42 @@ int mink_softmax_ce_backward(const float *prob, const int64_t *labels, const flo
 int mink_segment_mean(const float *x, int32_t ldx, int32_t C, const int32_t *members, const int32_t *seg,
                       int64_t n_out, float *y, void *stream);
 
+/* ------------------------------------------------------------------ segmentation tail (csrc/seghead.hip)
+ * SparseTensor.slice() (reference res16unet.py:435), any C >= 1.  Forward: y[i][:] = x[idx[i]][:], i < n (an index outside
+ * [0, n_src) gives a zero row).  Backward: y[r][:] = sum of x[members[j]][:] over j in [seg[r], seg[r+1]), in member
+ * order (fixed-order fp32 sum: bitwise reproducible), with the (members, seg) pair TensorField.sparse() builds for
+ * mink_segment_mean. */
+int mink_rows_gather(const float *x, int64_t ldx, int64_t n_src, int32_t C, const int32_t *idx, int64_t n, float *y, void *stream);
+int mink_segment_sum(const float *x, int32_t ldx, int32_t C, const int32_t *members, const int32_t *seg,
+                     int64_t n_out, float *y, void *stream);
+
+/* torch.nn.functional.cross_entropy(z, labels, weight=w, ignore_index=ignore_label) (mean reduction) over per-point logits
+ * z[n][C] (fp32, row stride ldz >= C), 2 <= C <= 128, with the prediction, the confusion matrix and the label counts out
+ * of the same pass over the logits (reference modules/segmentation_training.py SegLoss :27-44, utils fast_hist).
+ *   labels        : int64 [n] (labels_int64 != 0) or int32 [n]
+ *   w             : class weights [C], NULL = all ones
+ *   a row is VALID when 0 <= label < C and label != ignore_label, IGNORED when label == ignore_label and BAD otherwise;
+ *   bad rows are counted and otherwise treated like ignored ones (no device-side assert)
+ *   lse[n]        : log sum exp of every row -- all the backward pass needs besides the logits
+ *   pred[n]       : int32 argmax (lowest index on ties); NULL to skip
+ *   hist[C*C]     : int64, hist[label * C + pred] over the valid rows (zeroed here); NULL to skip
+ *   stats         : 40 bytes, 8-byte aligned: double num = sum_valid w[y] * (lse - z[y]); double den = sum_valid w[y];
+ *                   int64 n_valid; int64 n_ignored; int64 n_bad -- in this order
+ *   loss          : fp32 device scalar num / den (NaN when nothing is valid, as torch gives)
+ *   workspace     : >= mink_seg_ce_workspace_bytes(n, C), 8-byte aligned (per-workgroup partial sums)
+ * The assignment of rows to workgroups is fixed, every workgroup writes one (num, den) partial in double and a second
+ * launch adds the partials in index order: the result is bitwise the same from run to run.  n == 0 writes loss = NaN,
+ * a zero histogram and zero stats.
+ * Backward: dz[i][j] = g / den * valid_i * w[y_i] * (exp(z[i][j] - lse[i]) - [j == y_i]); g = *grad_loss and den = stats'
+ * second double are read on the device; every element of the dense dz[n][C] is written (zeros on ignored / bad rows, and
+ * everywhere when den == 0, where torch writes NaN). */
+int64_t mink_seg_ce_workspace_bytes(int64_t n, int32_t C);
+int mink_seg_ce_forward(const float *z, int64_t ldz, const void *labels, int32_t labels_int64, const float *w, int64_t ignore_label,
+                        int64_t n, int32_t C, float *lse, int32_t *pred, int64_t *hist, void *stats, float *loss, void *workspace,
+                        int64_t workspace_bytes, void *stream);
+int mink_seg_ce_backward(const float *z, int64_t ldz, const void *labels, int32_t labels_int64, const float *w, int64_t ignore_label,
+                         const float *lse, const void *stats, const float *grad_loss, int64_t n, int32_t C, float *dz, void *stream);
+
 /* ------------------------------------------------------------------ batch norm / relu / add
  * MinkowskiBatchNorm == torch.nn.BatchNorm1d on the feature matrix
  * (modules/common.py:22-24; witness resnet.py:101-105), MinkowskiReLU (resnet.py:61),

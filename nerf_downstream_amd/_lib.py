@@ -162,6 +162,11 @@ SIGNATURES = {
     "mink_softmax_ce_forward": (ctypes.c_int, [_p, _p, _i32, _i32, _p, _p, _p]),
     "mink_softmax_ce_backward": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _p, _p]),
     "mink_segment_mean": (ctypes.c_int, [_p, _i32, _i32, _p, _p, _i64, _p, _p]),
+    "mink_rows_gather": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _i64, _p, _p]),
+    "mink_segment_sum": (ctypes.c_int, [_p, _i32, _i32, _p, _p, _i64, _p, _p]),
+    "mink_seg_ce_workspace_bytes": (_i64, [_i64, _i32]),
+    "mink_seg_ce_forward": (ctypes.c_int, [_p, _i64, _p, _i32, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "mink_seg_ce_backward": (ctypes.c_int, [_p, _i64, _p, _i32, _p, _i64, _p, _p, _p, _i64, _i32, _p, _p]),
     "mink_bn_workspace_bytes": (_i64, [_i64, _i32]),
     "mink_bn_stats": (ctypes.c_int, [_p, _i64, _i32, _f32, _f32, _p, _p, _p, _p, _p, _i64, _p]),
     "mink_bn_apply": (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _p, _p]),

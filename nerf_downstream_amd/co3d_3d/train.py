@@ -123,19 +123,29 @@ def load_checkpoint(path, model, optimizer=None, scheduler=None, weights_only=Fa
 
 
 @torch.no_grad()
-def validate(module, loader, device, world):
+def validation_pass(module, loader, device, world, on_batch=None):
+    """One pass over `loader` in eval mode -> the module's accumulable vector summed over batches and ranks, on the device
+    (classification: loss*n, correct@1, correct@5, n; segmentation: loss*n, n, confusion matrix).  `on_batch(index, batch)`,
+    when given, is called after each batch's val_accumulate (co3d_3d/eval.py saves predictions there)."""
     model = module.model
     was_training = model.training
     model.eval()
-    tot = None  # the module's accumulable vector (classification: loss*n, correct@1, correct@5, n; segmentation: + confusion matrix)
-    for batch in loader:
+    tot = None
+    for i, batch in enumerate(loader):
         batch = _to_device(batch, device)
         v = module.val_accumulate(batch)
         tot = v if tot is None else tot + v
+        if on_batch is not None:
+            on_batch(i, batch)
     if world > 1:
         dist.all_reduce(tot)
     model.train(was_training)
-    return module.val_metrics(tot)
+    return tot
+
+
+@torch.no_grad()
+def validate(module, loader, device, world):
+    return module.val_metrics(validation_pass(module, loader, device, world))
 
 
 @gin.configurable

@@ -970,6 +970,8 @@ __global__ __launch_bounds__(EB) void global_avg_bwd_kernel(const float *__restr
   st4(dx + i * (int64_t)(4 * C4) + c, make_float4(g.x * inv, g.y * inv, g.z * inv, g.w * inv));
 }
 
+// MEAN: TensorField.sparse(); !MEAN (the plain sum, same member order): the backward of SparseTensor.slice()
+template <bool MEAN>
 __global__ __launch_bounds__(EB) void segment_mean_kernel(const float *__restrict__ x, int ldx, int C,
                                                           const int *__restrict__ members,
                                                           const int *__restrict__ seg, int64_t n_out,
@@ -981,7 +983,7 @@ __global__ __launch_bounds__(EB) void segment_mean_kernel(const float *__restric
   const int beg = seg[u], end = seg[u + 1];
   float s = 0.f;
   for (int j = beg; j < end; ++j) s += x[(int64_t)members[j] * ldx + c];  // input-row order
-  y[idx] = s / (float)(end - beg);
+  y[idx] = MEAN ? s / (float)(end - beg) : s;
 }
 
 // Workgroups of a column reduction over n rows with `rlanes` row lanes per workgroup: eight rows per thread where the rows are
@@ -1529,8 +1531,19 @@ int mink_segment_mean(const float *x, int32_t ldx, int32_t C, const int32_t *mem
   MINK_REQUIRE(C >= 1 && ldx >= C && n_out >= 0, "segment_mean: bad shape");
   if (n_out == 0) return MINK_OK;
   MINK_REQUIRE(x && members && seg && y, "segment_mean: NULL pointer");
-  segment_mean_kernel<<<dim3((unsigned)cdiv(n_out * C, EB)), EB, 0, (hipStream_t)stream>>>(x, ldx, C, members, seg,
-                                                                                          n_out, y);
+  segment_mean_kernel<true><<<dim3((unsigned)cdiv(n_out * C, EB)), EB, 0, (hipStream_t)stream>>>(x, ldx, C, members, seg,
+                                                                                                n_out, y);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_segment_sum(const float *x, int32_t ldx, int32_t C, const int32_t *members, const int32_t *seg,
+                     int64_t n_out, float *y, void *stream) {
+  MINK_REQUIRE(C >= 1 && ldx >= C && n_out >= 0, "segment_sum: bad shape");
+  if (n_out == 0) return MINK_OK;
+  MINK_REQUIRE(x && members && seg && y, "segment_sum: NULL pointer");
+  segment_mean_kernel<false><<<dim3((unsigned)cdiv(n_out * C, EB)), EB, 0, (hipStream_t)stream>>>(x, ldx, C, members, seg,
+                                                                                                 n_out, y);
   MINK_CHECK_LAUNCH();
   return MINK_OK;
 }

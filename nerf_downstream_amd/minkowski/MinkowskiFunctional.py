@@ -34,3 +34,8 @@ def gelu(input):
 
 def prelu(input, weight):
     return _wrap(input, Fn.ActivationFunction.apply(input.F, "prelu", 0.0, weight))
+
+
+# (extensions: not part of MinkowskiEngine) the segmentation tail on plain feature matrices -- see minkowski/functional.py
+seg_cross_entropy = Fn.seg_cross_entropy
+slice_rows = Fn.slice_rows

@@ -185,6 +185,7 @@ class CoordinateManager:
         self.in2out = {}
         self.tables = {}
         self.field_inverse = None
+        self.field_members = None  # (order, seg) of TensorField.sparse(): the rows of every voxel, CSR
         self.field_unique_index = None
         self._boff = {}
         self._batch_size = None

@@ -63,7 +63,10 @@ class SparseTensor:
         if not (_is_one(self.tensor_stride) and field.coordinate_manager is self._manager):
             raise ValueError("slice: needs the tensor-stride-1 tensor and the field it came from")
         m = self._manager
-        F = self._F if m.levels[1].n == field.F.shape[0] else self._F[m.field_inverse.long()]
+        if m.levels[1].n == field.F.shape[0]:
+            F = self._F  # no duplicates: the rows are the field's rows, in order (no copy)
+        else:
+            F = Fn.slice_rows(self._F, m.field_inverse, *_field_members(m))  # (gather; backward: fixed-order segment sum)
         return TensorField(features=F, coordinates=field.C, _manager=m)
 
     def __iadd__(self, other):  # `out += residual`, reference resnet_block.py:66
@@ -77,6 +80,19 @@ class SparseTensor:
 
     def __repr__(self):
         return f"SparseTensor(F={tuple(self._F.shape)}, tensor_stride={self.tensor_stride})"
+
+
+def _field_members(m):
+    """(order, seg), int32: the field rows of every voxel in input-row order, CSR -- what sparse() averages over and the
+    backward of slice() sums over.  Built once per field and kept on the manager."""
+    if m.field_members is None:
+        n_unique = m.levels[1].n
+        inv = m.field_inverse.long()
+        order = torch.sort(inv, stable=True).indices.int()  # members of each voxel, input-row order
+        seg = torch.zeros(n_unique + 1, dtype=torch.int32, device=inv.device)
+        seg[1:] = torch.cumsum(torch.bincount(inv, minlength=n_unique), 0).int()
+        m.field_members = (order, seg)
+    return m.field_members
 
 
 def _is_one(ts):
@@ -167,9 +183,6 @@ class TensorField:
         if n_unique == F.shape[0]:
             Fs = F.float()  # no duplicates: unique rows are the input rows, in order
         else:
-            inv = m.field_inverse.long()
-            order = torch.sort(inv, stable=True).indices.int()  # members of each voxel, input-row order
-            seg = torch.zeros(n_unique + 1, dtype=torch.int32, device=F.device)
-            seg[1:] = torch.cumsum(torch.bincount(inv, minlength=n_unique), 0).int()
+            order, seg = _field_members(m)
             Fs = Fn.segment_mean(F, order, seg, n_unique)
         return SparseTensor(Fs, CoordinateMapKey(1), m)
