@@ -45,6 +45,12 @@ __device__ __forceinline__ bool row_key(const void *__restrict__ coords, int64_t
   int b, x, y, z;
   if (MODE == 0) {
     const float4 c = reinterpret_cast<const float4 *>(coords)[i];
+    // the float-to-int conversion saturates and turns NaN into 0: NaN, +-inf and anything far outside the key space is
+    // refused here, before it can come out of the conversion as a legal cell (the comparison is false for NaN)
+    if (!(fabsf(c.x) < 65536.f && fabsf(c.y) < 65536.f && fabsf(c.z) < 65536.f && fabsf(c.w) < 65536.f)) {
+      key = 0;
+      return false;
+    }
     b = (int)floorf(c.x), x = (int)floorf(c.y), y = (int)floorf(c.z), z = (int)floorf(c.w);
   } else {
     const int4 c = reinterpret_cast<const int4 *>(coords)[i];

@@ -387,7 +387,8 @@ class CoordinateManager:
         nu, status = meta.tolist()  # the one host sync of this level
         if status & _STATUS_RANGE:
             raise ValueError(
-                "coordinate outside the supported range (batch < 65535, |x|,|y|,|z| < 32768 after quantisation)"
+                "coordinate outside the supported range (0 <= batch <= 65534, -32768 <= x, y, z <= 32767 after "
+                "quantisation; NaN and infinite coordinates are refused)"
             )
         lev.n = nu
         lev.coords = coords[:nu]
@@ -451,7 +452,8 @@ class CoordinateManager:
         m, nlev = meta_host.tolist(), len(ts_list)
         if m[nlev] & _STATUS_RANGE:
             raise ValueError(
-                "coordinate outside the supported range (batch < 65535, |x|,|y|,|z| < 32768 after quantisation)"
+                "coordinate outside the supported range (0 <= batch <= 65534, -32768 <= x, y, z <= 32767 after "
+                "quantisation; NaN and infinite coordinates are refused)"
             )
         self._batch_size = m[nlev + 1]
         n_prev = n

@@ -74,6 +74,25 @@ def test_downsample_matches_restatement_bit_for_bit():
     assert (lab[doffs[6]:doffs[7]] == -100).any()  # (conflicting labels voted away)
 
 
+@pytest.mark.parametrize("bad", [float("nan"), float("inf"), -float("inf"), 1e20, 700.0])
+def test_downsample_refuses_coordinates_without_a_voxel(bad):
+    """A NaN, infinite or far too large coordinate has no voxel key: the status word carries MINK_STATUS_RANGE and the
+    host check raises VoxelRangeError (700 / 0.02 = 35000 cells is past 32767 too); the same scene without it passes."""
+    from nerf_downstream_amd.minkowski.utils import VoxelRangeError, points_status_check
+
+    rng = np.random.default_rng(1)
+    scenes = [synthetic_scene(rng, 500), synthetic_scene(rng, 300)]
+    b, _ = _batch(scenes, [0.02, 0.02])
+    status = _downsample(b)[-1]
+    assert status[1] == 0
+    points_status_check([status[0], 0, 0, status[1]])
+    b["coordinates"][650, 2] = bad
+    status = _downsample(b)[-1]
+    assert status[1] & 1
+    with pytest.raises(VoxelRangeError):
+        points_status_check([status[0], 0, 0, status[1]])
+
+
 def test_colour_ops_match_restatement():
     from nerf_downstream_amd.minkowski.utils import color_augment_batch
 
