@@ -420,6 +420,39 @@ int mink_bn_bwd(const float *dy, const float *x, const float *y, int64_t n, int3
                 const float *invstd, const float *gamma, int32_t relu, float *dx, float *dresidual,
                 float *dgamma, float *dbeta, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ instance norm / layer norm (csrc/norm.hip)
+ * MinkowskiInstanceNorm (modules/common.py:25-26): sample b owns rows [batch_offsets[b], batch_offsets[b+1]) of x[n][C]
+ * (int32 [B+1] on the device, batch_offsets[B] == n; empty samples are legal) and is normalised per channel by its own
+ * mean / biased variance:  y = [relu]( (x - mean_b) * invstd_b * gamma + beta [+ residual] ),  invstd = 1/sqrt(var + eps).
+ * Any C in [1, 4096] (16-byte accesses when C % 4 == 0 and every matrix is 16-byte aligned, dword accesses otherwise),
+ * 1 <= B <= 65535, n < 2^31.  mean[B][C], invstd[B][C] are outputs kept for backward (0, 0 for an empty sample).
+ * Three launches whatever B is, nothing is read back; sum x and sum x^2 are accumulated in double, no floating-point
+ * atomics, partials combined in a fixed order: bitwise reproducible.
+ *   workspace : >= mink_in_workspace_bytes(n, C, B), 8-byte aligned */
+int64_t mink_in_workspace_bytes(int64_t n, int32_t C, int32_t B);
+int mink_in_fwd(const float *x, int64_t n, int32_t C, const int32_t *batch_offsets, int32_t B, float eps, const float *gamma,
+                const float *beta, const float *residual, int32_t relu, float *y, float *mean, float *invstd, void *workspace,
+                int64_t workspace_bytes, void *stream);
+/* Backward of the op above (four launches).  y (the forward output) is only read when relu != 0.
+ * dx[n][C] per sample from that sample's sum g and sum g*xhat (g = dy masked by y > 0); dgamma[C], dbeta[C] summed over all
+ * rows of all samples (samples added in index order); dresidual (may be NULL) receives g. */
+int mink_in_bwd(const float *dy, const float *x, const float *y, int64_t n, int32_t C, const int32_t *batch_offsets, int32_t B,
+                const float *mean, const float *invstd, const float *gamma, int32_t relu, float *dx, float *dresidual,
+                float *dgamma, float *dbeta, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* MinkowskiLayerNorm == torch.nn.LayerNorm(C) on the feature matrix (modules/common.py:27-28): every row is normalised over
+ * its C channels, 1 <= C <= 512:  y[r] = [relu]( (x[r] - mean_r) * invstd_r * gamma + beta [+ residual[r]] ).
+ * One launch; the row stays in registers between the mean pass and the sum (x - mean)^2 pass (two-pass variance).
+ * mean[n], invstd[n] are outputs kept for backward. */
+int mink_ln_fwd(const float *x, int64_t n, int32_t C, float eps, const float *gamma, const float *beta, const float *residual,
+                int32_t relu, float *y, float *mean, float *invstd, void *stream);
+/* Backward (two launches): dx[n][C] per row, dresidual (may be NULL) the masked dy, dgamma[C] / dbeta[C] as per-workgroup
+ * column partials (double) added in a fixed order.  workspace: >= mink_ln_workspace_bytes(n, C), 8-byte aligned. */
+int64_t mink_ln_workspace_bytes(int64_t n, int32_t C);
+int mink_ln_bwd(const float *dy, const float *x, const float *y, int64_t n, int32_t C, const float *mean, const float *invstd,
+                const float *gamma, int32_t relu, float *dx, float *dresidual, float *dgamma, float *dbeta, void *workspace,
+                int64_t workspace_bytes, void *stream);
+
 /* Split form for MinkowskiSyncBatchNorm (train.py:106-107): per-channel sums stay on the device
  * as doubles so the host can all-reduce them (RCCL) between the passes.
  *   mink_bn_reduce mode 0: sums = [sum x | sum x^2];  mode 1: [sum g | sum g*xhat] (g masked by y>0

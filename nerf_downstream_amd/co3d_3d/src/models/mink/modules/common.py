@@ -11,10 +11,24 @@ def default_me():
 
 
 def get_norm(norm_type, n_channels, D=3, bn_momentum=0.1, ME=None):
+    """"BN" / "IN" / "LN" (reference common.py:22-32).  "PN" (PowerNorm, part of the reference's pruning study) is not
+    implemented."""
     ME = ME or _HIP_ME
-    if norm_type != "BN":
-        raise ValueError(f"Norm type: {norm_type} not supported (only BN is on the classification path)")
-    return ME.MinkowskiBatchNorm(n_channels, momentum=bn_momentum)
+    if norm_type == "BN":
+        return ME.MinkowskiBatchNorm(n_channels, momentum=bn_momentum)
+    if norm_type == "IN":
+        return ME.MinkowskiInstanceNorm(n_channels)
+    if norm_type == "LN":
+        return ME.MinkowskiLayerNorm(n_channels)
+    if norm_type == "PN":
+        raise ValueError("Norm type: PN (PowerNorm) is not implemented; use BN, IN or LN")
+    raise ValueError(f"Norm type: {norm_type} not supported (BN, IN and LN are; PN is not implemented)")
+
+
+def takes_conv_stats(norm):
+    """True for the norm layers that accept the column statistics a convolution computes in its epilogue
+    (`conv(x, bn_stats=True)`): batch norm only -- per-sample and per-row statistics are not column sums."""
+    return hasattr(norm, "bn")
 
 
 def get_nonlinearity(nonlinearity_type, ME=None):

@@ -7,12 +7,13 @@ names conv1/norm1/conv2/norm2[/conv3/norm3]/downsample are kept for state-dict c
                  conv1, conv3 are 1x1x1 (plain feature-matrix products), conv2 is 3x3x3 and carries the stride
 
 With a backend that advertises SUPPORTS_FUSED_NORM the three elementwise tails
-(norm1+relu, downsample norm, norm2+add+relu) each run as ONE fused HIP pass."""
+(norm1+relu, downsample norm, norm2+add+relu) each run as ONE fused HIP pass, whatever norm_type ("BN", "IN", "LN")
+the block was built with; only a batch norm takes its statistics from the convolution before it (bn_stats=)."""
 import os
 
 import torch.nn as nn
 
-from .common import conv, default_me, get_nonlinearity, get_norm
+from .common import conv, default_me, get_nonlinearity, get_norm, takes_conv_stats
 
 
 class BasicBlock(nn.Module):
@@ -59,7 +60,7 @@ class BasicBlock(nn.Module):
         """downsample(x) = norm(conv(x)) (reference resnet.py:120-128); on the fused backend the convolution hands the
         column statistics of its output to the norm, as conv1 / conv2 do (and as the native trunk sequences it)."""
         ds = self.downsample
-        if self._fused and self.training and len(ds) == 2:
+        if self._fused and self.training and len(ds) == 2 and takes_conv_stats(ds[1]):
             return ds[1](ds[0](x, bn_stats=True))
         return ds(x)
 
@@ -73,15 +74,16 @@ class BasicBlock(nn.Module):
     def forward(self, x):
         if self._may_fork(x):
             shortcut, join = self._forked_shortcut(x)
-            st = self.training  # the convolutions hand their output's column statistics to the norm that follows
-            h = self.conv2(self.norm1(self.conv1(x, bn_stats=st), relu=True), bn_stats=st)
+            st = self.training  # the convolutions hand their output's column statistics to a batch norm that follows
+            h = self.conv2(self.norm1(self.conv1(x, bn_stats=st and takes_conv_stats(self.norm1)), relu=True),
+                           bn_stats=st and takes_conv_stats(self.norm2))
             join()
             return self.norm2(h, relu=True, residual=shortcut)
         shortcut = x if self.downsample is None else self._shortcut(x)
         if self._fused:
             st = self.training
-            h = self.norm1(self.conv1(x, bn_stats=st), relu=True)
-            return self.norm2(self.conv2(h, bn_stats=st), relu=True, residual=shortcut)
+            h = self.norm1(self.conv1(x, bn_stats=st and takes_conv_stats(self.norm1)), relu=True)
+            return self.norm2(self.conv2(h, bn_stats=st and takes_conv_stats(self.norm2)), relu=True, residual=shortcut)
         h = self.nonlinearity(self.norm1(self.conv1(x)))
         h = self.norm2(self.conv2(h))
         h += shortcut
@@ -120,7 +122,7 @@ class Bottleneck(BasicBlock):
         if self._fused:
             st = self.training
             h = self.norm1(self.conv1(x), relu=True)
-            h = self.norm2(self.conv2(h, bn_stats=st), relu=True)
+            h = self.norm2(self.conv2(h, bn_stats=st and takes_conv_stats(self.norm2)), relu=True)
             h = self.conv3(h)
             if join is not None:
                 join()

@@ -19,7 +19,7 @@ import torch.nn as nn
 from nerf_downstream_amd import gin_lite as gin
 
 from .base_model import MinkowskiBaseModel
-from .modules.common import conv, conv_tr, get_nonlinearity, get_norm
+from .modules.common import conv, conv_tr, get_nonlinearity, get_norm, takes_conv_stats
 from .modules.resnet_block import BasicBlock, Bottleneck
 
 
@@ -35,7 +35,7 @@ class _Unit(nn.Sequential):
             return super().forward(x)
         mods = list(self)
         for j in range(0, len(mods), 3):
-            x = mods[j + 1](mods[j](x, bn_stats=self.training), relu=True)
+            x = mods[j + 1](mods[j](x, bn_stats=self.training and takes_conv_stats(mods[j + 1])), relu=True)
         return x
 
 
@@ -97,8 +97,9 @@ class Res16UNet(MinkowskiBaseModel):
         self.final = conv(P[7] * exp, out_channel, kernel_size=1, stride=1, bias=True, D=D, ME=ME)
         if self.INSSEG:
             raise NotImplementedError("the instance-segmentation offset head is out of scope")
-        for m in self.modules():  # reference weight_initialization (res16unet.py:384-389)
-            if isinstance(m, nn.BatchNorm1d):
+        for m in self.modules():  # reference weight_initialization (res16unet.py:384-389), extended to the affine
+            # parameters of NORM_TYPE "LN" (nn.LayerNorm) and "IN" (weight / bias of shape (1, C))
+            if isinstance(m, (nn.BatchNorm1d, nn.LayerNorm, ME.MinkowskiInstanceNorm)):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
 

@@ -70,7 +70,7 @@ class ResNetBase(MinkowskiBaseModel):
 
     def weight_initialization(self):
         for m in self.modules():
-            if isinstance(m, nn.BatchNorm1d):
+            if isinstance(m, (nn.BatchNorm1d, nn.LayerNorm, self._ME.MinkowskiInstanceNorm)):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
 
@@ -80,6 +80,8 @@ class ResNetBase(MinkowskiBaseModel):
         if stride != 1 or self.inplanes != out_planes:
             shortcut = nn.Sequential(
                 conv(self.inplanes, out_planes, kernel_size=1, stride=stride, bias=False, D=self.D, ME=ME),
+                # ("BN" whatever NORM_TYPE is: the reference's _make_layer defaults norm_type="BN" and no caller passes another,
+                #  resnet.py:107-135 -- NORM_TYPE selects the stem's norm, bn1, only; the blocks keep their default too)
                 get_norm("BN", out_planes, D=self.D, bn_momentum=0.1, ME=ME),
             )
         seq = [self.BLOCK(self.inplanes, planes, stride=stride, downsample=shortcut, D=self.D, ME=ME)]
@@ -108,7 +110,8 @@ class ResNetBase(MinkowskiBaseModel):
                 out = self._ME.SparseTensor(feats, trunk.out_key_of(self._trunk_plan), xs.coordinate_manager)
                 return self._head(out)
             x = _Presparsed(xs)
-        if self._fused:  # bn1 -> relu -> pool in one pass over the finest-level activation; its
+        if self._fused:  # bn1 -> relu -> pool in one pass over the finest-level activation (NORM_TYPE "BN"; with "IN" /
+            # "LN" the pooling layer runs conv1, bn1 with its fused ReLU and the pooling as three autograd nodes); its
             # statistics come out of the stem convolution's epilogue (no extra pass over 825 k x 64)
             # -- and, in training, conv1 + bn1 + relu + pool are one autograd node (the input needs no
             # gradient) whose backward keeps the gradient of the convolution output in registers

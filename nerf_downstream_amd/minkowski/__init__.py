@@ -15,6 +15,7 @@ from .modules import (  # noqa: F401
     MinkowskiGELU,
     MinkowskiGlobalAvgPooling,
     MinkowskiInstanceNorm,
+    MinkowskiLayerNorm,
     MinkowskiLeakyReLU,
     MinkowskiLinear,
     MinkowskiNetwork,
@@ -42,5 +43,5 @@ class SparseTensorQuantizationMode(enum.Enum):
 
 
 BACKEND = "hip-gfx950"
-SUPPORTS_FUSED_NORM = True  # MinkowskiBatchNorm.forward(x, relu=, residual=)
+SUPPORTS_FUSED_NORM = True  # Minkowski{Batch,Instance,Layer}Norm.forward(x, relu=, residual=)
 SUPPORTS_PREPARE_AHEAD = True  # TensorField.prepare_ahead(plan) + CoordinateManager.trace

@@ -763,6 +763,111 @@ class BatchNormFunction(torch.autograd.Function):
         return gx, dgamma, dbeta, None, None, None, None, None, gres, None, None
 
 
+class InstanceNormFunction(torch.autograd.Function):
+    """Per-sample, per-channel normalisation of F (ME.MinkowskiInstanceNorm) with the residual add and ReLU of
+    BatchNormFunction: sample b owns rows [offsets[b], offsets[b+1]) -- `offsets` is the manager's int32 [B+1] device
+    tensor and is never read by the host.  Three launches forward, four backward, whatever B is (csrc/norm.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, offsets, eps, residual, relu):
+        L = lib()
+        x = _f32c(x)
+        n, C = x.shape
+        dev = x.device
+        assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() >= 2, \
+            "batch offsets: a contiguous int32 [B+1] device tensor"
+        B = offsets.numel() - 1
+        gamma, beta = _f32c(gamma).reshape(-1), _f32c(beta).reshape(-1)
+        if residual is not None:
+            residual = _f32c(residual)
+        y = torch.empty_like(x)
+        mean = torch.empty(B, C, dtype=torch.float32, device=dev)
+        invstd = torch.empty(B, C, dtype=torch.float32, device=dev)
+        ws = _scratch(L.mink_in_workspace_bytes(n, C, B), dev, "in")
+        check(
+            L.mink_in_fwd(
+                x.data_ptr(), n, C, offsets.data_ptr(), B, eps, gamma.data_ptr(), beta.data_ptr(), _ptr(residual), int(relu),
+                y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
+            )
+        )
+        ctx.save_for_backward(x, y if relu else None, mean, invstd, gamma)
+        # (not a saved tensor: the manager carves its index tensors out of one arena, so a later carve-out next to the offsets
+        #  bumps the version counter they share without touching them)
+        ctx.offsets = offsets
+        ctx.relu, ctx.has_res = relu, residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        L = lib()
+        x, y, mean, invstd, gamma = ctx.saved_tensors
+        offsets = ctx.offsets
+        gy = _f32c(gy)
+        n, C = x.shape
+        dev = x.device
+        B = offsets.numel() - 1
+        gx = torch.empty_like(x)
+        gres = torch.empty_like(x) if ctx.has_res else None
+        dgamma = torch.empty(C, dtype=torch.float32, device=dev)
+        dbeta = torch.empty(C, dtype=torch.float32, device=dev)
+        ws = _scratch(L.mink_in_workspace_bytes(n, C, B), dev, "in")
+        check(
+            L.mink_in_bwd(
+                gy.data_ptr(), x.data_ptr(), _ptr(y), n, C, offsets.data_ptr(), B, mean.data_ptr(), invstd.data_ptr(),
+                gamma.data_ptr(), int(ctx.relu), gx.data_ptr(), _ptr(gres), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(),
+                ws.numel(), _stream(),
+            )
+        )
+        return gx, dgamma, dbeta, None, None, gres, None
+
+
+class LayerNormFunction(torch.autograd.Function):
+    """torch.nn.LayerNorm(C) over the channels of every row of F (ME.MinkowskiLayerNorm), 1 <= C <= 512, with the residual
+    add and ReLU of BatchNormFunction: one launch forward, two backward (csrc/norm.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, residual, relu):
+        L = lib()
+        x = _f32c(x)
+        n, C = x.shape
+        dev = x.device
+        gamma, beta = _f32c(gamma).reshape(-1), _f32c(beta).reshape(-1)
+        if residual is not None:
+            residual = _f32c(residual)
+        y = torch.empty_like(x)
+        mean = torch.empty(n, dtype=torch.float32, device=dev)
+        invstd = torch.empty(n, dtype=torch.float32, device=dev)
+        check(
+            L.mink_ln_fwd(
+                x.data_ptr(), n, C, eps, gamma.data_ptr(), beta.data_ptr(), _ptr(residual), int(relu), y.data_ptr(),
+                mean.data_ptr(), invstd.data_ptr(), _stream(),
+            )
+        )
+        ctx.save_for_backward(x, y if relu else None, mean, invstd, gamma)
+        ctx.relu, ctx.has_res = relu, residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        L = lib()
+        x, y, mean, invstd, gamma = ctx.saved_tensors
+        gy = _f32c(gy)
+        n, C = x.shape
+        dev = x.device
+        gx = torch.empty_like(x)
+        gres = torch.empty_like(x) if ctx.has_res else None
+        dgamma = torch.empty(C, dtype=torch.float32, device=dev)
+        dbeta = torch.empty(C, dtype=torch.float32, device=dev)
+        ws = _scratch(L.mink_ln_workspace_bytes(n, C), dev, "ln")
+        check(
+            L.mink_ln_bwd(
+                gy.data_ptr(), x.data_ptr(), _ptr(y), n, C, mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), int(ctx.relu),
+                gx.data_ptr(), _ptr(gres), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
+            )
+        )
+        return gx, dgamma, dbeta, None, gres, None
+
+
 class SyncBatchNormFunction(torch.autograd.Function):
     """BatchNorm with statistics over all ranks (ME.MinkowskiSyncBatchNorm, reference
     train.py:106-107): per-channel (sum x, sum x^2, rows) are all-reduced between the reduction and

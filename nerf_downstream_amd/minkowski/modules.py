@@ -287,11 +287,14 @@ class MinkowskiPReLU(nn.Module):
 class MinkowskiInstanceNorm(nn.Module):
     """ME.MinkowskiInstanceNorm(num_features) (reference modules/common.py:25-26): every batch sample's voxels are
     normalised per channel by that sample's own mean / biased variance, then scaled and shifted by `weight` (ones) /
-    `bias` (zeros).  The rows of one sample are contiguous, so each sample is one batch-norm pass (training-mode
-    statistics, no running buffers) over its row range.
+    `bias` (zeros).  The rows of one sample are contiguous: the segmented kernels of csrc/norm.hip read the manager's
+    device-resident batch offsets, so the layer is three launches forward and four backward whatever the batch size, with
+    no host synchronisation.  No running buffers: eval mode behaves as training mode.
     eps: ME's instance norm divides by sqrt(var + 1e-8) [ME-recall of MinkowskiInstanceNormFunction; parity unpinned: ME
     is absent and the reference holds no fixture for this layer -- it is only named by the layer factory, not used by a
-    shipped model]; the value is an attribute so a caller that knows better can set it."""
+    shipped model]; the value is an attribute so a caller that knows better can set it.
+
+    Extension shared with MinkowskiBatchNorm: `forward(x, relu=True, residual=r)` computes relu(norm(x) + r) in one pass."""
 
     def __init__(self, num_features):
         super().__init__()
@@ -299,13 +302,51 @@ class MinkowskiInstanceNorm(nn.Module):
         self.weight = nn.Parameter(torch.ones(1, num_features))
         self.bias = nn.Parameter(torch.zeros(1, num_features))
 
-    def forward(self, input):
+    def forward(self, input, relu=False, residual=None):
         m = input.coordinate_manager
-        boff = m.batch_offsets(input.coordinate_map_key).tolist()
-        F, g, b = input.F, self.weight.reshape(-1), self.bias.reshape(-1)
-        parts = [Fn.BatchNormFunction.apply(F[s:e], g, b, None, None, True, 0.0, self.eps, None, False, None)
-                 for s, e in zip(boff[:-1], boff[1:]) if e > s]
-        return SparseTensor(torch.cat(parts, 0), input.coordinate_map_key, m)
+        if residual is not None:
+            input._check(residual)
+        out = Fn.InstanceNormFunction.apply(input.F, self.weight.reshape(-1), self.bias.reshape(-1),
+                                            m.batch_offsets(input.coordinate_map_key), self.eps,
+                                            residual.F if residual is not None else None, bool(relu))
+        return SparseTensor(out, input.coordinate_map_key, m)
+
+    def extra_repr(self):
+        return f"{self.num_features}, eps={self.eps}"
+
+
+class MinkowskiLayerNorm(nn.Module):
+    """ME.MinkowskiLayerNorm(num_features) (reference modules/common.py:27-28): an `nn.LayerNorm` (attribute `ln`, so
+    state-dict keys are `*.ln.weight` / `*.ln.bias`) over the channels of every row of F -- one HIP launch forward, two
+    backward (csrc/norm.hip), 1 <= num_features <= 512.  Takes a SparseTensor or a TensorField and returns the same kind.
+    No running buffers: eval mode behaves as training mode.
+
+    Extension shared with MinkowskiBatchNorm: `forward(x, relu=True, residual=r)` computes relu(norm(x) + r) in one pass."""
+
+    def __init__(self, num_features, eps=1e-5, affine=True):
+        super().__init__()
+        if not 1 <= int(num_features) <= 512:
+            raise ValueError(f"MinkowskiLayerNorm({num_features}): the row-wise kernels hold a row in registers and take at most 512 channels")
+        self.ln = nn.LayerNorm(num_features, eps=eps, elementwise_affine=affine)
+
+    def forward(self, input, relu=False, residual=None):
+        from .tensor import TensorField
+
+        ln = self.ln
+        F = input.F
+        if residual is not None:
+            if isinstance(input, TensorField):
+                if residual.coordinate_manager is not input.coordinate_manager or residual.F.shape != F.shape:
+                    raise ValueError("TensorFields must share the coordinate manager and the rows")
+            else:
+                input._check(residual)
+        C = ln.normalized_shape[0]
+        gamma = ln.weight if ln.weight is not None else torch.ones(C, device=F.device)
+        beta = ln.bias if ln.bias is not None else torch.zeros(C, device=F.device)
+        out = Fn.LayerNormFunction.apply(F, gamma, beta, ln.eps, residual.F if residual is not None else None, bool(relu))
+        if isinstance(input, TensorField):
+            return TensorField(features=out, coordinates=input.C, _manager=input.coordinate_manager)
+        return SparseTensor(out, input.coordinate_map_key, input.coordinate_manager)
 
 
 class MinkowskiLinear(nn.Module):
@@ -341,7 +382,8 @@ class MinkowskiSumPooling(nn.Module):
 
     def forward(self, input, norm=None, conv=None):
         """`norm` (extension): a MinkowskiBatchNorm to apply, followed by ReLU, to `input` on the
-        fly -- pool(relu(norm(input))) in one pass without materialising the normalised tensor.
+        fly -- pool(relu(norm(input))) in one pass without materialising the normalised tensor (any
+        other norm layer -- instance norm, layer norm, SyncBN -- runs as norm(input, relu=True), then the pooling).
         `conv` (extension, with `norm`): a MinkowskiConvolution to apply first --
         pool(relu(norm(conv(input)))), the stem of the reference ResNets, as one autograd node
         whose backward never materialises the gradient of the convolution output either."""
@@ -349,12 +391,12 @@ class MinkowskiSumPooling(nn.Module):
             fused = self._conv_norm_pool(input, norm, conv)
             if fused is not None:
                 return fused
-            input = conv(input, bn_stats=norm is not None and norm.bn.training)
+            input = conv(input, bn_stats=isinstance(norm, MinkowskiBatchNorm) and norm.bn.training)
         m, in_key = input.coordinate_manager, input.coordinate_map_key
         out_key = m.stride(in_key, self.stride)
         nbr, _ = m.kernel_table(in_key, out_key, self.kernel_size, 1)
         i2o = m.stride_map(in_key, out_key)
-        fusable = norm is not None and norm.bn.affine and type(norm) is MinkowskiBatchNorm
+        fusable = type(norm) is MinkowskiBatchNorm and norm.bn.affine
         if fusable and (norm.bn.training or not torch.is_grad_enabled()):
             bn = norm.bn
             training = bn.training or not bn.track_running_stats
