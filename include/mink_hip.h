@@ -480,13 +480,55 @@ int mink_bn_relu_pool_bwd(const float *dy_pool, const float *x, int64_t n, int32
                           void *workspace, int64_t workspace_bytes, void *stream);
 
 /* Max pooling over a neighbour table whose windows may overlap -- the 3x3 stride-2 pooling of the dense 2-D
- * comparison network (torchvision ResNet, reference co3d_2d/src/model/models.py:18-23), also ME.MinkowskiMaxPooling.
+ * comparison network (torchvision ResNet, reference co3d_2d/src/model/models.py:18-23), which is its only caller: C % 4 == 0,
+ * contiguous rows, and a window with no present entry gets -inf.  ME.MinkowskiMaxPooling on sparse tensors goes through
+ * mink_pool_local_max_fwd / _bwd below (any C, row pitch, empty windows -> 0).
  * arg[n_out][C] receives the input row of each maximum; backward gathers through the transposed table nbr_t[n_in][K]
  * (the windows containing a row), so there are no atomics. */
 int mink_pool_max_fwd(const float *x, int32_t C, const int32_t *nbr, int64_t n_out, int32_t K, float *y, int32_t *arg,
                       void *stream);
 int mink_pool_max_bwd(const float *dy, const int32_t *arg, int32_t C, const int32_t *nbr_t, int64_t n_in, int32_t K,
                       float *dx, void *stream);
+
+/* ------------------------------------------------------------------ sparse pooling family (csrc/pool.hip)
+ * Conventions of mink_pool_sum_* / mink_in_* / mink_ln_*: fp32 features x[n][C] with a row pitch ldx >= C (outputs and
+ * gradients are contiguous, pitch C), any 1 <= C <= 4096 -- 16-byte accesses when C % 4 == 0, ldx % 4 == 0 and the pointers are
+ * 16-byte aligned, dword accesses otherwise --, no host read-back, no floating-point atomics, sums in a fixed order (two runs
+ * are bitwise equal), empty table entries are -1.
+ *
+ * Local pooling over a neighbour table nbr[n_out][K] whose windows may overlap (1 <= K <= 81), k ascending:
+ *   mode 0 (ME.MinkowskiSumPooling beyond kernel_size == stride): y[o] = sum over the present k of x[nbr[o][k]]
+ *   mode 1 (ME.MinkowskiAvgPooling):                              y[o] = that sum / cnt[o]
+ * cnt[o] (int32 [n_out]; required for mode 1, optional for mode 0) = the number of present entries of row o: the average
+ * divides by the number of non-empty inputs, NOT by the kernel volume [ME-recall of MinkowskiAvgPooling; parity unpinned: ME
+ * is absent and the reference holds no fixture for this layer].  A row with no present entry gets 0 and cnt 0.
+ * Backward gathers through the transposed table nbr_t[n_in][K] (nbr_t[i][k] = o iff nbr[o][k] = i):
+ *   dx[i] = sum over the present k of dy[nbr_t[i][k]] (/ cnt[nbr_t[i][k]] for mode 1). */
+int mink_pool_local_fwd(const float *x, int32_t ldx, int32_t C, const int32_t *nbr, int64_t n_out, int32_t K, int32_t mode,
+                        float *y, int32_t *cnt, void *stream);
+int mink_pool_local_bwd(const float *dy, int32_t C, const int32_t *nbr_t, int64_t n_in, int32_t K, int32_t mode,
+                        const int32_t *cnt, float *dx, void *stream);
+/* ME.MinkowskiMaxPooling: y[o][c] = max over the present k of x[nbr[o][k]][c], arg[o][c] = that input row; the lowest k wins a
+ * tie (the first present entry in kernel-offset order), a NaN never replaces a number.  A row with no present entry gets 0
+ * and arg -1.  Backward: dx[i][c] = sum over the present k of (arg[o][c] == i ? dy[o][c] : 0), o = nbr_t[i][k]. */
+int mink_pool_local_max_fwd(const float *x, int32_t ldx, int32_t C, const int32_t *nbr, int64_t n_out, int32_t K, float *y,
+                            int32_t *arg, void *stream);
+int mink_pool_local_max_bwd(const float *dy, const int32_t *arg, int32_t C, const int32_t *nbr_t, int64_t n_in, int32_t K,
+                            float *dx, void *stream);
+/* Global pooling, segmented over batch_offsets (int32 [B+1] on the device, 1 <= B <= 65535; sample b owns rows
+ * [batch_offsets[b], batch_offsets[b+1])).  Launch shape of mink_in_fwd: per-workgroup partials in `workspace`
+ * (mink_global_pool_workspace_bytes, 8-byte aligned), combined in a fixed order; two launches forward, one backward for any B.
+ *   ME.MinkowskiGlobalMaxPooling: y[b][c] = max over the sample's rows, arg[b][c] = the LOWEST row attaining it (row index into
+ *     x); an empty sample gives 0 and arg -1.  Backward: dx[i][c] = arg[b][c] == i ? dy[b][c] : 0, one pass over the rows of dx.
+ *   ME.MinkowskiGlobalSumPooling: y[b] = sum of the sample's rows, accumulated in double and rounded once; dx[i] = dy[b]. */
+int64_t mink_global_pool_workspace_bytes(int64_t n, int32_t C, int32_t B);
+int mink_global_max_fwd(const float *x, int64_t n, int32_t ldx, int32_t C, const int32_t *batch_offsets, int32_t B, float *y,
+                        int32_t *arg, void *workspace, int64_t workspace_bytes, void *stream);
+int mink_global_max_bwd(const float *dy, const int32_t *arg, int64_t n, int32_t C, const int32_t *batch_offsets, int32_t B,
+                        float *dx, void *stream);
+int mink_global_sum_fwd(const float *x, int64_t n, int32_t ldx, int32_t C, const int32_t *batch_offsets, int32_t B, float *y,
+                        void *workspace, int64_t workspace_bytes, void *stream);
+int mink_global_sum_bwd(const float *dy, int64_t n, int32_t C, const int32_t *batch_offsets, int32_t B, float *dx, void *stream);
 
 /* Elementwise: mode 0: y = max(x,0); mode 1: dx = (y>0) ? dy : 0 (a=dy,b=y);
  * mode 2: y = a + b. */

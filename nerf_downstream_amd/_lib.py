@@ -155,6 +155,15 @@ SIGNATURES = {
     "mink_pool_sum_bwd": (ctypes.c_int, [_p, _i32, _p, _i64, _p, _p]),
     "mink_pool_max_fwd": (ctypes.c_int, [_p, _i32, _p, _i64, _i32, _p, _p, _p]),
     "mink_pool_max_bwd": (ctypes.c_int, [_p, _p, _i32, _p, _i64, _i32, _p, _p]),
+    "mink_pool_local_fwd": (ctypes.c_int, [_p, _i32, _i32, _p, _i64, _i32, _i32, _p, _p, _p]),
+    "mink_pool_local_bwd": (ctypes.c_int, [_p, _i32, _p, _i64, _i32, _i32, _p, _p, _p]),
+    "mink_pool_local_max_fwd": (ctypes.c_int, [_p, _i32, _i32, _p, _i64, _i32, _p, _p, _p]),
+    "mink_pool_local_max_bwd": (ctypes.c_int, [_p, _p, _i32, _p, _i64, _i32, _p, _p]),
+    "mink_global_pool_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "mink_global_max_fwd": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _p, _p, _i64, _p]),
+    "mink_global_max_bwd": (ctypes.c_int, [_p, _p, _i64, _i32, _p, _i32, _p, _p]),
+    "mink_global_sum_fwd": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _p, _i64, _p]),
+    "mink_global_sum_bwd": (ctypes.c_int, [_p, _i64, _i32, _p, _i32, _p, _p]),
     "mink_global_avg_fwd": (ctypes.c_int, [_p, _i32, _p, _i32, _p, _p]),
     "mink_global_avg_bwd": (ctypes.c_int, [_p, _i32, _p, _i32, _i64, _p, _p]),
     "mink_head_forward": (ctypes.c_int, [_p, _p, _i32, _i32, _p, _p, _i32, _p, _p, _p]),

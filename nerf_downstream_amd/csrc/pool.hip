@@ -1,0 +1,537 @@
+// The sparse pooling family on gfx950: local average / sum / max pooling over a neighbour table whose windows may overlap
+// (ME.MinkowskiAvgPooling, MinkowskiSumPooling beyond kernel_size == stride, MinkowskiMaxPooling) and the segmented global
+// max / sum pooling over the batch offsets (ME.MinkowskiGlobalMaxPooling, MinkowskiGlobalSumPooling).  The non-overlapping
+// sum pooling of the ResNet stem, its fused forms and the global average stay in elementwise.hip, untouched.
+//
+// All of them are bandwidth-bound row passes over x[n][C] (row pitch ldx >= C): a thread owns one column group of one row,
+// 16 bytes wide when C % 4 == 0 and every pointer is 16-byte aligned (and ldx % 4 == 0), one dword otherwise (C = 1, 3, 70).
+//
+// Local pools.  nbr[n_out][K] holds the input row of output o at kernel offset k, or -1.  Forward walks k = 0 .. K-1 in
+// order and skips the empty entries; backward gathers through the transposed table nbr_t[n_in][K] (nbr_t[i][k] = o iff
+// nbr[o][k] = i, the windows that contain row i), again k ascending: one owner per element, no atomics, a fixed order.
+//   average: y[o] = (sum of the present rows) / cnt[o], cnt[o] = number of present entries -- NOT the kernel volume; one true
+//            fp32 division per element (dx[i] = sum of dy[o] / cnt[o], the same division per term)
+//   max    : the first present entry in offset order wins a tie (v > m only replaces); arg[o][c] = its input row.  A row
+//            with no present entry gets y = 0, arg = -1.  A NaN never replaces a number.
+//
+// Global pools.  Sample b owns rows [off[b], off[b+1]) (the manager's device-resident offsets; never read by the host).  The
+// launch shape is that of the instance norm (norm.hip): grid (G, B, channel slabs), every sample cut into the same number G
+// of row chunks chosen from n and B alone, one partial per workgroup, then one wave per (sample, channel) combines the G
+// partials -- lane l takes partials l, l + 64, ... in order, then a fixed butterfly.  Two launches forward, one backward,
+// whatever B is.  An empty sample finds an empty range: y = 0, arg = -1.
+//   max: the combine rule is a total order (larger value, then lower row), so arg[b][c] is the LOWEST row attaining the
+//        maximum however the rows were spread over threads.  Backward is one pass over the rows of dx that compares the row
+//        index with arg: dx[i][c] = arg[b][c] == i ? dy[b][c] : 0 -- no scatter.
+//   sum: accumulated in DOUBLE from the first add on and rounded to fp32 once; backward dx[i] = dy[b].
+// Determinism: rows -> threads -> partials -> results is a fixed assignment in a fixed order: two runs are bitwise equal.
+#include <algorithm>
+
+#include "common.h"
+
+namespace mink {
+namespace {
+
+constexpr int PB = 256;               // threads per workgroup
+constexpr int kPoolMaxBlocks = 2048;  // B * G stays near this
+
+template <int VEC>
+__device__ __forceinline__ void ldf(const float *__restrict__ p, float (&v)[VEC]) {
+  if constexpr (VEC == 4) {
+    const float4 t = *reinterpret_cast<const float4 *>(p);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+  } else {
+    v[0] = p[0];
+  }
+}
+template <int VEC>
+__device__ __forceinline__ void stf(float *__restrict__ p, const float (&v)[VEC]) {
+  if constexpr (VEC == 4)
+    *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  else
+    p[0] = v[0];
+}
+template <int VEC>
+__device__ __forceinline__ void ldi(const int *__restrict__ p, int (&v)[VEC]) {
+  if constexpr (VEC == 4) {
+    const int4 t = *reinterpret_cast<const int4 *>(p);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+  } else {
+    v[0] = p[0];
+  }
+}
+template <int VEC>
+__device__ __forceinline__ void sti(int *__restrict__ p, const int (&v)[VEC]) {
+  if constexpr (VEC == 4)
+    *reinterpret_cast<int4 *>(p) = make_int4(v[0], v[1], v[2], v[3]);
+  else
+    p[0] = v[0];
+}
+
+// ------------------------------------------------------------------------------------------------ local pools
+enum { kSum = 0, kAvg = 1 };
+
+template <int VEC, int MODE>
+__global__ __launch_bounds__(PB) void pool_local_fwd_kernel(const float *__restrict__ x, int ldx, int C, const int *__restrict__ nbr,
+                                                            int64_t n_out, int K, float *__restrict__ y, int *__restrict__ cnt) {
+  const int ncg = C / VEC;
+  const int64_t total = n_out * ncg;
+  for (int64_t idx = (int64_t)blockIdx.x * PB + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * PB) {
+    const int64_t o = idx / ncg;
+    const int c = (int)(idx - o * ncg) * VEC;
+    const int *__restrict__ row = nbr + o * K;
+    float s[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) s[j] = 0.f;
+    int m = 0;
+    for (int k = 0; k < K; ++k) {
+      const int i = row[k];
+      if (i >= 0) {
+        float v[VEC];
+        ldf<VEC>(x + (int64_t)i * ldx + c, v);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) s[j] += v[j];
+        ++m;
+      }
+    }
+    if (MODE == kAvg && m > 0) {
+      const float d = (float)m;
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) s[j] = s[j] / d;
+    }
+    stf<VEC>(y + o * C + c, s);
+    if (cnt && c == 0) cnt[o] = m;
+  }
+}
+
+template <int VEC, int MODE>
+__global__ __launch_bounds__(PB) void pool_local_bwd_kernel(const float *__restrict__ dy, int C, const int *__restrict__ nbr_t,
+                                                            int64_t n_in, int K, const int *__restrict__ cnt,
+                                                            float *__restrict__ dx) {
+  const int ncg = C / VEC;
+  const int64_t total = n_in * ncg;
+  for (int64_t idx = (int64_t)blockIdx.x * PB + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * PB) {
+    const int64_t i = idx / ncg;
+    const int c = (int)(idx - i * ncg) * VEC;
+    const int *__restrict__ row = nbr_t + i * K;
+    float s[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) s[j] = 0.f;
+    for (int k = 0; k < K; ++k) {
+      const int o = row[k];
+      if (o >= 0) {
+        float g[VEC];
+        ldf<VEC>(dy + (int64_t)o * C + c, g);
+        if (MODE == kAvg) {
+          const float d = (float)cnt[o];  // (>= 1: window o contains row i)
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) g[j] = g[j] / d;
+        }
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) s[j] += g[j];
+      }
+    }
+    stf<VEC>(dx + i * C + c, s);
+  }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(PB) void pool_local_max_fwd_kernel(const float *__restrict__ x, int ldx, int C,
+                                                                const int *__restrict__ nbr, int64_t n_out, int K,
+                                                                float *__restrict__ y, int *__restrict__ arg) {
+  const int ncg = C / VEC;
+  const int64_t total = n_out * ncg;
+  for (int64_t idx = (int64_t)blockIdx.x * PB + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * PB) {
+    const int64_t o = idx / ncg;
+    const int c = (int)(idx - o * ncg) * VEC;
+    const int *__restrict__ row = nbr + o * K;
+    float m[VEC];
+    int a[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) m[j] = 0.f, a[j] = -1;
+    for (int k = 0; k < K; ++k) {
+      const int i = row[k];
+      if (i >= 0) {
+        float v[VEC];
+        ldf<VEC>(x + (int64_t)i * ldx + c, v);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j)
+          if (a[j] < 0 || v[j] > m[j]) m[j] = v[j], a[j] = i;  // (the lowest k wins a tie)
+      }
+    }
+    stf<VEC>(y + o * C + c, m);
+    sti<VEC>(arg + o * C + c, a);
+  }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(PB) void pool_local_max_bwd_kernel(const float *__restrict__ dy, const int *__restrict__ arg, int C,
+                                                                const int *__restrict__ nbr_t, int64_t n_in, int K,
+                                                                float *__restrict__ dx) {
+  const int ncg = C / VEC;
+  const int64_t total = n_in * ncg;
+  for (int64_t idx = (int64_t)blockIdx.x * PB + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * PB) {
+    const int64_t i = idx / ncg;
+    const int c = (int)(idx - i * ncg) * VEC;
+    const int *__restrict__ row = nbr_t + i * K;
+    float s[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) s[j] = 0.f;
+    for (int k = 0; k < K; ++k) {
+      const int o = row[k];
+      if (o >= 0) {
+        float g[VEC];
+        int a[VEC];
+        ldf<VEC>(dy + (int64_t)o * C + c, g);
+        ldi<VEC>(arg + (int64_t)o * C + c, a);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) s[j] += a[j] == (int)i ? g[j] : 0.f;
+      }
+    }
+    stf<VEC>(dx + i * C + c, s);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ global pools
+// rows [lo, hi) of sample b, clamped into [0, n] (offsets that do not describe x cannot send a load out of bounds)
+__device__ __forceinline__ void pool_sample_range(const int *__restrict__ off, int b, int64_t n, int64_t &lo, int64_t &hi) {
+  lo = off[b], hi = off[b + 1];
+  lo = lo < 0 ? 0 : (lo > n ? n : lo);
+  hi = hi < lo ? lo : (hi > n ? n : hi);
+}
+
+// the sample that owns `row`: the largest b in [0, B) with off[b] <= row
+__device__ __forceinline__ int pool_sample_of(const int *__restrict__ off, int B, int64_t row) {
+  int lo = 0, hi = B;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((int64_t)off[mid] <= row) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// (m, a) <- the better of (m, a) and (v, r): a present candidate (r >= 0) beats an absent one, then the larger value, then
+// the lower row.  Symmetric, so both sides of a butterfly exchange end with the same pair.
+__device__ __forceinline__ void max_take(float &m, int &a, float v, int r) {
+  if (r >= 0 && (a < 0 || v > m || (v == m && r < a))) m = v, a = r;
+}
+
+// Chunk g of sample b -> pval / parg [b][g][C].  A thread owns VEC channels (column group cg) and the rows rl, rl + rlanes,
+// ... of the chunk, ascending; tprb column groups per workgroup, blockIdx.z walks further slabs of tprb groups.
+template <int VEC>
+__global__ __launch_bounds__(PB) void gmax_partial_kernel(const float *__restrict__ x, int ldx, const int *__restrict__ off,
+                                                          int64_t n, int C, int tprb, float *__restrict__ pval,
+                                                          int *__restrict__ parg) {
+  extern __shared__ __align__(16) unsigned char s_raw[];  // [rlanes][W] float, then [rlanes][W] int
+  const int b = blockIdx.y, G = gridDim.x, g = blockIdx.x;
+  int64_t lo, hi;
+  pool_sample_range(off, b, n, lo, hi);
+  const int64_t len = hi - lo;
+  const int64_t r0 = lo + len * g / G, r1 = lo + len * (g + 1) / G;
+  const int ncg = C / VEC, rlanes = PB / tprb, W = tprb * VEC;
+  float *s_val = reinterpret_cast<float *>(s_raw);
+  int *s_arg = reinterpret_cast<int *>(s_raw) + rlanes * W;
+  const int cl = threadIdx.x % tprb, rl = threadIdx.x / tprb;
+  const int cg = blockIdx.z * tprb + cl;
+  float m[VEC];
+  int a[VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) m[k] = 0.f, a[k] = -1;
+  if (rl < rlanes && cg < ncg) {
+    const int c = cg * VEC;
+#pragma unroll 4
+    for (int64_t row = r0 + rl; row < r1; row += rlanes) {
+      float v[VEC];
+      ldf<VEC>(x + row * ldx + c, v);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k)
+        if (a[k] < 0 || v[k] > m[k]) m[k] = v[k], a[k] = (int)row;
+    }
+  }
+  if (rl < rlanes) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) s_val[rl * W + cl * VEC + k] = m[k], s_arg[rl * W + cl * VEC + k] = a[k];
+  }
+  __syncthreads();
+  const int64_t base = ((int64_t)b * G + g) * C;
+  for (int e = threadIdx.x; e < W; e += PB) {
+    const int c = blockIdx.z * W + e;
+    if (c >= C) continue;
+    float bm = s_val[e];
+    int ba = s_arg[e];
+    for (int r = 1; r < rlanes; ++r) max_take(bm, ba, s_val[r * W + e], s_arg[r * W + e]);
+    pval[base + c] = bm;
+    parg[base + c] = ba;
+  }
+}
+
+// grid (ceil(C / 4), B): one wave per (sample, channel) combines the G chunk partials
+__global__ __launch_bounds__(PB) void gmax_finalize_kernel(const float *__restrict__ pval, const int *__restrict__ parg, int G, int C,
+                                                           float *__restrict__ y, int *__restrict__ arg) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
+  if (c >= C) return;  // whole wave
+  const int lane = threadIdx.x & 63;
+  const int64_t base = (int64_t)b * G * C + c;
+  float m = 0.f;
+  int a = -1;
+  for (int j = lane; j < G; j += 64) max_take(m, a, pval[base + (int64_t)j * C], parg[base + (int64_t)j * C]);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float ov = __shfl_xor(m, o, 64);
+    const int oa = __shfl_xor(a, o, 64);
+    max_take(m, a, ov, oa);
+  }
+  if (lane == 0) {
+    y[(int64_t)b * C + c] = a < 0 ? 0.f : m;
+    arg[(int64_t)b * C + c] = a;
+  }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(PB) void gsum_partial_kernel(const float *__restrict__ x, int ldx, const int *__restrict__ off,
+                                                          int64_t n, int C, int tprb, double *__restrict__ partial) {
+  extern __shared__ __align__(16) unsigned char s_raw[];  // [rlanes][W] double
+  double *s_red = reinterpret_cast<double *>(s_raw);
+  const int b = blockIdx.y, G = gridDim.x, g = blockIdx.x;
+  int64_t lo, hi;
+  pool_sample_range(off, b, n, lo, hi);
+  const int64_t len = hi - lo;
+  const int64_t r0 = lo + len * g / G, r1 = lo + len * (g + 1) / G;
+  const int ncg = C / VEC, rlanes = PB / tprb, W = tprb * VEC;
+  const int cl = threadIdx.x % tprb, rl = threadIdx.x / tprb;
+  const int cg = blockIdx.z * tprb + cl;
+  double s[VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) s[k] = 0.0;
+  if (rl < rlanes && cg < ncg) {
+    const int c = cg * VEC;
+#pragma unroll 4
+    for (int64_t row = r0 + rl; row < r1; row += rlanes) {
+      float v[VEC];
+      ldf<VEC>(x + row * ldx + c, v);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) s[k] += (double)v[k];
+    }
+  }
+  if (rl < rlanes) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) s_red[rl * W + cl * VEC + k] = s[k];
+  }
+  __syncthreads();
+  const int64_t base = ((int64_t)b * G + g) * C;
+  for (int e = threadIdx.x; e < W; e += PB) {
+    const int c = blockIdx.z * W + e;
+    if (c >= C) continue;
+    double t = 0.0;
+    for (int r = 0; r < rlanes; ++r) t += s_red[r * W + e];
+    partial[base + c] = t;
+  }
+}
+
+__global__ __launch_bounds__(PB) void gsum_finalize_kernel(const double *__restrict__ partial, int G, int C, float *__restrict__ y) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
+  if (c >= C) return;  // whole wave
+  const int lane = threadIdx.x & 63;
+  const int64_t base = (int64_t)b * G * C + c;
+  double s = 0.0;
+  for (int j = lane; j < G; j += 64) s += partial[base + (int64_t)j * C];
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane == 0) y[(int64_t)b * C + c] = (float)s;  // the one rounding
+}
+
+// MAX: dx[i][c] = arg[b][c] == i ? dy[b][c] : 0;  !MAX: dx[i][c] = dy[b][c].  Flat over the n * C / VEC column groups.
+template <int VEC, bool MAX>
+__global__ __launch_bounds__(PB) void gpool_bwd_kernel(const float *__restrict__ dy, const int *__restrict__ arg, int64_t n, int C,
+                                                       const int *__restrict__ off, int B, float *__restrict__ dx) {
+  const int ncg = C / VEC;
+  const int64_t total = n * ncg;
+  int b = 0;
+  int64_t lo = 0, hi = 0;  // the cached sample's rows: empty until the first search
+  for (int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x; i < total; i += (int64_t)gridDim.x * PB) {
+    const int64_t row = i / ncg;
+    const int c = (int)(i - row * ncg) * VEC;
+    if (row < lo || row >= hi) {
+      b = pool_sample_of(off, B, row);
+      lo = off[b], hi = off[b + 1];
+    }
+    float g[VEC];
+    ldf<VEC>(dy + (int64_t)b * C + c, g);
+    if (MAX) {
+      int a[VEC];
+      ldi<VEC>(arg + (int64_t)b * C + c, a);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) g[k] = a[k] == (int)row ? g[k] : 0.f;
+    }
+    stf<VEC>(dx + i * VEC, g);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+inline int pool_chunks(int64_t n, int B) {
+  const int64_t cap = std::max<int64_t>(1, kPoolMaxBlocks / std::max(B, 1));
+  return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256), cap));
+}
+inline unsigned pool_grid(int64_t work) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(work, PB), 1 << 16)); }
+inline bool a16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+}  // namespace mink
+
+using namespace mink;
+
+#define POOL_SHAPE(name, rows, C)                                                                                      \
+  MINK_REQUIRE((rows) >= 0 && (rows) <= 0x7fffffffLL && (C) >= 1 && (C) <= 4096, name ": bad shape (rows=%lld, C=%d; 1 <= C <= 4096)", \
+               (long long)(rows), (int)(C))
+
+extern "C" {
+
+int mink_pool_local_fwd(const float *x, int32_t ldx, int32_t C, const int32_t *nbr, int64_t n_out, int32_t K, int32_t mode,
+                        float *y, int32_t *cnt, void *stream) {
+  POOL_SHAPE("pool_local_fwd", n_out, C);
+  MINK_REQUIRE(K >= 1 && K <= 81 && ldx >= C && (mode == kSum || mode == kAvg), "pool_local_fwd: bad arguments (K=%d, ldx=%d, mode=%d)", K,
+               ldx, mode);
+  if (n_out == 0) return MINK_OK;
+  MINK_REQUIRE(x && nbr && y && (mode == kSum || cnt), "pool_local_fwd: NULL pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && a16(x) && a16(y);
+  const unsigned grid = pool_grid(n_out * (vec ? C / 4 : C));
+  if (mode == kAvg) {
+    if (vec) pool_local_fwd_kernel<4, kAvg><<<dim3(grid), PB, 0, st>>>(x, ldx, C, nbr, n_out, K, y, cnt);
+    else pool_local_fwd_kernel<1, kAvg><<<dim3(grid), PB, 0, st>>>(x, ldx, C, nbr, n_out, K, y, cnt);
+  } else {
+    if (vec) pool_local_fwd_kernel<4, kSum><<<dim3(grid), PB, 0, st>>>(x, ldx, C, nbr, n_out, K, y, cnt);
+    else pool_local_fwd_kernel<1, kSum><<<dim3(grid), PB, 0, st>>>(x, ldx, C, nbr, n_out, K, y, cnt);
+  }
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_pool_local_bwd(const float *dy, int32_t C, const int32_t *nbr_t, int64_t n_in, int32_t K, int32_t mode,
+                        const int32_t *cnt, float *dx, void *stream) {
+  POOL_SHAPE("pool_local_bwd", n_in, C);
+  MINK_REQUIRE(K >= 1 && K <= 81 && (mode == kSum || mode == kAvg), "pool_local_bwd: bad arguments (K=%d, mode=%d)", K, mode);
+  if (n_in == 0) return MINK_OK;
+  MINK_REQUIRE(dy && nbr_t && dx && (mode == kSum || cnt), "pool_local_bwd: NULL pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = (C & 3) == 0 && a16(dy) && a16(dx);
+  const unsigned grid = pool_grid(n_in * (vec ? C / 4 : C));
+  if (mode == kAvg) {
+    if (vec) pool_local_bwd_kernel<4, kAvg><<<dim3(grid), PB, 0, st>>>(dy, C, nbr_t, n_in, K, cnt, dx);
+    else pool_local_bwd_kernel<1, kAvg><<<dim3(grid), PB, 0, st>>>(dy, C, nbr_t, n_in, K, cnt, dx);
+  } else {
+    if (vec) pool_local_bwd_kernel<4, kSum><<<dim3(grid), PB, 0, st>>>(dy, C, nbr_t, n_in, K, cnt, dx);
+    else pool_local_bwd_kernel<1, kSum><<<dim3(grid), PB, 0, st>>>(dy, C, nbr_t, n_in, K, cnt, dx);
+  }
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_pool_local_max_fwd(const float *x, int32_t ldx, int32_t C, const int32_t *nbr, int64_t n_out, int32_t K, float *y,
+                            int32_t *arg, void *stream) {
+  POOL_SHAPE("pool_local_max_fwd", n_out, C);
+  MINK_REQUIRE(K >= 1 && K <= 81 && ldx >= C, "pool_local_max_fwd: bad arguments (K=%d, ldx=%d)", K, ldx);
+  if (n_out == 0) return MINK_OK;
+  MINK_REQUIRE(x && nbr && y && arg, "pool_local_max_fwd: NULL pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && a16(x) && a16(y) && a16(arg);
+  const unsigned grid = pool_grid(n_out * (vec ? C / 4 : C));
+  if (vec) pool_local_max_fwd_kernel<4><<<dim3(grid), PB, 0, st>>>(x, ldx, C, nbr, n_out, K, y, arg);
+  else pool_local_max_fwd_kernel<1><<<dim3(grid), PB, 0, st>>>(x, ldx, C, nbr, n_out, K, y, arg);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_pool_local_max_bwd(const float *dy, const int32_t *arg, int32_t C, const int32_t *nbr_t, int64_t n_in, int32_t K,
+                            float *dx, void *stream) {
+  POOL_SHAPE("pool_local_max_bwd", n_in, C);
+  MINK_REQUIRE(K >= 1 && K <= 81, "pool_local_max_bwd: bad arguments (K=%d)", K);
+  if (n_in == 0) return MINK_OK;
+  MINK_REQUIRE(dy && arg && nbr_t && dx, "pool_local_max_bwd: NULL pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = (C & 3) == 0 && a16(dy) && a16(arg) && a16(dx);
+  const unsigned grid = pool_grid(n_in * (vec ? C / 4 : C));
+  if (vec) pool_local_max_bwd_kernel<4><<<dim3(grid), PB, 0, st>>>(dy, arg, C, nbr_t, n_in, K, dx);
+  else pool_local_max_bwd_kernel<1><<<dim3(grid), PB, 0, st>>>(dy, arg, C, nbr_t, n_in, K, dx);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int64_t mink_global_pool_workspace_bytes(int64_t n, int32_t C, int32_t B) {
+  if (n < 0 || C < 1 || B < 1) return 0;
+  return (int64_t)B * pool_chunks(n, B) * C * (int64_t)sizeof(double);  // max: (float, int32) per partial; sum: one double
+}
+
+#define GPOOL_ARGS(name)                                                                                                           \
+  POOL_SHAPE(name, n, C);                                                                                                          \
+  MINK_REQUIRE(B >= 1 && B <= 65535, name ": bad batch size %d (1 <= B <= 65535)", B)
+
+int mink_global_max_fwd(const float *x, int64_t n, int32_t ldx, int32_t C, const int32_t *batch_offsets, int32_t B, float *y,
+                        int32_t *arg, void *workspace, int64_t workspace_bytes, void *stream) {
+  GPOOL_ARGS("global_max_fwd");
+  MINK_REQUIRE(ldx >= C && batch_offsets && y && arg && workspace && (n == 0 || x), "global_max_fwd: NULL pointer or ldx < C");
+  MINK_REQUIRE(workspace_bytes >= mink_global_pool_workspace_bytes(n, C, B) && ((uintptr_t)workspace & 7) == 0,
+               "global_max_fwd: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)workspace_bytes,
+               (long long)mink_global_pool_workspace_bytes(n, C, B));
+  hipStream_t st = (hipStream_t)stream;
+  const int G = pool_chunks(n, B);
+  float *pval = (float *)workspace;
+  int *parg = (int *)(pval + (int64_t)B * G * C);
+  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && a16(x);
+  const int VEC = vec ? 4 : 1, ncg = C / VEC, tprb = std::min(ncg, PB), rlanes = PB / tprb;
+  const dim3 grid((unsigned)G, (unsigned)B, (unsigned)cdiv(ncg, tprb));
+  const size_t shm = (size_t)rlanes * tprb * VEC * (sizeof(float) + sizeof(int));
+  if (vec) gmax_partial_kernel<4><<<grid, PB, shm, st>>>(x, ldx, batch_offsets, n, C, tprb, pval, parg);
+  else gmax_partial_kernel<1><<<grid, PB, shm, st>>>(x, ldx, batch_offsets, n, C, tprb, pval, parg);
+  MINK_CHECK_LAUNCH();
+  gmax_finalize_kernel<<<dim3((unsigned)cdiv(C, 4), (unsigned)B), PB, 0, st>>>(pval, parg, G, C, y, arg);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_global_max_bwd(const float *dy, const int32_t *arg, int64_t n, int32_t C, const int32_t *batch_offsets, int32_t B,
+                        float *dx, void *stream) {
+  GPOOL_ARGS("global_max_bwd");
+  if (n == 0) return MINK_OK;
+  MINK_REQUIRE(dy && arg && batch_offsets && dx, "global_max_bwd: NULL pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = (C & 3) == 0 && a16(dy) && a16(arg) && a16(dx);
+  if (vec) gpool_bwd_kernel<4, true><<<dim3(pool_grid(n * (C / 4))), PB, 0, st>>>(dy, arg, n, C, batch_offsets, B, dx);
+  else gpool_bwd_kernel<1, true><<<dim3(pool_grid(n * C)), PB, 0, st>>>(dy, arg, n, C, batch_offsets, B, dx);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_global_sum_fwd(const float *x, int64_t n, int32_t ldx, int32_t C, const int32_t *batch_offsets, int32_t B, float *y,
+                        void *workspace, int64_t workspace_bytes, void *stream) {
+  GPOOL_ARGS("global_sum_fwd");
+  MINK_REQUIRE(ldx >= C && batch_offsets && y && workspace && (n == 0 || x), "global_sum_fwd: NULL pointer or ldx < C");
+  MINK_REQUIRE(workspace_bytes >= mink_global_pool_workspace_bytes(n, C, B) && ((uintptr_t)workspace & 7) == 0,
+               "global_sum_fwd: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)workspace_bytes,
+               (long long)mink_global_pool_workspace_bytes(n, C, B));
+  hipStream_t st = (hipStream_t)stream;
+  const int G = pool_chunks(n, B);
+  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && a16(x);
+  const int VEC = vec ? 4 : 1, ncg = C / VEC, tprb = std::min(ncg, PB), rlanes = PB / tprb;
+  const dim3 grid((unsigned)G, (unsigned)B, (unsigned)cdiv(ncg, tprb));
+  const size_t shm = (size_t)rlanes * tprb * VEC * sizeof(double);
+  if (vec) gsum_partial_kernel<4><<<grid, PB, shm, st>>>(x, ldx, batch_offsets, n, C, tprb, (double *)workspace);
+  else gsum_partial_kernel<1><<<grid, PB, shm, st>>>(x, ldx, batch_offsets, n, C, tprb, (double *)workspace);
+  MINK_CHECK_LAUNCH();
+  gsum_finalize_kernel<<<dim3((unsigned)cdiv(C, 4), (unsigned)B), PB, 0, st>>>((const double *)workspace, G, C, y);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_global_sum_bwd(const float *dy, int64_t n, int32_t C, const int32_t *batch_offsets, int32_t B, float *dx, void *stream) {
+  GPOOL_ARGS("global_sum_bwd");
+  if (n == 0) return MINK_OK;
+  MINK_REQUIRE(dy && batch_offsets && dx, "global_sum_bwd: NULL pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = (C & 3) == 0 && a16(dy) && a16(dx);
+  if (vec) gpool_bwd_kernel<4, false><<<dim3(pool_grid(n * (C / 4))), PB, 0, st>>>(dy, nullptr, n, C, batch_offsets, B, dx);
+  else gpool_bwd_kernel<1, false><<<dim3(pool_grid(n * C)), PB, 0, st>>>(dy, nullptr, n, C, batch_offsets, B, dx);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+}  // extern "C"

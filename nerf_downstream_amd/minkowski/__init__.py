@@ -6,6 +6,7 @@ import enum
 from . import MinkowskiFunctional, MinkowskiOps, utils  # noqa: F401
 from .coords import CoordinateManager, CoordinateMapKey  # noqa: F401
 from .modules import (  # noqa: F401
+    MinkowskiAvgPooling,
     MinkowskiBatchNorm,
     MinkowskiCELU,
     MinkowskiConvolution,
@@ -14,10 +15,13 @@ from .modules import (  # noqa: F401
     MinkowskiELU,
     MinkowskiGELU,
     MinkowskiGlobalAvgPooling,
+    MinkowskiGlobalMaxPooling,
+    MinkowskiGlobalSumPooling,
     MinkowskiInstanceNorm,
     MinkowskiLayerNorm,
     MinkowskiLeakyReLU,
     MinkowskiLinear,
+    MinkowskiMaxPooling,
     MinkowskiNetwork,
     MinkowskiPReLU,
     MinkowskiReLU,

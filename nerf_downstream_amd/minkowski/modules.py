@@ -370,15 +370,81 @@ class MinkowskiDropout(nn.Module):
                             input.coordinate_manager)
 
 
-class MinkowskiSumPooling(nn.Module):
-    """ME.MinkowskiSumPooling(kernel_size=2, stride=2, dimension=3) (resnet.py:62-64)."""
+def _local_pool_args(name, kernel_size, stride, dilation, kernel_generator, dimension):
+    """(kernel_size, stride) of a local pooling layer, or ValueError naming the limit: dimension 3, dilation 1, no custom
+    kernel generator, a kernel that is odd (centred offsets) or equal to the stride (offsets {0..k-1}) with at most 27 cells."""
+    if dimension != 3:
+        raise ValueError(f"{name}: dimension={dimension!r}; the HIP backend implements dimension=3")
+    if kernel_generator is not None:
+        raise ValueError(f"{name}: custom kernel generators are not implemented (kernel_generator must be None)")
+    try:
+        ks, s, dil = _as_int(kernel_size), _as_int(stride), _as_int(dilation)
+    except AssertionError as e:
+        raise ValueError(f"{name}: {e}") from None
+    if dil != 1:
+        raise ValueError(f"{name}: dilation={dil}; only dilation=1 is implemented")
+    if ks < 1 or s < 1:
+        raise ValueError(f"{name}: kernel_size={ks}, stride={s}; both must be >= 1")
+    if ks ** 3 > 27:
+        raise ValueError(f"{name}: kernel_size={ks}; at most 27 kernel cells (kernel_size <= 3) are implemented")
+    if ks % 2 == 0 and ks != s:
+        raise ValueError(f"{name}: kernel_size={ks}, stride={s}; the kernel size must be odd or equal to the stride")
+    return ks, s
+
+
+class _LocalPooling(nn.Module):
+    """Local pooling on the coordinate map `CoordinateManager.stride(in_key, stride)` (the input map for stride 1) through the
+    neighbour tables the convolutions use: kernel_table(in_key, out_key, kernel_size, 1, transposed=True)."""
 
     def __init__(self, kernel_size, stride=1, dilation=1, kernel_generator=None, dimension=None):
         super().__init__()
-        self.kernel_size, self.stride = _as_int(kernel_size), _as_int(stride)
-        assert dimension == 3 and _as_int(dilation) == 1
-        assert self.kernel_size == self.stride and self.kernel_size ** 3 <= 27, \
-            "only non-overlapping pooling (kernel_size == stride) is implemented"
+        self.kernel_size, self.stride = _local_pool_args(type(self).__name__, kernel_size, stride, dilation, kernel_generator,
+                                                         dimension)
+        self.dilation, self.dimension = 1, dimension
+
+    def _tables(self, input):
+        m, in_key = input.coordinate_manager, input.coordinate_map_key
+        out_key = m.stride(in_key, self.stride)
+        nbr, nbr_t = m.kernel_table(in_key, out_key, self.kernel_size, 1, transposed=True)
+        return m, out_key, nbr, nbr_t
+
+    def extra_repr(self):
+        return f"kernel_size={self.kernel_size}, stride={self.stride}, dilation=1"
+
+
+class MinkowskiAvgPooling(_LocalPooling):
+    """ME.MinkowskiAvgPooling(kernel_size, stride=1, dilation=1, kernel_generator=None, dimension=None) (reference co3d.py:107,
+    scannet.py:511): every output voxel is the sum of the input voxels present in its window divided by HOW MANY are present,
+    not by the kernel volume [ME-recall of MinkowskiAvgPooling; parity unpinned: ME is absent and the reference holds no
+    fixture for this layer].  Windows may overlap (kernel_size=3, stride=2 or 1); stride 1 pools onto the input map."""
+
+    def forward(self, input):
+        m, out_key, nbr, nbr_t = self._tables(input)
+        out, _ = Fn.AvgPoolFunction.apply(input.F, nbr, nbr_t)
+        return SparseTensor(out, out_key, m)
+
+
+class MinkowskiMaxPooling(_LocalPooling):
+    """ME.MinkowskiMaxPooling(kernel_size, stride=1, dilation=1, kernel_generator=None, dimension=None) (reference fcnn.py:121:
+    kernel_size=3, stride=2): the channel-wise maximum over the input voxels present in the window; on a tie the gradient goes
+    to the first present voxel in kernel-offset order."""
+
+    def forward(self, input):
+        m, out_key, nbr, nbr_t = self._tables(input)
+        out, _ = Fn.SparseMaxPoolFunction.apply(input.F, nbr, nbr_t)
+        return SparseTensor(out, out_key, m)
+
+
+class MinkowskiSumPooling(nn.Module):
+    """ME.MinkowskiSumPooling(kernel_size=2, stride=2, dimension=3) (resnet.py:62-64).  kernel_size == stride is the
+    non-overlapping pooling of the ResNet stem (its own kernels and fused forms); an odd kernel_size != stride (3 over
+    stride 2 or 1) sums overlapping windows through the kernels of MinkowskiAvgPooling, without the division."""
+
+    def __init__(self, kernel_size, stride=1, dilation=1, kernel_generator=None, dimension=None):
+        super().__init__()
+        self.kernel_size, self.stride = _local_pool_args("MinkowskiSumPooling", kernel_size, stride, dilation, kernel_generator,
+                                                         dimension)
+        self.overlapping = self.kernel_size != self.stride
 
     def forward(self, input, norm=None, conv=None):
         """`norm` (extension): a MinkowskiBatchNorm to apply, followed by ReLU, to `input` on the
@@ -393,6 +459,13 @@ class MinkowskiSumPooling(nn.Module):
                 return fused
             input = conv(input, bn_stats=isinstance(norm, MinkowskiBatchNorm) and norm.bn.training)
         m, in_key = input.coordinate_manager, input.coordinate_map_key
+        if self.overlapping:  # (no fused forms: the norm, if any, runs as its own layer)
+            if norm is not None:
+                input = norm(input, relu=True)
+            out_key = m.stride(in_key, self.stride)
+            nbr, nbr_t = m.kernel_table(in_key, out_key, self.kernel_size, 1, transposed=True)
+            out, _ = Fn.OverlapSumPoolFunction.apply(input.F, nbr, nbr_t)
+            return SparseTensor(out, out_key, m)
         out_key = m.stride(in_key, self.stride)
         nbr, _ = m.kernel_table(in_key, out_key, self.kernel_size, 1)
         i2o = m.stride_map(in_key, out_key)
@@ -416,7 +489,7 @@ class MinkowskiSumPooling(nn.Module):
         """The fully fused stem, or None when it does not apply (eval mode, input gradient wanted,
         conv with bias / stride, SyncBN, or a shape the streaming weight-gradient kernel leaves
         to the general one)."""
-        if (norm is None or type(norm) is not MinkowskiBatchNorm or not norm.bn.affine or not norm.bn.training
+        if (self.overlapping or norm is None or type(norm) is not MinkowskiBatchNorm or not norm.bn.affine or not norm.bn.training
                 or not norm.bn.track_running_stats or conv.bias is not None or conv.use_mm or conv.stride != 1
                 or conv.kernel_volume != 27 or conv.dilation != 1 or input.F.requires_grad or not torch.is_grad_enabled()):
             return None
@@ -442,4 +515,31 @@ class MinkowskiGlobalAvgPooling(nn.Module):
     def forward(self, input):
         m = input.coordinate_manager
         out = Fn.GlobalAvgPoolFunction.apply(input.F, m.batch_offsets(input.coordinate_map_key))
+        return SparseTensor(out, CoordinateMapKey(ORIGIN_TS), m)
+
+
+class MinkowskiGlobalMaxPooling(nn.Module):
+    """ME.MinkowskiGlobalMaxPooling() (reference fcnn.py:12, pointnet.py:90): row b of the output is the channel-wise maximum
+    over the voxels of batch index b (zeros for a sample without voxels), on the origin map like MinkowskiGlobalAvgPooling --
+    so ME.cat(global_max(x), global_avg(x)) is the head of fcnn.py:15-18.  Segmented over the manager's device-resident batch
+    offsets: two launches forward, one backward whatever the batch size, no host synchronisation."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, input):
+        m = input.coordinate_manager
+        out, _ = Fn.GlobalMaxPoolFunction.apply(input.F, m.batch_offsets(input.coordinate_map_key))
+        return SparseTensor(out, CoordinateMapKey(ORIGIN_TS), m)
+
+
+class MinkowskiGlobalSumPooling(nn.Module):
+    """ME.MinkowskiGlobalSumPooling(): row b of the output is the sum over the voxels of batch index b (accumulated in double)."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, input):
+        m = input.coordinate_manager
+        out = Fn.GlobalSumPoolFunction.apply(input.F, m.batch_offsets(input.coordinate_map_key))
         return SparseTensor(out, CoordinateMapKey(ORIGIN_TS), m)
