@@ -530,6 +530,36 @@ int mink_global_sum_fwd(const float *x, int64_t n, int32_t ldx, int32_t C, const
                         void *workspace, int64_t workspace_bytes, void *stream);
 int mink_global_sum_bwd(const float *dy, int64_t n, int32_t C, const int32_t *batch_offsets, int32_t B, float *dx, void *stream);
 
+/* ------------------------------------------------------------------ trilinear interpolation and splat (csrc/interp.hip)
+ * ME.MinkowskiInterpolation (reference co3d_3d/src/data/transforms.py:472,514-521 PerlinNoise; models/mink/fcnn.py:194-208
+ * `y.interpolate(x)`) and TensorField.splat (fcnn.py:186) [ME-recall of interpolation_map_weight / TensorField.splat; parity
+ * unpinned: ME is absent and the reference holds no fixture for either].  Everything is fp32; conventions of the pooling
+ * family above (row pitch, 16-byte or dword lanes, no floating-point atomics, fixed summation order, -1 = absent).
+ *
+ * A query row (b, x, y, z) of tfield[n][4] (fp32, 16-byte aligned) is read against the map of tensor stride ts whose hash
+ * map is (table_keys, table_vals, cap) (values = row ids < n_rows).  Per axis lo = floor(x / ts) * ts with lo <= x < lo + ts
+ * exactly, d = (x - lo) / ts; corner c (bit 0 = x, bit 1 = y, bit 2 = z) is at lo + ts with factor d where its bit is set and
+ * at lo with factor 1 - d where it is clear; w[q][c] = the product of the three factors, imap[q][c] = the corner's row or -1
+ * (a present corner of weight 0 keeps its row).  The batch index is (int)b; one outside 0..65534 finds nothing.  A corner
+ * outside the 16-bit key range and a NaN or infinite coordinate set MINK_STATUS_RANGE in *status (a device word the caller
+ * zeroes). */
+int mink_interp_map_weight(const float *tfield, int64_t n, int32_t ts, const uint64_t *table_keys, const int32_t *table_vals,
+                           int64_t cap, int64_t n_rows, int32_t *imap, float *w, uint32_t *status, void *stream);
+/* The splat's coordinate rows: corners[8n][4] int32 = the eight corners of floor(tfield row) at tensor stride 1, listed
+ * (point 0, corners 0..7), (point 1, ...), and their weights w[8n] (may be NULL).  mink_coords_build_levels /
+ * mink_coords_make_keys + mink_coords_unique turn them into the map; the `inverse` they return is the splat's imap. */
+int mink_splat_coords(const float *tfield, int64_t n, int32_t *corners, float *w, uint32_t *status, void *stream);
+/* y[q][:] = sum over c = 0..7 (ascending, absent entries skipped) of w[q][c] * x[imap[q][c]][:]; x has n_x rows of pitch ldx.
+ * Interpolation forward and splat backward. */
+int mink_interp_gather(const float *x, int32_t ldx, int64_t n_x, int32_t C, const int32_t *imap, const float *w, int64_t n_q,
+                       float *y, void *stream);
+/* dx[i][:] = sum over j in [seg[i], seg[i+1]) of w[members[j]] * dy[members[j] >> 3][:], i < n_rows: the pairs (q, c) grouped
+ * by target row as a CSR, members[n_pairs] = q * 8 + c ascending inside a segment; dy has n_q rows of pitch ldy.
+ * Interpolation backward and splat forward.  A segment is summed by one wave (up to 256 pairs) or one workgroup (longer) in
+ * a fixed order: two runs are bitwise equal. */
+int mink_interp_segsum(const float *dy, int32_t ldy, int64_t n_q, int32_t C, const float *w, const int32_t *members,
+                       const int32_t *seg, int64_t n_rows, int64_t n_pairs, float *dx, void *stream);
+
 /* Elementwise: mode 0: y = max(x,0); mode 1: dx = (y>0) ? dy : 0 (a=dy,b=y);
  * mode 2: y = a + b. */
 int mink_eltwise(const float *a, const float *b, int64_t count, int32_t mode, float *y, void *stream);

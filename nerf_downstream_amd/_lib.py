@@ -164,6 +164,10 @@ SIGNATURES = {
     "mink_global_max_bwd": (ctypes.c_int, [_p, _p, _i64, _i32, _p, _i32, _p, _p]),
     "mink_global_sum_fwd": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _p, _i64, _p]),
     "mink_global_sum_bwd": (ctypes.c_int, [_p, _i64, _i32, _p, _i32, _p, _p]),
+    "mink_interp_map_weight": (ctypes.c_int, [_p, _i64, _i32, _p, _p, _i64, _i64, _p, _p, _p, _p]),
+    "mink_splat_coords": (ctypes.c_int, [_p, _i64, _p, _p, _p, _p]),
+    "mink_interp_gather": (ctypes.c_int, [_p, _i32, _i64, _i32, _p, _p, _i64, _p, _p]),
+    "mink_interp_segsum": (ctypes.c_int, [_p, _i32, _i64, _i32, _p, _p, _p, _i64, _i64, _p, _p]),
     "mink_global_avg_fwd": (ctypes.c_int, [_p, _i32, _p, _i32, _p, _p]),
     "mink_global_avg_bwd": (ctypes.c_int, [_p, _i32, _p, _i32, _i64, _p, _p]),
     "mink_head_forward": (ctypes.c_int, [_p, _p, _i32, _i32, _p, _p, _i32, _p, _p, _p]),

@@ -18,6 +18,7 @@ from .modules import (  # noqa: F401
     MinkowskiGlobalMaxPooling,
     MinkowskiGlobalSumPooling,
     MinkowskiInstanceNorm,
+    MinkowskiInterpolation,
     MinkowskiLayerNorm,
     MinkowskiLeakyReLU,
     MinkowskiLinear,

@@ -484,6 +484,31 @@ class CoordinateManager:
             self._note_lazy(lev.tkeys, lev.tvals)
         return lev.tkeys, lev.tvals, lev.cap
 
+    def interpolation_map_weight(self, key, tfield):
+        """(imap int32 [N, 8], w float32 [N, 8]) of the float queries tfield[N, 4] = (b, x, y, z) against the map `key`
+        [ME-recall of interpolation_map_weight; parity unpinned, ME is absent].  Per axis lo = floor(x / ts) * ts,
+        d = (x - lo) / ts; corner c (bit 0 = x, bit 1 = y, bit 2 = z) is at lo + ts with factor d where its bit is set, at lo
+        with 1 - d where it is clear, and weighs the product of its factors.  imap holds the corner's row, -1 where the map
+        has no such voxel (no renormalisation; a present corner of weight 0 keeps its row); the batch index is int(b), and
+        one without voxels finds nothing.  A corner outside the 16-bit key range, NaN and infinity raise ValueError (one
+        host read of the status word)."""
+        assert tfield.is_cuda and tfield.dim() == 2 and tfield.shape[1] == 4, "tfield: a device tensor [N, 4] = (b, x, y, z)"
+        q = tfield.detach().float().contiguous()
+        n, lev = q.shape[0], self.levels[key.ts]
+        tkeys, tvals, cap = self.hash_map(key.ts)
+        self._sync_lazy()
+        imap = torch.empty(n, 8, dtype=torch.int32, device=q.device)
+        w = torch.empty(n, 8, dtype=torch.float32, device=q.device)
+        status = torch.zeros(1, dtype=torch.int32, device=q.device)
+        check(lib().mink_interp_map_weight(q.data_ptr(), n, key.ts, tkeys.data_ptr(), tvals.data_ptr(), cap, lev.n, imap.data_ptr(),
+                                           w.data_ptr(), status.data_ptr(), _stream()))
+        if int(status.item()) & _STATUS_RANGE:
+            raise ValueError(
+                "coordinate outside the supported range (0 <= batch <= 65534, -32768 <= x, y, z <= 32767 for every corner of "
+                "the query's cell; NaN and infinite coordinates are refused)"
+            )
+        return imap, w
+
     # ------------------------------------------------------------------ maps built on demand
     # A map requested for the first time is built on whatever stream asks for it.  With several
     # compute streams (shortcut branch, weight-gradient stream) another stream may hit the cached

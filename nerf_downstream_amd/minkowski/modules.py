@@ -543,3 +543,25 @@ class MinkowskiGlobalSumPooling(nn.Module):
         m = input.coordinate_manager
         out = Fn.GlobalSumPoolFunction.apply(input.F, m.batch_offsets(input.coordinate_map_key))
         return SparseTensor(out, CoordinateMapKey(ORIGIN_TS), m)
+
+
+class MinkowskiInterpolation(nn.Module):
+    """ME.MinkowskiInterpolation(return_kernel_map=False, return_weights=False) (reference data/transforms.py:472,514-521)
+    [ME-recall of interpolation_map_weight; parity unpinned, ME is absent]: forward(input, tfield) reads the SparseTensor
+    `input`, at any tensor stride, at the float rows tfield[N, 4] = (b, x, y, z) by trilinear interpolation -> a tensor
+    [N, C].  A corner absent from the map contributes nothing (no renormalisation); the gradient goes to the features only.
+    With `return_kernel_map=True` or `return_weights=True` the result is ME's tuple (features, in_map, out_map, weights): the
+    found entries in (query, corner) order, in_map = rows of `input`, out_map = rows of tfield (one host synchronisation)."""
+
+    def __init__(self, return_kernel_map=False, return_weights=False):
+        super().__init__()
+        self.return_kernel_map, self.return_weights = bool(return_kernel_map), bool(return_weights)
+
+    def forward(self, input, tfield):
+        imap, w = input.coordinate_manager.interpolation_map_weight(input.coordinate_map_key, tfield)
+        out = Fn.InterpolationFunction.apply(input.F, imap, w, Fn.lazy_csr(imap, input.F.shape[0]))
+        if not (self.return_kernel_map or self.return_weights):
+            return out
+        flat = imap.reshape(-1)
+        found = torch.nonzero(flat >= 0).reshape(-1)
+        return out, flat[found].long(), found // 8, w.reshape(-1)[found]

@@ -69,6 +69,20 @@ class SparseTensor:
             F = Fn.slice_rows(self._F, m.field_inverse, *_field_members(m))  # (gather; backward: fixed-order segment sum)
         return TensorField(features=F, coordinates=field.C, _manager=m)
 
+    def features_at_coordinates(self, query):
+        """Trilinear interpolation of this tensor's features at the float rows query[N, 4] = (b, x, y, z), at any tensor
+        stride -> a tensor [N, C] [ME-recall of SparseTensor.features_at_coordinates; parity unpinned, ME is absent].  An
+        absent corner contributes nothing (no renormalisation); the gradient goes to the features only."""
+        imap, w = self._manager.interpolation_map_weight(self.coordinate_map_key, query)
+        return Fn.InterpolationFunction.apply(self._F, imap, w, Fn.lazy_csr(imap, self._F.shape[0]))
+
+    def interpolate(self, field):
+        """`y.interpolate(x)` (reference models/mink/fcnn.py:194-208): this tensor's features, at any tensor stride, read at
+        the coordinates of the TensorField `field` -> a TensorField with `field`'s coordinates and manager.  The field need
+        not be the one this tensor was quantised from (a splat lives on a manager of its own)."""
+        F = self.features_at_coordinates(field.C)
+        return TensorField(features=F, coordinates=field.C, _manager=field.coordinate_manager)
+
     def __iadd__(self, other):  # `out += residual`, reference resnet_block.py:66
         self._check(other)
         self._F = Fn.AddFunction.apply(self._F, other._F)
@@ -186,3 +200,32 @@ class TensorField:
             order, seg = _field_members(m)
             Fs = Fn.segment_mean(F, order, seg, n_unique)
         return SparseTensor(Fs, CoordinateMapKey(1), m)
+
+    def splat(self):
+        """`x.splat()` (reference models/mink/fcnn.py:186) [ME-recall of TensorField.splat; parity unpinned, ME is absent]:
+        every row is spread over the eight corners of its floor cell with the trilinear weights, F_s[v] = the sum of
+        w[p][c] * F[p] over the corners that fall on voxel v -- the transpose of interpolation, so the per-channel feature sum
+        is kept.  The voxels are the corners listed (point 0, corners 0..7), (point 1, ...), numbered by first occurrence.
+
+        The result lives on a coordinate manager OF ITS OWN: a manager holds one map per tensor stride, and this field's
+        manager already holds its floor map at stride 1.  Strided levels, convolutions and pooling work on the splat's
+        manager as on any other; `interpolate(field)` reads them back at this field."""
+        C = self._C.detach().float().contiguous()
+        n = C.shape[0]
+        if n == 0:
+            raise ValueError("empty coordinate field")
+        corners = torch.empty(8 * n, 4, dtype=torch.int32, device=C.device)
+        w = torch.empty(n, 8, dtype=torch.float32, device=C.device)
+        status = torch.zeros(1, dtype=torch.int32, device=C.device)
+        Fn.check(Fn.lib().mink_splat_coords(C.data_ptr(), n, corners.data_ptr(), w.data_ptr(), status.data_ptr(), Fn._stream()))
+        if int(status.item()) & 1:  # MINK_STATUS_RANGE
+            raise ValueError(
+                "coordinate outside the supported range (0 <= batch <= 65534, -32768 <= x, y, z <= 32767 for every corner of "
+                "the point's cell; NaN and infinite coordinates are refused)"
+            )
+        m = CoordinateManager(D=C.shape[1] - 1, device=C.device)
+        key = m.insert_field(corners)
+        n_rows = m.levels[1].n
+        imap = m.field_inverse.reshape(n, 8)
+        Fs = Fn.SplatFunction.apply(self._F, imap, w, Fn.pair_csr(imap, n_rows), n_rows)
+        return SparseTensor(Fs, key, m)
