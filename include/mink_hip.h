@@ -560,6 +560,35 @@ int mink_interp_gather(const float *x, int32_t ldx, int64_t n_x, int32_t C, cons
 int mink_interp_segsum(const float *dy, int32_t ldy, int64_t n_q, int32_t C, const float *w, const int32_t *members,
                        const int32_t *seg, int64_t n_rows, int64_t n_pairs, float *dx, void *stream);
 
+/* ------------------------------------------------------------------ point stage of the point classifiers (csrc/field.hip)
+ * What happens on a TensorField before and after .sparse() in reference models/mink/fcnn.py:143-165 and pointnet.py:100-109.
+ * Conventions of the pooling and interpolation families above (fp32, row pitch, 16-byte or dword lanes, no floating-point
+ * atomics, fixed summation order, -1 = absent, a device status word for range errors).
+ *
+ * `y.slice(x)` at tensor stride ts (reference fcnn.py:158-161: strides 2, 8, 32, 128): idx[i] = the row of the voxel of tensor
+ * stride ts that contains the float row (b, x, y, z) of tfield[n][4] (fp32, 16-byte aligned), or -1 when the map
+ * (table_keys, table_vals, cap; values = row ids < n_rows) holds none.  The key is floor(floor(x) / ts) * ts per axis (floor
+ * towards minus infinity for negative values too), the batch index is (int)b and one outside 0..65534 finds nothing; key
+ * packing and probe sequence are those of mink_interp_map_weight.  A key outside the 16-bit range and a NaN or infinite
+ * coordinate set MINK_STATUS_RANGE in *status (a device word the caller zeroes).
+ * [ME-recall of SparseTensor.slice: ME composes the field's inverse mapping with the stride maps from tensor stride 1 to ts;
+ * for a level derived by striding -- every level of a manager here -- that is the voxel containing the point, which is what
+ * this computes directly.  Parity unpinned: ME is absent and the reference holds no fixture for it.] */
+int mink_field_map(const float *tfield, int64_t n, int32_t ts, const uint64_t *table_keys, const int32_t *table_vals, int64_t cap,
+                   int64_t n_rows, int32_t *idx, uint32_t *status, void *stream);
+/* `ME.cat(y1.slice(x), ..., y4.slice(x))` (reference fcnn.py:158-163) in one launch, without the [n][C_s] intermediates:
+ * y[i][off_s : off_s + C_s] = x_s[idx_s[i]][:], off_s = C_0 + ... + C_(s-1), for 1 <= n_src <= 8 sources; source s has rows[s]
+ * rows of pitch ldx[s]; idx_s[i] < 0 (or >= rows[s]) gives zeros in that source's columns.  x, ldx, rows, C, idx are HOST arrays
+ * of n_src entries; y has n rows of pitch ldy >= the sum of C.  The backward is mink_segment_sum per source over the column
+ * slice dy + off_s (pitch ldy) with a CSR of the field rows grouped by voxel, rows with idx < 0 in no segment. */
+int mink_field_gather_cat(int32_t n_src, const float *const *x, const int32_t *ldx, const int64_t *rows, const int32_t *C,
+                          const int32_t *const *idx, int64_t n, float *y, int32_t ldy, void *stream);
+/* Backward of mink_segment_mean (TensorField.sparse() of learned per-point features, reference fcnn.py:143-144,165):
+ * dx[members[j]][:] = dy[u][:] / (seg[u+1] - seg[u]) for j in [seg[u], seg[u+1]), u < n_out; members[n_members] are rows of
+ * dx (n_in rows of pitch lddx), each written exactly once; a member behind seg[n_out] belongs to no segment. */
+int mink_segment_mean_bwd(const float *dy, int32_t ldy, int32_t C, const int32_t *members, const int32_t *seg, int64_t n_out,
+                          int64_t n_members, int64_t n_in, float *dx, int32_t lddx, void *stream);
+
 /* Elementwise: mode 0: y = max(x,0); mode 1: dx = (y>0) ? dy : 0 (a=dy,b=y);
  * mode 2: y = a + b. */
 int mink_eltwise(const float *a, const float *b, int64_t count, int32_t mode, float *y, void *stream);

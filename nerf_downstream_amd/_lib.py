@@ -168,6 +168,9 @@ SIGNATURES = {
     "mink_splat_coords": (ctypes.c_int, [_p, _i64, _p, _p, _p, _p]),
     "mink_interp_gather": (ctypes.c_int, [_p, _i32, _i64, _i32, _p, _p, _i64, _p, _p]),
     "mink_interp_segsum": (ctypes.c_int, [_p, _i32, _i64, _i32, _p, _p, _p, _i64, _i64, _p, _p]),
+    "mink_field_map": (ctypes.c_int, [_p, _i64, _i32, _p, _p, _i64, _i64, _p, _p, _p]),
+    "mink_field_gather_cat": (ctypes.c_int, [_i32, _p, _p, _p, _p, _p, _i64, _p, _i32, _p]),
+    "mink_segment_mean_bwd": (ctypes.c_int, [_p, _i32, _i32, _p, _p, _i64, _i64, _i64, _p, _i32, _p]),
     "mink_global_avg_fwd": (ctypes.c_int, [_p, _i32, _p, _i32, _p, _p]),
     "mink_global_avg_bwd": (ctypes.c_int, [_p, _i32, _p, _i32, _i64, _p, _p]),
     "mink_head_forward": (ctypes.c_int, [_p, _p, _i32, _i32, _p, _p, _i32, _p, _p, _p]),

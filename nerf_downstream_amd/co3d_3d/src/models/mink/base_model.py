@@ -1,5 +1,6 @@
 """Input boundary of the Minkowski models (counterpart of the reference's
 co3d_3d/src/models/mink/base_model.py:6-13 and models/interface.py:4-9)."""
+import os
 from abc import ABC, abstractmethod
 
 from nerf_downstream_amd import minkowski as _HIP_ME
@@ -24,7 +25,8 @@ class MinkowskiBaseModel(_HIP_ME.MinkowskiNetwork, InputInterface):
         self._coord_plan = None
         self._recent_traces = []  # map-request traces of the last few fields (filled by their forward pass)
         self._side = None
-        self.prepare_ahead = True
+        # (MINK_PREPARE_AHEAD=0: every batch's maps are built on the compute stream, on demand -- the A/B switch of the trainer CLI)
+        self.prepare_ahead = os.environ.get("MINK_PREPARE_AHEAD", "1") != "0"
 
     def process_input(self, batch, defer=False, _fence=True):
         """`defer=True` (extension, HIP backend): only launch the coordinate pyramid of this batch

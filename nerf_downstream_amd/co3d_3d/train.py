@@ -19,6 +19,7 @@ import csv
 import json
 import logging
 import os
+import random
 import subprocess
 import sys
 import time
@@ -422,6 +423,7 @@ def main(argv=None):
     logging.info(f"Gin configuration files: {args.ginc}")
     logging.info(f"Gin bindings: {ginbs}")
     np.random.seed(args.seed)
+    random.seed(args.seed)  # (the augmentation gates draw from `random`: reference pl.seed_everything seeds it too)
     gin.parse_config_files_and_bindings(args.ginc, ginbs)
     train(save_path=args.save_path, resume_training=args.resume, run_name=args.run_name,
           run_name_postfix=args.run_name_postfix, seed=args.seed)

@@ -187,6 +187,8 @@ class CoordinateManager:
         self.field_inverse = None
         self.field_members = None  # (order, seg) of TensorField.sparse(): the rows of every voxel, CSR
         self.field_unique_index = None
+        self._field_maps = {}  # tensor stride -> (coordinate tensor, idx, csr_fn) of field_map(): the strided slices of a field
+        self._field_boff = None  # (coordinate tensor, offsets) of field_batch_offsets(): global pooling of a field
         self._boff = {}
         self._batch_size = None
         self._batch_checked = False
@@ -508,6 +510,50 @@ class CoordinateManager:
                 "the query's cell; NaN and infinite coordinates are refused)"
             )
         return imap, w
+
+    def field_map(self, key, coords):
+        """(idx int32 [N], csr_fn) of the float rows coords[N, 4] = (b, x, y, z) of a TensorField of this manager against
+        the map `key`: idx[i] = the row of the voxel of that tensor stride containing row i, -1 where there is none
+        (mink_field_map) [ME-recall of SparseTensor.slice; parity unpinned, ME is absent]; csr_fn() -> the rows grouped by
+        voxel (functional.index_csr), built on first use -- the backward of the slice.  Kept on the manager per tensor stride
+        for the coordinate tensor it was computed from (a field and everything derived from it share that tensor), so the
+        four slices of fcnn.py:158-161 and the next batch's backward find it.  Out-of-range, NaN and infinite rows raise
+        ValueError (one host read of the status word)."""
+        assert coords.is_cuda and coords.dim() == 2 and coords.shape[1] == 4, "coords: a device tensor [N, 4] = (b, x, y, z)"
+        self._sync_lazy()
+        ent = self._field_maps.get(key.ts)
+        if ent is not None and ent[0] is coords:
+            return ent[1], ent[2]
+        Fn = _Fn()
+        q = coords.detach().float().contiguous()
+        n, lev = q.shape[0], self.levels[key.ts]
+        tkeys, tvals, cap = self.hash_map(key.ts)
+        self._sync_lazy()
+        out = torch.zeros(n + 1, dtype=torch.int32, device=q.device)  # [idx | status]
+        check(lib().mink_field_map(q.data_ptr(), n, key.ts, tkeys.data_ptr(), tvals.data_ptr(), cap, lev.n, out.data_ptr(),
+                                   out[n:].data_ptr(), _stream()))
+        if int(out[n].item()) & _STATUS_RANGE:
+            raise ValueError(
+                "coordinate outside the supported range (0 <= batch <= 65534, -32768 <= x, y, z <= 32767 after "
+                "quantisation; NaN and infinite coordinates are refused)"
+            )
+        idx = out[:n]
+        csr_fn = Fn.lazy_index_csr(idx, lev.n)
+        self._field_maps[key.ts] = (coords, idx, csr_fn)
+        self._note_lazy(out)
+        return idx, csr_fn
+
+    def field_batch_offsets(self, coords):
+        """int32 [B + 1] row ranges per batch index of a TensorField's own rows (global pooling of a field, reference
+        pointnet.py:106): from the batch column, on the device; ValueError when it is not non-decreasing.  Kept for the
+        coordinate tensor it was computed from."""
+        self._sync_lazy()
+        ent = self._field_boff
+        if ent is None or ent[0] is not coords:
+            boff = _Fn().field_batch_offsets(coords, self._batch_size)
+            ent = self._field_boff = (coords, boff)
+            self._note_lazy(boff)
+        return ent[1]
 
     # ------------------------------------------------------------------ maps built on demand
     # A map requested for the first time is built on whatever stream asks for it.  With several

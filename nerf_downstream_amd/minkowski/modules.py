@@ -8,7 +8,40 @@ import torch.nn as nn
 
 from . import functional as Fn
 from .coords import ORIGIN_TS, CoordinateMapKey, _as_int
-from .tensor import SparseTensor
+from .tensor import SparseTensor, TensorField
+
+
+def _features(input):
+    """The feature matrix of a SparseTensor or a TensorField.  A field may come straight from the prepare stream: its
+    manager, coordinates and features are made usable on the current stream first (TensorField._settle, once per field)."""
+    if isinstance(input, TensorField):
+        input._settle()
+    return input.F
+
+
+def _same_kind(input, features):
+    """`features` on the rows of `input`: a TensorField with its coordinates and manager for a field (reference fcnn.py:143,
+    pointnet.py:100-109 run Linear / BatchNorm / activation / Dropout on the points), a SparseTensor on its map otherwise."""
+    if isinstance(input, TensorField):
+        return input._like(features)
+    return SparseTensor(features, input.coordinate_map_key, input.coordinate_manager)
+
+
+def _check_same(input, other):
+    if isinstance(input, TensorField):
+        if not isinstance(other, TensorField) or other.coordinate_manager is not input.coordinate_manager or other.F.shape[0] != input.F.shape[0]:
+            raise ValueError("TensorFields must share the coordinate manager and the rows")
+    else:
+        input._check(other)
+
+
+def _sample_offsets(input):
+    """int32 [B+1] device row ranges of the batch samples: the map's for a SparseTensor, the field's own rows for a TensorField."""
+    m = input.coordinate_manager
+    if isinstance(input, TensorField):
+        input._settle()
+        return m.field_batch_offsets(input.C)
+    return m.batch_offsets(input.coordinate_map_key)
 
 
 class MinkowskiNetwork(nn.Module):
@@ -136,7 +169,23 @@ class MinkowskiConvolutionTranspose(MinkowskiConvolution):
 
 def cat(*tensors):
     """ME.cat (reference res16unet.py:410-425): feature-wise concatenation of sparse tensors that share
-    one coordinate map."""
+    one coordinate map -- or of TensorFields that share a manager and their rows (reference fcnn.py:163), giving a
+    TensorField.  When every argument is a strided slice whose gather is still pending (`y.slice(x)` at a tensor stride
+    beyond 1), the concatenated rows are written by one launch (mink_field_gather_cat), bit for bit what torch.cat of the
+    separate slices gives, forward and backward."""
+    fields = [isinstance(t, TensorField) for t in tensors]
+    if any(fields):
+        if not all(fields):
+            raise ValueError("ME.cat: SparseTensors and TensorFields cannot be mixed")
+        first = tensors[0]
+        for t in tensors[1:]:
+            if t.coordinate_manager is not first.coordinate_manager or t.C.shape[0] != first.C.shape[0]:
+                raise ValueError("TensorFields must share the coordinate manager and the rows")
+        if len(tensors) <= 8 and all(t._F is None and t._pending is not None for t in tensors):
+            out = Fn.FieldGatherCatFunction.apply(tuple(t._pending[1] for t in tensors), *[t._pending[0] for t in tensors])
+        else:
+            out = torch.cat([t.F for t in tensors], dim=1)
+        return first._like(out)
     for t in tensors[1:]:
         tensors[0]._check(t)
     return SparseTensor(torch.cat([t.F for t in tensors], dim=1), tensors[0].coordinate_map_key,
@@ -171,16 +220,17 @@ class MinkowskiBatchNorm(nn.Module):
         training = bn.training or not bn.track_running_stats
         if training and bn.track_running_stats and not self.counted_by_parent:
             bn.num_batches_tracked += 1
+        F = _features(input)
         if residual is not None:
-            input._check(residual)
-        gamma = bn.weight if bn.affine else torch.ones(bn.num_features, device=input.F.device)
-        beta = bn.bias if bn.affine else torch.zeros(bn.num_features, device=input.F.device)
+            _check_same(input, residual)
+        gamma = bn.weight if bn.affine else torch.ones(bn.num_features, device=F.device)
+        beta = bn.bias if bn.affine else torch.zeros(bn.num_features, device=F.device)
         out = Fn.BatchNormFunction.apply(
-            input.F, gamma, beta, bn.running_mean, bn.running_var, training,
+            F, gamma, beta, bn.running_mean, bn.running_var, training,
             _bn_momentum(bn), bn.eps,
             residual.F if residual is not None else None, bool(relu),
             getattr(input, "_bn_partial", None) if training else None)
-        return SparseTensor(out, input.coordinate_map_key, input.coordinate_manager)
+        return _same_kind(input, out)
 
 
 class MinkowskiSyncBatchNorm(MinkowskiBatchNorm):
@@ -202,11 +252,11 @@ class MinkowskiSyncBatchNorm(MinkowskiBatchNorm):
         if bn.track_running_stats and not self.counted_by_parent:
             bn.num_batches_tracked += 1
         if residual is not None:
-            input._check(residual)
+            _check_same(input, residual)
         out = Fn.SyncBatchNormFunction.apply(
-            input.F, bn.weight, bn.bias, bn.running_mean, bn.running_var, _bn_momentum(bn),
+            _features(input), bn.weight, bn.bias, bn.running_mean, bn.running_var, _bn_momentum(bn),
             bn.eps, residual.F if residual is not None else None, bool(relu), self.process_group)
-        return SparseTensor(out, input.coordinate_map_key, input.coordinate_manager)
+        return _same_kind(input, out)
 
     @classmethod
     def convert_sync_batchnorm(cls, module, process_group=None):
@@ -232,7 +282,7 @@ class MinkowskiReLU(nn.Module):
         self.inplace = inplace
 
     def forward(self, input):
-        return SparseTensor(Fn.ReLUFunction.apply(input.F), input.coordinate_map_key, input.coordinate_manager)
+        return _same_kind(input, Fn.ReLUFunction.apply(_features(input)))
 
 
 class _Activation(nn.Module):
@@ -248,8 +298,7 @@ class _Activation(nn.Module):
             self.alpha = float(args[0] if args else kwargs.get(self.ARG, self.ALPHA))
 
     def forward(self, input):
-        out = Fn.ActivationFunction.apply(input.F, self.KIND, self.alpha, None)
-        return SparseTensor(out, input.coordinate_map_key, input.coordinate_manager)
+        return _same_kind(input, Fn.ActivationFunction.apply(_features(input), self.KIND, self.alpha, None))
 
 
 class MinkowskiLeakyReLU(_Activation):
@@ -280,8 +329,7 @@ class MinkowskiPReLU(nn.Module):
         self.weight = nn.Parameter(torch.full((num_parameters,), float(init)))
 
     def forward(self, input):
-        out = Fn.ActivationFunction.apply(input.F, "prelu", 0.0, self.weight)
-        return SparseTensor(out, input.coordinate_map_key, input.coordinate_manager)
+        return _same_kind(input, Fn.ActivationFunction.apply(_features(input), "prelu", 0.0, self.weight))
 
 
 class MinkowskiInstanceNorm(nn.Module):
@@ -303,13 +351,12 @@ class MinkowskiInstanceNorm(nn.Module):
         self.bias = nn.Parameter(torch.zeros(1, num_features))
 
     def forward(self, input, relu=False, residual=None):
-        m = input.coordinate_manager
         if residual is not None:
-            input._check(residual)
-        out = Fn.InstanceNormFunction.apply(input.F, self.weight.reshape(-1), self.bias.reshape(-1),
-                                            m.batch_offsets(input.coordinate_map_key), self.eps,
+            _check_same(input, residual)
+        out = Fn.InstanceNormFunction.apply(_features(input), self.weight.reshape(-1), self.bias.reshape(-1),
+                                            _sample_offsets(input), self.eps,
                                             residual.F if residual is not None else None, bool(relu))
-        return SparseTensor(out, input.coordinate_map_key, m)
+        return _same_kind(input, out)
 
     def extra_repr(self):
         return f"{self.num_features}, eps={self.eps}"
@@ -330,23 +377,15 @@ class MinkowskiLayerNorm(nn.Module):
         self.ln = nn.LayerNorm(num_features, eps=eps, elementwise_affine=affine)
 
     def forward(self, input, relu=False, residual=None):
-        from .tensor import TensorField
-
         ln = self.ln
-        F = input.F
+        F = _features(input)
         if residual is not None:
-            if isinstance(input, TensorField):
-                if residual.coordinate_manager is not input.coordinate_manager or residual.F.shape != F.shape:
-                    raise ValueError("TensorFields must share the coordinate manager and the rows")
-            else:
-                input._check(residual)
+            _check_same(input, residual)
         C = ln.normalized_shape[0]
         gamma = ln.weight if ln.weight is not None else torch.ones(C, device=F.device)
         beta = ln.bias if ln.bias is not None else torch.zeros(C, device=F.device)
         out = Fn.LayerNormFunction.apply(F, gamma, beta, ln.eps, residual.F if residual is not None else None, bool(relu))
-        if isinstance(input, TensorField):
-            return TensorField(features=out, coordinates=input.C, _manager=input.coordinate_manager)
-        return SparseTensor(out, input.coordinate_map_key, input.coordinate_manager)
+        return _same_kind(input, out)
 
 
 class MinkowskiLinear(nn.Module):
@@ -357,7 +396,7 @@ class MinkowskiLinear(nn.Module):
         self.linear = nn.Linear(in_features, out_features, bias=bias)
 
     def forward(self, input):
-        return SparseTensor(self.linear(input.F), input.coordinate_map_key, input.coordinate_manager)
+        return _same_kind(input, self.linear(_features(input)))
 
 
 class MinkowskiDropout(nn.Module):
@@ -366,8 +405,7 @@ class MinkowskiDropout(nn.Module):
         self.p = p
 
     def forward(self, input):
-        return SparseTensor(nn.functional.dropout(input.F, self.p, self.training), input.coordinate_map_key,
-                            input.coordinate_manager)
+        return _same_kind(input, nn.functional.dropout(_features(input), self.p, self.training))
 
 
 def _local_pool_args(name, kernel_size, stride, dilation, kernel_generator, dimension):
@@ -513,9 +551,8 @@ class MinkowskiGlobalAvgPooling(nn.Module):
     """ME.MinkowskiGlobalAvgPooling() (resnet.py:15-22): row b of the output is batch index b."""
 
     def forward(self, input):
-        m = input.coordinate_manager
-        out = Fn.GlobalAvgPoolFunction.apply(input.F, m.batch_offsets(input.coordinate_map_key))
-        return SparseTensor(out, CoordinateMapKey(ORIGIN_TS), m)
+        out = Fn.GlobalAvgPoolFunction.apply(_features(input), _sample_offsets(input))
+        return SparseTensor(out, CoordinateMapKey(ORIGIN_TS), input.coordinate_manager)
 
 
 class MinkowskiGlobalMaxPooling(nn.Module):
@@ -528,9 +565,8 @@ class MinkowskiGlobalMaxPooling(nn.Module):
         super().__init__()
 
     def forward(self, input):
-        m = input.coordinate_manager
-        out, _ = Fn.GlobalMaxPoolFunction.apply(input.F, m.batch_offsets(input.coordinate_map_key))
-        return SparseTensor(out, CoordinateMapKey(ORIGIN_TS), m)
+        out, _ = Fn.GlobalMaxPoolFunction.apply(_features(input), _sample_offsets(input))
+        return SparseTensor(out, CoordinateMapKey(ORIGIN_TS), input.coordinate_manager)
 
 
 class MinkowskiGlobalSumPooling(nn.Module):
@@ -540,9 +576,8 @@ class MinkowskiGlobalSumPooling(nn.Module):
         super().__init__()
 
     def forward(self, input):
-        m = input.coordinate_manager
-        out = Fn.GlobalSumPoolFunction.apply(input.F, m.batch_offsets(input.coordinate_map_key))
-        return SparseTensor(out, CoordinateMapKey(ORIGIN_TS), m)
+        out = Fn.GlobalSumPoolFunction.apply(_features(input), _sample_offsets(input))
+        return SparseTensor(out, CoordinateMapKey(ORIGIN_TS), input.coordinate_manager)
 
 
 class MinkowskiInterpolation(nn.Module):

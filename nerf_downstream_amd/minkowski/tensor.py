@@ -60,14 +60,22 @@ class SparseTensor:
     def slice(self, field):
         """`out.slice(x)` (reference res16unet.py:435): the features of this tensor-stride-1 tensor read
         back at the rows of the TensorField it was quantised from (F[inverse mapping])."""
-        if not (_is_one(self.tensor_stride) and field.coordinate_manager is self._manager):
-            raise ValueError("slice: needs the tensor-stride-1 tensor and the field it came from")
+        if field.coordinate_manager is not self._manager:
+            raise ValueError("slice: needs the tensor-stride-1 tensor and the field it came from (a tensor at another tensor "
+                             "stride is read at a field of ITS OWN coordinate manager only)")
         m = self._manager
+        if not _is_one(self.tensor_stride):
+            # reference fcnn.py:158-161 (strides 2, 8, 32, 128): every field row reads the voxel of this stride containing it
+            # (mink_field_map, kept on the manager).  The gather is left pending so that ME.cat of several such slices
+            # writes the concatenated rows in one launch; `.F` of the result runs it for this slice alone.
+            field._settle()
+            return TensorField(features=None, coordinates=field.C, _manager=m, _origin=field,
+                               _pending=(self._F, m.field_map(self.coordinate_map_key, field.C)))
         if m.levels[1].n == field.F.shape[0]:
             F = self._F  # no duplicates: the rows are the field's rows, in order (no copy)
         else:
             F = Fn.slice_rows(self._F, m.field_inverse, *_field_members(m))  # (gather; backward: fixed-order segment sum)
-        return TensorField(features=F, coordinates=field.C, _manager=m)
+        return TensorField(features=F, coordinates=field.C, _manager=m, _origin=field)
 
     def features_at_coordinates(self, query):
         """Trilinear interpolation of this tensor's features at the float rows query[N, 4] = (b, x, y, z), at any tensor
@@ -81,7 +89,7 @@ class SparseTensor:
         the coordinates of the TensorField `field` -> a TensorField with `field`'s coordinates and manager.  The field need
         not be the one this tensor was quantised from (a splat lives on a manager of its own)."""
         F = self.features_at_coordinates(field.C)
-        return TensorField(features=F, coordinates=field.C, _manager=field.coordinate_manager)
+        return TensorField(features=F, coordinates=field.C, _manager=field.coordinate_manager, _origin=field)
 
     def __iadd__(self, other):  # `out += residual`, reference resnet_block.py:66
         self._check(other)
@@ -125,10 +133,19 @@ class TensorField:
         `defer=True` only launches the coordinate pyramid (no host synchronisation); `finish()`
         -- called explicitly once other work has been queued, or implicitly by `.sparse()` --
         reads the row counts back and builds the rest of the plan on the same stream."""
-        assert features is not None and coordinates is not None
-        if kwargs.get("_manager") is not None:  # a slice(): shares the manager of the field it came from
+        self._origin = self._pending = None
+        if kwargs.get("_manager") is not None:  # a derived field (a slice(), a module's output): shares the manager of the field it came from
+            # `_origin`: the field that built the manager -- it alone holds the plan, the build stream and the readiness event,
+            # so `.sparse()` of a derived field runs ITS finish() and hand-over.  `_pending` = (source features, (idx, csr_fn)):
+            # a strided slice whose gather has not run yet (see SparseTensor.slice).
+            assert coordinates is not None and (features is not None or kwargs.get("_pending") is not None)
             self._F, self._C, self._manager, self._plan, self._ready = features, coordinates, kwargs["_manager"], None, None
+            origin = kwargs.get("_origin")
+            if origin is not None and origin._manager is self._manager:
+                self._origin = origin._origin if origin._origin is not None else origin
+            self._pending = kwargs.get("_pending")
             return
+        assert features is not None and coordinates is not None
         qm = kwargs.get("quantization_mode")
         if qm is not None and getattr(qm, "name", str(qm)) != "UNWEIGHTED_AVERAGE":
             raise NotImplementedError(f"TensorField(quantization_mode={qm}): only UNWEIGHTED_AVERAGE (the ME default the "
@@ -166,6 +183,9 @@ class TensorField:
 
     @property
     def F(self):
+        if self._F is None:  # a strided slice read on its own: the one-source form of the fused gather
+            x, fmap = self._pending
+            self._F = Fn.FieldGatherCatFunction.apply((fmap,), x)
         return self._F
 
     @property
@@ -176,29 +196,44 @@ class TensorField:
     def coordinate_manager(self):
         return self._manager
 
-    def sparse(self):
-        m = self._manager
-        self.finish()
-        if self._ready is not None:  # maps were built ahead of time on another stream
+    def _like(self, features):
+        """A field with these features on this field's rows: same coordinates, same manager, same origin."""
+        return TensorField(features=features, coordinates=self._C, _manager=self._manager, _origin=self)
+
+    def _settle(self):
+        """Everything the manager holds is usable on the current stream: the origin's deferred construction is finished and,
+        when its maps were built ahead on the prepare stream, the current stream waits for them and takes them over -- once;
+        later calls, from the origin or from any field derived from it, find nothing left to do."""
+        root = self._origin if self._origin is not None else self
+        m = root._manager
+        root.finish()
+        if root._ready is not None:  # maps were built ahead of time on another stream
             cur = Fn.current_stream()
-            cur.wait_event(self._ready)
+            cur.wait_event(root._ready)
             m.hand_over(cur)
-            for t in (self._F, self._C):  # may have been produced on the build stream (GPU-side decode)
+            for t in (root._F, root._C):  # may have been produced on the build stream (GPU-side decode)
                 t.record_stream(cur)
             for name in ("source_rows", "row_labels", "point_rows"):  # (segmentation batches: the labels of the rows)
-                rows = getattr(self, name, None)
+                rows = getattr(root, name, None)
                 if rows is not None:
                     rows.record_stream(cur)
             if m.xb is not None:
                 m.xb[1].record_stream(cur)
-            self._ready = None
+            root._ready = None
+
+    def sparse(self):
+        m = self._manager
+        self._settle()
         n_unique = m.levels[1].n
-        F = self._F
+        F = self.F
         if n_unique == F.shape[0]:
             Fs = F.float()  # no duplicates: unique rows are the input rows, in order
         else:
             order, seg = _field_members(m)
-            Fs = Fn.segment_mean(F, order, seg, n_unique)
+            if F.requires_grad and torch.is_grad_enabled():  # learned per-point features (reference fcnn.py:143-144,165)
+                Fs = Fn.SegmentMeanFunction.apply(F, order, seg, n_unique)
+            else:
+                Fs = Fn.segment_mean(F, order, seg, n_unique)
         return SparseTensor(Fs, CoordinateMapKey(1), m)
 
     def splat(self):
@@ -210,6 +245,7 @@ class TensorField:
         The result lives on a coordinate manager OF ITS OWN: a manager holds one map per tensor stride, and this field's
         manager already holds its floor map at stride 1.  Strided levels, convolutions and pooling work on the splat's
         manager as on any other; `interpolate(field)` reads them back at this field."""
+        self._settle()
         C = self._C.detach().float().contiguous()
         n = C.shape[0]
         if n == 0:
@@ -227,5 +263,5 @@ class TensorField:
         key = m.insert_field(corners)
         n_rows = m.levels[1].n
         imap = m.field_inverse.reshape(n, 8)
-        Fs = Fn.SplatFunction.apply(self._F, imap, w, Fn.pair_csr(imap, n_rows), n_rows)
+        Fs = Fn.SplatFunction.apply(self.F, imap, w, Fn.pair_csr(imap, n_rows), n_rows)
         return SparseTensor(Fs, key, m)
