@@ -1052,6 +1052,40 @@ typedef struct {
 int mink_conv_timing(int32_t mode, int32_t kind, int32_t K, int32_t cin, int32_t cout);
 int64_t mink_conv_timing_fetch(MinkTimingEntry *out, int64_t max);
 
+/* ------------------------------------------------------------------ dynamic graph layers (csrc/graph.hip)
+ * DGCNN (reference co3d_3d/src/models/mink/dgcnn.py:8-38,81-85) on the rows of a field, without an n x n distance matrix
+ * and without any edge-sized (n x k x C) tensor.
+ *
+ * mink_knn: idx[i][0..k) = the global rows of the k rows of the SAME sample (batch_offsets int32 [B + 1], device, never read
+ *   by the host) nearest to row i of x[n][C] (row stride ldx floats) in squared Euclidean distance, row i included; ascending
+ *   distance, ties to the lower row.  The ranking score is ||x_j||^2 - 2 x_i.x_j in fp32 (inner products on the fp32 matrix
+ *   cores).  1 <= C <= MINK_KNN_MAX_C, 1 <= k <= MINK_KNN_MAX_K, samples of any size (empty ones included), n k < 2^31.  The
+ *   slots of a row whose sample holds fewer than k rows with a comparable (non-NaN) score are -1.
+ *
+ * Edge convolution.  With W = [W1 | W2] the reference's W [x_j - x_i ; x_i] is e[i][j] = P[idx[i][j]] + Q[i], P = X W1^T,
+ *   Q = X (W2 - W1)^T, both [n][C] (C = output channels, any C >= 1).  An idx outside [0, n) is clamped, never followed.
+ *   mink_edge_stats: per-channel (sum e, sum e^2) over the n k edges as double column partials [mink_edge_stats_rows(n)][2][C]
+ *     for mink_bn_stats_from_partials (row count n k).
+ *   mink_edge_fwd: y[i][c] = max_j lrelu_0.2(gamma (e - mean) invstd + beta), arg[i][c] = the lowest slot j attaining it.
+ *   mink_edge_bwd: with z^ / e^ at the arg slot, g = dy (z^ > 0 ? 1 : 0.2), dbeta = sum_i g, dgamma = sum_i g e^; training != 0:
+ *     de[i][j] = gamma invstd ([j = arg] g - dbeta / M - e^[i][j] dgamma / M), M = n k; else only the [j = arg] g term.  dQ[i] sums
+ *     de over the k edges leaving row i, dP[r] over the edges arriving at r: (members, seg) = the flat edge ids i k + j grouped
+ *     by idx, int32 [n k] / [n + 1], ascending inside a segment.  Fixed-order sums, no atomics: bitwise reproducible. */
+#define MINK_KNN_MAX_K 64
+#define MINK_KNN_MAX_C 256
+int mink_knn(const float *x, int64_t n, int64_t ldx, int32_t C, const int32_t *batch_offsets, int32_t B, int32_t k, int32_t *idx,
+             void *stream);
+int32_t mink_edge_stats_rows(int64_t n);
+int mink_edge_stats(const float *P, const float *Q, const int32_t *idx, int64_t n, int32_t k, int32_t C, double *partial,
+                    int64_t partial_bytes, void *stream);
+int mink_edge_fwd(const float *P, const float *Q, const int32_t *idx, int64_t n, int32_t k, int32_t C, const float *mean,
+                  const float *invstd, const float *gamma, const float *beta, float *y, uint8_t *arg, void *stream);
+int64_t mink_edge_bwd_workspace_bytes(int64_t n, int32_t C);
+int mink_edge_bwd(const float *dy, const float *P, const float *Q, const int32_t *idx, const uint8_t *arg, int64_t n, int32_t k,
+                  int32_t C, const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t training,
+                  const int32_t *members, const int32_t *seg, float *dP, float *dQ, float *dgamma, float *dbeta, void *workspace,
+                  int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -550,10 +550,17 @@ class CoordinateManager:
         self._sync_lazy()
         ent = self._field_boff
         if ent is None or ent[0] is not coords:
-            boff = _Fn().field_batch_offsets(coords, self._batch_size)
-            ent = self._field_boff = (coords, boff)
+            sizes = []
+            boff = _Fn().field_batch_offsets(coords, self._batch_size, sizes)
+            ent = self._field_boff = (coords, boff, sizes)
             self._note_lazy(boff)
         return ent[1]
+
+    def field_sample_sizes(self, coords):
+        """The rows of every batch sample of a TensorField, on the host: they came with the status word that
+        field_batch_offsets reads, so asking for them costs nothing more."""
+        self.field_batch_offsets(coords)
+        return self._field_boff[2]
 
     # ------------------------------------------------------------------ maps built on demand
     # A map requested for the first time is built on whatever stream asks for it.  With several

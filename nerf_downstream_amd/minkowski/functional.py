@@ -1721,17 +1721,21 @@ class FieldGatherCatFunction(torch.autograd.Function):
         return (None, *out)
 
 
-def field_batch_offsets(coords, B):
+def field_batch_offsets(coords, B, sizes=None):
     """int32 [B + 1] row ranges of the batch indices 0..B-1 in the batch column of a field's float rows coords[n, 4]
-    (mink_batch_offsets on the device); ValueError when the column is not non-decreasing (one read of the status word)."""
+    (mink_batch_offsets on the device); ValueError when the column is not non-decreasing (one read of the status word).
+    `sizes`: a list that receives the B per-sample row counts, which arrive with that same read."""
     n = coords.shape[0]
     rows = torch.zeros(n, 4, dtype=torch.int32, device=coords.device)
     rows[:, 0] = coords[:, 0].detach().to(torch.int32)
     out = torch.zeros(B + 2, dtype=torch.int32, device=coords.device)  # [offsets | status]
     check(lib().mink_batch_offsets(rows.data_ptr(), n, B, out.data_ptr(), out[B + 1:].data_ptr(), _stream()))
-    if int(out[B + 1].item()) & 2:  # MINK_STATUS_UNSORTED
+    host = out.tolist()
+    if host[B + 1] & 2:  # MINK_STATUS_UNSORTED
         raise ValueError("global pooling of a TensorField: batch indices must be non-decreasing (use ME.utils.sparse_collate); "
                          "the rows are not sorted for you")
+    if sizes is not None:
+        sizes[:] = [host[b + 1] - host[b] for b in range(B)]
     return out[: B + 1]
 
 
