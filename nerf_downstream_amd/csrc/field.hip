@@ -17,7 +17,7 @@
 //                      input row is written exactly once.
 #include <algorithm>
 
-#include "common.h"
+#include "rowpass.h"
 
 namespace mink {
 namespace {
@@ -33,23 +33,6 @@ struct CatSources {
   int32_t off[kMaxSrc + 1];  // first column of every source in y; off[n_src] = the width of y
 };
 
-template <int VEC>
-__device__ __forceinline__ void ldv(const float *__restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4 *>(p);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void stv(float *__restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4)
-    *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else
-    p[0] = v[0];
-}
-
 __global__ __launch_bounds__(FB) void field_map_kernel(const float4 *__restrict__ tfield, int64_t n, int ts,
                                                        const uint64_t *__restrict__ tkeys, const int32_t *__restrict__ tvals,
                                                        uint64_t mask, int64_t n_rows, int32_t *__restrict__ idx, uint32_t *status) {
@@ -57,7 +40,7 @@ __global__ __launch_bounds__(FB) void field_map_kernel(const float4 *__restrict_
   if (i >= n) return;
   const float4 q = tfield[i];
   int row = -1;
-  if (!(fabsf(q.x) < 65536.f && fabsf(q.y) < 65536.f && fabsf(q.z) < 65536.f && fabsf(q.w) < 65536.f)) {
+  if (!query_in_range(q)) {
     atomicOr(status, MINK_STATUS_RANGE);  // NaN / infinite / far outside the key space
   } else {
     const int b = (int)q.x;
@@ -129,9 +112,6 @@ __global__ __launch_bounds__(FB) void segment_mean_bwd_kernel(const float *__res
   }
 }
 
-inline unsigned field_grid(int64_t work) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(work, FB), 1 << 16)); }
-inline bool a16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 }  // namespace mink
 
@@ -146,7 +126,7 @@ int mink_field_map(const float *tfield, int64_t n, int32_t ts, const uint64_t *t
   MINK_REQUIRE(cap >= 64 && (cap & (cap - 1)) == 0, "field_map: table capacity %lld is not a power of two >= 64", (long long)cap);
   if (n == 0) return MINK_OK;
   MINK_REQUIRE(tfield && table_keys && table_vals && idx && status, "field_map: NULL pointer");
-  MINK_REQUIRE(a16(tfield), "field_map: tfield must be 16-byte aligned rows of 4");
+  MINK_REQUIRE(aligned16(tfield), "field_map: tfield must be 16-byte aligned rows of 4");
   field_map_kernel<<<dim3((unsigned)cdiv(n, FB)), FB, 0, (hipStream_t)stream>>>((const float4 *)tfield, n, ts, table_keys, table_vals,
                                                                               (uint64_t)cap - 1, n_rows, idx, status);
   MINK_CHECK_LAUNCH();
@@ -159,7 +139,7 @@ int mink_field_gather_cat(int32_t n_src, const float *const *x, const int32_t *l
   MINK_REQUIRE(n >= 0 && n <= 0x0fffffffLL && x && ldx && rows && C && idx, "field_gather_cat: bad arguments (n=%lld)", (long long)n);
   CatSources src;
   int64_t width = 0;
-  bool vec = a16(y) && (ldy & 3) == 0;
+  bool vec = aligned16(y) && (ldy & 3) == 0;
   for (int s = 0; s < kMaxSrc; ++s) {
     const int k = s < n_src ? s : 0;  // (unused slots repeat source 0: never selected, never NULL)
     MINK_REQUIRE(C[k] >= 1 && C[k] <= 4096 && ldx[k] >= C[k] && rows[k] >= 0 && rows[k] <= 0x0fffffffLL,
@@ -169,7 +149,7 @@ int mink_field_gather_cat(int32_t n_src, const float *const *x, const int32_t *l
     if (s < n_src) {
       src.off[s] = (int32_t)width;
       width += C[k];
-      vec = vec && (C[k] & 3) == 0 && (ldx[k] & 3) == 0 && a16(x[k]);
+      vec = vec && (C[k] & 3) == 0 && (ldx[k] & 3) == 0 && aligned16(x[k]);
     }
   }
   for (int s = n_src; s <= kMaxSrc; ++s) src.off[s] = (int32_t)width;
@@ -178,8 +158,8 @@ int mink_field_gather_cat(int32_t n_src, const float *const *x, const int32_t *l
   if (n == 0) return MINK_OK;
   MINK_REQUIRE(y, "field_gather_cat: NULL output");
   hipStream_t st = (hipStream_t)stream;
-  if (vec) field_gather_cat_kernel<4><<<dim3(field_grid(n * (width / 4))), FB, 0, st>>>(src, n_src, n, y, ldy);
-  else field_gather_cat_kernel<1><<<dim3(field_grid(n * width)), FB, 0, st>>>(src, n_src, n, y, ldy);
+  if (vec) field_gather_cat_kernel<4><<<dim3(flat_grid(n * (width / 4), FB, 1 << 16)), FB, 0, st>>>(src, n_src, n, y, ldy);
+  else field_gather_cat_kernel<1><<<dim3(flat_grid(n * width, FB, 1 << 16)), FB, 0, st>>>(src, n_src, n, y, ldy);
   MINK_CHECK_LAUNCH();
   return MINK_OK;
 }
@@ -194,12 +174,10 @@ int mink_segment_mean_bwd(const float *dy, int32_t ldy, int32_t C, const int32_t
   if (n_out == 0 || n_members == 0 || n_in == 0) return MINK_OK;
   MINK_REQUIRE(dy && members && seg && dx, "segment_mean_bwd: NULL pointer");
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = (C & 3) == 0 && (ldy & 3) == 0 && (lddx & 3) == 0 && a16(dy) && a16(dx);
-  if (vec)
-    segment_mean_bwd_kernel<4><<<dim3(field_grid(n_members * (C / 4))), FB, 0, st>>>(dy, ldy, C, members, seg, n_out, n_members, n_in, dx,
-                                                                                   lddx);
-  else
-    segment_mean_bwd_kernel<1><<<dim3(field_grid(n_members * C)), FB, 0, st>>>(dy, ldy, C, members, seg, n_out, n_members, n_in, dx, lddx);
+  const bool vec = (C & 3) == 0 && (ldy & 3) == 0 && (lddx & 3) == 0 && aligned16(dy) && aligned16(dx);
+  const dim3 grid(flat_grid(n_members * (vec ? C / 4 : C), FB, 1 << 16));
+  if (vec) segment_mean_bwd_kernel<4><<<grid, FB, 0, st>>>(dy, ldy, C, members, seg, n_out, n_members, n_in, dx, lddx);
+  else segment_mean_bwd_kernel<1><<<grid, FB, 0, st>>>(dy, ldy, C, members, seg, n_out, n_members, n_in, dx, lddx);
   MINK_CHECK_LAUNCH();
   return MINK_OK;
 }

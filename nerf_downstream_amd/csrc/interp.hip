@@ -20,7 +20,7 @@
 // pairs go to one wave each, longer ones to a whole workgroup in a second launch (each launch skips the other's rows).
 #include <algorithm>
 
-#include "common.h"
+#include "rowpass.h"
 
 namespace mink {
 namespace {
@@ -28,23 +28,6 @@ namespace {
 constexpr int IB = 256;          // threads per workgroup
 constexpr int kLongSeg = 256;    // pairs (four waves' worth); longer segments take a workgroup instead of a wave
 constexpr int kColLanes = 16;    // column groups a team reads side by side (the rest of the team are row lanes)
-
-template <int VEC>
-__device__ __forceinline__ void ldv(const float *__restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4 *>(p);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void stv(float *__restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4)
-    *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else
-    p[0] = v[0];
-}
 
 // one axis: cell origin (an integer, exact in fp32 for |x| < 65536) and the upper corner's factor
 __device__ __forceinline__ void cell_axis(float x, float ts, int &lo_i, float &d) {
@@ -57,7 +40,7 @@ __device__ __forceinline__ void cell_axis(float x, float ts, int &lo_i, float &d
 
 // query row -> batch index, corner coordinates and weight of corner c.  false: NaN / infinite / far outside the key space
 __device__ __forceinline__ bool query_corner(const float4 q, int ts, int c, int &b, int &cx, int &cy, int &cz, float &w) {
-  if (!(fabsf(q.x) < 65536.f && fabsf(q.y) < 65536.f && fabsf(q.z) < 65536.f && fabsf(q.w) < 65536.f)) return false;
+  if (!query_in_range(q)) return false;
   const float fts = (float)ts;
   float dx, dy, dz;
   cell_axis(q.y, fts, cx, dx);
@@ -196,19 +179,10 @@ __global__ __launch_bounds__(IB) void interp_segsum_kernel(const float *__restri
   }
 }
 
-inline unsigned interp_grid(int64_t work, int per_block) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(work, per_block), 1 << 16));
-}
-inline bool a16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 }  // namespace mink
 
 using namespace mink;
-
-#define INTERP_SHAPE(name, rows, C)                                                                                             \
-  MINK_REQUIRE((rows) >= 0 && (rows) <= 0x0fffffffLL && (C) >= 1 && (C) <= 4096, name ": bad shape (rows=%lld, C=%d; 1 <= C <= 4096)", \
-               (long long)(rows), (int)(C))
 
 extern "C" {
 
@@ -219,7 +193,7 @@ int mink_interp_map_weight(const float *tfield, int64_t n, int32_t ts, const uin
   MINK_REQUIRE(cap >= 64 && (cap & (cap - 1)) == 0, "interp_map_weight: table capacity %lld is not a power of two >= 64", (long long)cap);
   if (n == 0) return MINK_OK;
   MINK_REQUIRE(tfield && table_keys && table_vals && imap && w && status, "interp_map_weight: NULL pointer");
-  MINK_REQUIRE(a16(tfield), "interp_map_weight: tfield must be 16-byte aligned rows of 4");
+  MINK_REQUIRE(aligned16(tfield), "interp_map_weight: tfield must be 16-byte aligned rows of 4");
   interp_map_weight_kernel<<<dim3((unsigned)cdiv(8 * n, IB)), IB, 0, (hipStream_t)stream>>>(
       (const float4 *)tfield, n, ts, table_keys, table_vals, (uint64_t)cap - 1, n_rows, imap, w, status);
   MINK_CHECK_LAUNCH();
@@ -230,7 +204,7 @@ int mink_splat_coords(const float *tfield, int64_t n, int32_t *corners, float *w
   MINK_REQUIRE(n >= 0 && n <= 0x0fffffffLL, "splat_coords: bad row count %lld", (long long)n);
   if (n == 0) return MINK_OK;
   MINK_REQUIRE(tfield && corners && status, "splat_coords: NULL pointer");
-  MINK_REQUIRE(a16(tfield) && a16(corners), "splat_coords: tfield and corners must be 16-byte aligned rows of 4");
+  MINK_REQUIRE(aligned16(tfield) && aligned16(corners), "splat_coords: tfield and corners must be 16-byte aligned rows of 4");
   splat_coords_kernel<<<dim3((unsigned)cdiv(8 * n, IB)), IB, 0, (hipStream_t)stream>>>((const float4 *)tfield, n, (int4 *)corners, w,
                                                                                      status);
   MINK_CHECK_LAUNCH();
@@ -239,29 +213,29 @@ int mink_splat_coords(const float *tfield, int64_t n, int32_t *corners, float *w
 
 int mink_interp_gather(const float *x, int32_t ldx, int64_t n_x, int32_t C, const int32_t *imap, const float *w, int64_t n_q,
                        float *y, void *stream) {
-  INTERP_SHAPE("interp_gather", n_q, C);
+  MINK_REQUIRE_ROWS_C("interp_gather", n_q, 0x0fffffffLL, C);
   MINK_REQUIRE(ldx >= C && n_x >= 0, "interp_gather: bad arguments (ldx=%d, rows of x=%lld)", ldx, (long long)n_x);
   if (n_q == 0) return MINK_OK;
   MINK_REQUIRE(imap && w && y && (n_x == 0 || x), "interp_gather: NULL pointer");
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && a16(x) && a16(y);
-  if (vec) interp_gather_kernel<4><<<dim3(interp_grid(n_q * (C / 4), IB)), IB, 0, st>>>(x, ldx, n_x, C, imap, w, n_q, y);
-  else interp_gather_kernel<1><<<dim3(interp_grid(n_q * C, IB)), IB, 0, st>>>(x, ldx, n_x, C, imap, w, n_q, y);
+  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && aligned16(x) && aligned16(y);
+  if (vec) interp_gather_kernel<4><<<dim3(flat_grid(n_q * (C / 4), IB, 1 << 16)), IB, 0, st>>>(x, ldx, n_x, C, imap, w, n_q, y);
+  else interp_gather_kernel<1><<<dim3(flat_grid(n_q * C, IB, 1 << 16)), IB, 0, st>>>(x, ldx, n_x, C, imap, w, n_q, y);
   MINK_CHECK_LAUNCH();
   return MINK_OK;
 }
 
 int mink_interp_segsum(const float *dy, int32_t ldy, int64_t n_q, int32_t C, const float *w, const int32_t *members,
                        const int32_t *seg, int64_t n_rows, int64_t n_pairs, float *dx, void *stream) {
-  INTERP_SHAPE("interp_segsum", n_rows, C);
+  MINK_REQUIRE_ROWS_C("interp_segsum", n_rows, 0x0fffffffLL, C);
   MINK_REQUIRE(ldy >= C && n_q >= 0 && n_q <= 0x0fffffffLL && n_pairs >= 0 && n_pairs <= 8 * n_q,
                "interp_segsum: bad arguments (ldy=%d, queries=%lld, pairs=%lld)", ldy, (long long)n_q, (long long)n_pairs);
   if (n_rows == 0) return MINK_OK;
   MINK_REQUIRE(seg && dx && (n_pairs == 0 || (dy && w && members)), "interp_segsum: NULL pointer");
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = (C & 3) == 0 && (ldy & 3) == 0 && a16(dy) && a16(dx);
+  const bool vec = (C & 3) == 0 && (ldy & 3) == 0 && aligned16(dy) && aligned16(dx);
   const int tprb = std::min(vec ? C / 4 : C, kColLanes);
-  const dim3 gw(interp_grid(n_rows, IB / 64)), gl(interp_grid(n_rows, 8));
+  const dim3 gw(flat_grid(n_rows, IB / 64, 1 << 16)), gl(flat_grid(n_rows, 8, 1 << 16));
   if (vec) {
     interp_segsum_kernel<4, 64><<<gw, IB, 0, st>>>(dy, ldy, n_q, C, w, members, seg, n_rows, n_pairs, tprb, dx);
     MINK_CHECK_LAUNCH();

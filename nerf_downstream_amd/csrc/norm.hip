@@ -24,31 +24,13 @@
 // two runs are bitwise equal.
 #include <algorithm>
 
-#include "common.h"
+#include "rowpass.h"
 
 namespace mink {
 
 constexpr int NB = 256;            // threads per workgroup
-constexpr int kInMaxBlocks = 2048;  // B * G stays near this
 constexpr int kLnMaxC = 512;
 constexpr int kLnRedBlocks = 1024;  // workgroups (= partial rows) of the layer-norm backward
-
-template <int VEC>
-__device__ __forceinline__ void ldv(const float *__restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4 *>(p);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void stv(float *__restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4)
-    *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else
-    p[0] = v[0];
-}
 
 // Two column sums over `count` partial rows (`stride` doubles apart) by one wave: lane l adds rows l, l + 64, ... in order,
 // then a fixed butterfly; every lane returns the sums.
@@ -60,24 +42,6 @@ __device__ __forceinline__ void wave_sum2(const double *__restrict__ p0, const d
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64), b += __shfl_xor(b, o, 64);
   s = a, ss = b;
-}
-
-// rows [lo, hi) of sample b, clamped into [0, n] (offsets that do not describe x cannot send a load out of bounds)
-__device__ __forceinline__ void sample_range(const int *__restrict__ off, int b, int64_t n, int64_t &lo, int64_t &hi) {
-  lo = off[b], hi = off[b + 1];
-  lo = lo < 0 ? 0 : (lo > n ? n : lo);
-  hi = hi < lo ? lo : (hi > n ? n : hi);
-}
-
-// the sample that owns `row`: the largest b in [0, B) with off[b] <= row (an empty sample shares its offset with the next
-// one and is never the answer for a row inside it)
-__device__ __forceinline__ int sample_of(const int *__restrict__ off, int B, int64_t row) {
-  int lo = 0, hi = B;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if ((int64_t)off[mid] <= row) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 
 // ------------------------------------------------------------------------------------------------ instance norm
@@ -92,13 +56,7 @@ __global__ __launch_bounds__(NB) void in_reduce_kernel(const float *__restrict__
                                                        const float *__restrict__ invstd, double *__restrict__ partial) {
   extern __shared__ __align__(16) double s_red[];  // [rlanes][2][W]
   const int b = blockIdx.y, G = gridDim.x, g = blockIdx.x;
-  int64_t lo, hi;
-  sample_range(off, b, n, lo, hi);
-  const int64_t len = hi - lo;
-  const int64_t r0 = lo + len * g / G, r1 = lo + len * (g + 1) / G;
-  const int ncg = C / VEC, rlanes = NB / tprb, W = tprb * VEC;
-  const int cl = threadIdx.x % tprb, rl = threadIdx.x / tprb;
-  const int cg = blockIdx.z * tprb + cl;
+  const auto [r0, r1, ncg, rlanes, W, cl, rl, cg] = chunk_lane<VEC, NB>(off, n, C, tprb);
   double s0[VEC], s1[VEC];
 #pragma unroll
   for (int k = 0; k < VEC; ++k) s0[k] = 0.0, s1[k] = 0.0;
@@ -445,19 +403,12 @@ __global__ __launch_bounds__(NB) void ln_param_grad_kernel(const double *__restr
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline int in_chunks(int64_t n, int B) {
-  const int64_t cap = std::max<int64_t>(1, kInMaxBlocks / std::max(B, 1));
-  return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256), cap));
-}
-static inline unsigned flat_grid(int64_t work) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(work, NB), 4096)); }
-static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 struct InWorkspace {
   double *partial, *dsum;
   float *gmean, *gxmean;
 };
 static inline int64_t in_ws_layout(int64_t n, int C, int B, void *base, InWorkspace *w) {
-  const int64_t np = (int64_t)B * in_chunks(n, B) * 2 * C, nd = (int64_t)B * 2 * C, nf = (int64_t)B * C;
+  const int64_t np = (int64_t)B * sample_chunks(n, B) * 2 * C, nd = (int64_t)B * 2 * C, nf = (int64_t)B * C;
   if (w) {
     w->partial = (double *)base;
     w->dsum = w->partial + np;
@@ -470,10 +421,9 @@ static inline int64_t in_ws_layout(int64_t n, int C, int B, void *base, InWorksp
 template <int VEC, bool BWD>
 static void launch_in_reduce(const float *a, const float *x, const float *yr, const int *off, int64_t n, int C, int B,
                              const float *mean, const float *invstd, double *partial, hipStream_t st) {
-  const int ncg = C / VEC, tprb = std::min(ncg, NB), rlanes = NB / tprb;
-  const dim3 grid((unsigned)in_chunks(n, B), (unsigned)B, (unsigned)cdiv(ncg, tprb));
-  const size_t shm = (size_t)rlanes * 2 * tprb * VEC * sizeof(double);
-  in_reduce_kernel<VEC, BWD><<<grid, NB, shm, st>>>(a, x, yr, off, n, C, tprb, mean, invstd, partial);
+  const ChunkLaunch l(n, C, B, VEC, NB);
+  const size_t shm = (size_t)l.rlanes * 2 * l.W * sizeof(double);
+  in_reduce_kernel<VEC, BWD><<<l.grid, NB, shm, st>>>(a, x, yr, off, n, C, l.tprb, mean, invstd, partial);
 }
 
 static inline int ln_group(int ncg) {
@@ -499,9 +449,7 @@ int mink_in_fwd(const float *x, int64_t n, int32_t C, const int32_t *batch_offse
   MINK_REQUIRE(n >= 0 && n <= 0x7fffffffLL && C >= 1 && C <= 4096 && B >= 1 && B <= 65535, "in_fwd: bad shape (n=%lld, C=%d, B=%d)",
                (long long)n, C, B);
   MINK_REQUIRE(batch_offsets && gamma && beta && mean && invstd && workspace && (n == 0 || (x && y)), "in_fwd: NULL pointer");
-  MINK_REQUIRE(workspace_bytes >= mink_in_workspace_bytes(n, C, B) && ((uintptr_t)workspace & 7) == 0,
-               "in_fwd: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)workspace_bytes,
-               (long long)mink_in_workspace_bytes(n, C, B));
+  MINK_REQUIRE_WORKSPACE("in_fwd", workspace_bytes, mink_in_workspace_bytes(n, C, B), workspace);
   hipStream_t st = (hipStream_t)stream;
   InWorkspace w;
   in_ws_layout(n, C, B, workspace, &w);
@@ -512,14 +460,14 @@ int mink_in_fwd(const float *x, int64_t n, int32_t C, const int32_t *batch_offse
   else
     launch_in_reduce<1, false>(x, nullptr, nullptr, batch_offsets, n, C, B, nullptr, nullptr, w.partial, st);
   MINK_CHECK_LAUNCH();
-  in_finalize_kernel<false><<<dim3((unsigned)cdiv(C, 4), (unsigned)B), NB, 0, st>>>(w.partial, in_chunks(n, B), batch_offsets, n, C, eps,
+  in_finalize_kernel<false><<<dim3((unsigned)cdiv(C, 4), (unsigned)B), NB, 0, st>>>(w.partial, sample_chunks(n, B), batch_offsets, n, C, eps,
                                                                                  mean, invstd, nullptr);
   MINK_CHECK_LAUNCH();
   if (n == 0) return MINK_OK;
   if (vec)
-    in_apply_kernel<4><<<dim3(flat_grid(n * (C / 4))), NB, 0, st>>>(x, n, C, batch_offsets, B, mean, invstd, gamma, beta, residual, relu, y);
+    in_apply_kernel<4><<<dim3(flat_grid(n * (C / 4), NB, 4096)), NB, 0, st>>>(x, n, C, batch_offsets, B, mean, invstd, gamma, beta, residual, relu, y);
   else
-    in_apply_kernel<1><<<dim3(flat_grid(n * C)), NB, 0, st>>>(x, n, C, batch_offsets, B, mean, invstd, gamma, beta, residual, relu, y);
+    in_apply_kernel<1><<<dim3(flat_grid(n * C, NB, 4096)), NB, 0, st>>>(x, n, C, batch_offsets, B, mean, invstd, gamma, beta, residual, relu, y);
   MINK_CHECK_LAUNCH();
   return MINK_OK;
 }
@@ -532,9 +480,7 @@ int mink_in_bwd(const float *dy, const float *x, const float *y, int64_t n, int3
   MINK_REQUIRE(batch_offsets && gamma && mean && invstd && dgamma && dbeta && workspace && (n == 0 || (dy && x && dx)),
                "in_bwd: NULL pointer");
   MINK_REQUIRE(!relu || n == 0 || y, "in_bwd: fused ReLU needs the forward output");
-  MINK_REQUIRE(workspace_bytes >= mink_in_workspace_bytes(n, C, B) && ((uintptr_t)workspace & 7) == 0,
-               "in_bwd: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)workspace_bytes,
-               (long long)mink_in_workspace_bytes(n, C, B));
+  MINK_REQUIRE_WORKSPACE("in_bwd", workspace_bytes, mink_in_workspace_bytes(n, C, B), workspace);
   hipStream_t st = (hipStream_t)stream;
   InWorkspace w;
   in_ws_layout(n, C, B, workspace, &w);
@@ -547,17 +493,17 @@ int mink_in_bwd(const float *dy, const float *x, const float *y, int64_t n, int3
   else
     launch_in_reduce<1, true>(dy, x, yr, batch_offsets, n, C, B, mean, invstd, w.partial, st);
   MINK_CHECK_LAUNCH();
-  in_finalize_kernel<true><<<dim3((unsigned)cdiv(C, 4), (unsigned)B), NB, 0, st>>>(w.partial, in_chunks(n, B), batch_offsets, n, C, 0.f,
+  in_finalize_kernel<true><<<dim3((unsigned)cdiv(C, 4), (unsigned)B), NB, 0, st>>>(w.partial, sample_chunks(n, B), batch_offsets, n, C, 0.f,
                                                                                 w.gmean, w.gxmean, w.dsum);
   MINK_CHECK_LAUNCH();
   in_param_grad_kernel<<<dim3((unsigned)cdiv(C, NB)), NB, 0, st>>>(w.dsum, B, C, dgamma, dbeta);
   MINK_CHECK_LAUNCH();
   if (n == 0) return MINK_OK;
   if (vec && ws16)
-    in_bwd_apply_kernel<4><<<dim3(flat_grid(n * (C / 4))), NB, 0, st>>>(dy, x, yr, n, C, batch_offsets, B, mean, invstd, gamma, w.gmean,
+    in_bwd_apply_kernel<4><<<dim3(flat_grid(n * (C / 4), NB, 4096)), NB, 0, st>>>(dy, x, yr, n, C, batch_offsets, B, mean, invstd, gamma, w.gmean,
                                                                        w.gxmean, dx, dresidual);
   else
-    in_bwd_apply_kernel<1><<<dim3(flat_grid(n * C)), NB, 0, st>>>(dy, x, yr, n, C, batch_offsets, B, mean, invstd, gamma, w.gmean, w.gxmean,
+    in_bwd_apply_kernel<1><<<dim3(flat_grid(n * C, NB, 4096)), NB, 0, st>>>(dy, x, yr, n, C, batch_offsets, B, mean, invstd, gamma, w.gmean, w.gxmean,
                                                                  dx, dresidual);
   MINK_CHECK_LAUNCH();
   return MINK_OK;
@@ -599,9 +545,7 @@ int mink_ln_bwd(const float *dy, const float *x, const float *y, int64_t n, int3
                kLnMaxC);
   MINK_REQUIRE(gamma && dgamma && dbeta && workspace && (n == 0 || (dy && x && mean && invstd && dx)), "ln_bwd: NULL pointer");
   MINK_REQUIRE(!relu || n == 0 || y, "ln_bwd: fused ReLU needs the forward output");
-  MINK_REQUIRE(workspace_bytes >= mink_ln_workspace_bytes(n, C) && ((uintptr_t)workspace & 7) == 0,
-               "ln_bwd: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)workspace_bytes,
-               (long long)mink_ln_workspace_bytes(n, C));
+  MINK_REQUIRE_WORKSPACE("ln_bwd", workspace_bytes, mink_ln_workspace_bytes(n, C), workspace);
   hipStream_t st = (hipStream_t)stream;
   const float *yr = relu ? y : nullptr;
   const bool vec = (C & 3) == 0 && aligned16(dy) && aligned16(x) && aligned16(yr) && aligned16(dx) && aligned16(dresidual) && aligned16(gamma);

@@ -15,10 +15,10 @@
 //            with no present entry gets y = 0, arg = -1.  A NaN never replaces a number.
 //
 // Global pools.  Sample b owns rows [off[b], off[b+1]) (the manager's device-resident offsets; never read by the host).  The
-// launch shape is that of the instance norm (norm.hip): grid (G, B, channel slabs), every sample cut into the same number G
-// of row chunks chosen from n and B alone, one partial per workgroup, then one wave per (sample, channel) combines the G
-// partials -- lane l takes partials l, l + 64, ... in order, then a fixed butterfly.  Two launches forward, one backward,
-// whatever B is.  An empty sample finds an empty range: y = 0, arg = -1.
+// launch shape is the per-sample chunked reduction of rowpass.h: grid (G, B, channel slabs), every sample cut into the same
+// number G of row chunks chosen from n and B alone, one partial per workgroup, then one wave per (sample, channel) combines
+// the G partials -- lane l takes partials l, l + 64, ... in order, then a fixed butterfly.  Two launches forward, one
+// backward, whatever B is.  An empty sample finds an empty range: y = 0, arg = -1.
 //   max: the combine rule is a total order (larger value, then lower row), so arg[b][c] is the LOWEST row attaining the
 //        maximum however the rows were spread over threads.  Backward is one pass over the rows of dx that compares the row
 //        index with arg: dx[i][c] = arg[b][c] == i ? dy[b][c] : 0 -- no scatter.
@@ -26,46 +26,12 @@
 // Determinism: rows -> threads -> partials -> results is a fixed assignment in a fixed order: two runs are bitwise equal.
 #include <algorithm>
 
-#include "common.h"
+#include "rowpass.h"
 
 namespace mink {
 namespace {
 
-constexpr int PB = 256;               // threads per workgroup
-constexpr int kPoolMaxBlocks = 2048;  // B * G stays near this
-
-template <int VEC>
-__device__ __forceinline__ void ldf(const float *__restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4 *>(p);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void stf(float *__restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4)
-    *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else
-    p[0] = v[0];
-}
-template <int VEC>
-__device__ __forceinline__ void ldi(const int *__restrict__ p, int (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const int4 t = *reinterpret_cast<const int4 *>(p);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void sti(int *__restrict__ p, const int (&v)[VEC]) {
-  if constexpr (VEC == 4)
-    *reinterpret_cast<int4 *>(p) = make_int4(v[0], v[1], v[2], v[3]);
-  else
-    p[0] = v[0];
-}
+constexpr int PB = 256;  // threads per workgroup
 
 // ------------------------------------------------------------------------------------------------ local pools
 enum { kSum = 0, kAvg = 1 };
@@ -87,7 +53,7 @@ __global__ __launch_bounds__(PB) void pool_local_fwd_kernel(const float *__restr
       const int i = row[k];
       if (i >= 0) {
         float v[VEC];
-        ldf<VEC>(x + (int64_t)i * ldx + c, v);
+        ldv<VEC>(x + (int64_t)i * ldx + c, v);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) s[j] += v[j];
         ++m;
@@ -98,7 +64,7 @@ __global__ __launch_bounds__(PB) void pool_local_fwd_kernel(const float *__restr
 #pragma unroll
       for (int j = 0; j < VEC; ++j) s[j] = s[j] / d;
     }
-    stf<VEC>(y + o * C + c, s);
+    stv<VEC>(y + o * C + c, s);
     if (cnt && c == 0) cnt[o] = m;
   }
 }
@@ -120,7 +86,7 @@ __global__ __launch_bounds__(PB) void pool_local_bwd_kernel(const float *__restr
       const int o = row[k];
       if (o >= 0) {
         float g[VEC];
-        ldf<VEC>(dy + (int64_t)o * C + c, g);
+        ldv<VEC>(dy + (int64_t)o * C + c, g);
         if (MODE == kAvg) {
           const float d = (float)cnt[o];  // (>= 1: window o contains row i)
 #pragma unroll
@@ -130,7 +96,7 @@ __global__ __launch_bounds__(PB) void pool_local_bwd_kernel(const float *__restr
         for (int j = 0; j < VEC; ++j) s[j] += g[j];
       }
     }
-    stf<VEC>(dx + i * C + c, s);
+    stv<VEC>(dx + i * C + c, s);
   }
 }
 
@@ -152,14 +118,14 @@ __global__ __launch_bounds__(PB) void pool_local_max_fwd_kernel(const float *__r
       const int i = row[k];
       if (i >= 0) {
         float v[VEC];
-        ldf<VEC>(x + (int64_t)i * ldx + c, v);
+        ldv<VEC>(x + (int64_t)i * ldx + c, v);
 #pragma unroll
         for (int j = 0; j < VEC; ++j)
           if (a[j] < 0 || v[j] > m[j]) m[j] = v[j], a[j] = i;  // (the lowest k wins a tie)
       }
     }
-    stf<VEC>(y + o * C + c, m);
-    sti<VEC>(arg + o * C + c, a);
+    stv<VEC>(y + o * C + c, m);
+    stv<VEC>(arg + o * C + c, a);
   }
 }
 
@@ -181,34 +147,17 @@ __global__ __launch_bounds__(PB) void pool_local_max_bwd_kernel(const float *__r
       if (o >= 0) {
         float g[VEC];
         int a[VEC];
-        ldf<VEC>(dy + (int64_t)o * C + c, g);
-        ldi<VEC>(arg + (int64_t)o * C + c, a);
+        ldv<VEC>(dy + (int64_t)o * C + c, g);
+        ldv<VEC>(arg + (int64_t)o * C + c, a);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) s[j] += a[j] == (int)i ? g[j] : 0.f;
       }
     }
-    stf<VEC>(dx + i * C + c, s);
+    stv<VEC>(dx + i * C + c, s);
   }
 }
 
 // ------------------------------------------------------------------------------------------------ global pools
-// rows [lo, hi) of sample b, clamped into [0, n] (offsets that do not describe x cannot send a load out of bounds)
-__device__ __forceinline__ void pool_sample_range(const int *__restrict__ off, int b, int64_t n, int64_t &lo, int64_t &hi) {
-  lo = off[b], hi = off[b + 1];
-  lo = lo < 0 ? 0 : (lo > n ? n : lo);
-  hi = hi < lo ? lo : (hi > n ? n : hi);
-}
-
-// the sample that owns `row`: the largest b in [0, B) with off[b] <= row
-__device__ __forceinline__ int pool_sample_of(const int *__restrict__ off, int B, int64_t row) {
-  int lo = 0, hi = B;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if ((int64_t)off[mid] <= row) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // (m, a) <- the better of (m, a) and (v, r): a present candidate (r >= 0) beats an absent one, then the larger value, then
 // the lower row.  Symmetric, so both sides of a butterfly exchange end with the same pair.
 __device__ __forceinline__ void max_take(float &m, int &a, float v, int r) {
@@ -223,15 +172,9 @@ __global__ __launch_bounds__(PB) void gmax_partial_kernel(const float *__restric
                                                           int *__restrict__ parg) {
   extern __shared__ __align__(16) unsigned char s_raw[];  // [rlanes][W] float, then [rlanes][W] int
   const int b = blockIdx.y, G = gridDim.x, g = blockIdx.x;
-  int64_t lo, hi;
-  pool_sample_range(off, b, n, lo, hi);
-  const int64_t len = hi - lo;
-  const int64_t r0 = lo + len * g / G, r1 = lo + len * (g + 1) / G;
-  const int ncg = C / VEC, rlanes = PB / tprb, W = tprb * VEC;
+  const auto [r0, r1, ncg, rlanes, W, cl, rl, cg] = chunk_lane<VEC, PB>(off, n, C, tprb);
   float *s_val = reinterpret_cast<float *>(s_raw);
   int *s_arg = reinterpret_cast<int *>(s_raw) + rlanes * W;
-  const int cl = threadIdx.x % tprb, rl = threadIdx.x / tprb;
-  const int cg = blockIdx.z * tprb + cl;
   float m[VEC];
   int a[VEC];
 #pragma unroll
@@ -241,7 +184,7 @@ __global__ __launch_bounds__(PB) void gmax_partial_kernel(const float *__restric
 #pragma unroll 4
     for (int64_t row = r0 + rl; row < r1; row += rlanes) {
       float v[VEC];
-      ldf<VEC>(x + row * ldx + c, v);
+      ldv<VEC>(x + row * ldx + c, v);
 #pragma unroll
       for (int k = 0; k < VEC; ++k)
         if (a[k] < 0 || v[k] > m[k]) m[k] = v[k], a[k] = (int)row;
@@ -292,13 +235,7 @@ __global__ __launch_bounds__(PB) void gsum_partial_kernel(const float *__restric
   extern __shared__ __align__(16) unsigned char s_raw[];  // [rlanes][W] double
   double *s_red = reinterpret_cast<double *>(s_raw);
   const int b = blockIdx.y, G = gridDim.x, g = blockIdx.x;
-  int64_t lo, hi;
-  pool_sample_range(off, b, n, lo, hi);
-  const int64_t len = hi - lo;
-  const int64_t r0 = lo + len * g / G, r1 = lo + len * (g + 1) / G;
-  const int ncg = C / VEC, rlanes = PB / tprb, W = tprb * VEC;
-  const int cl = threadIdx.x % tprb, rl = threadIdx.x / tprb;
-  const int cg = blockIdx.z * tprb + cl;
+  const auto [r0, r1, ncg, rlanes, W, cl, rl, cg] = chunk_lane<VEC, PB>(off, n, C, tprb);
   double s[VEC];
 #pragma unroll
   for (int k = 0; k < VEC; ++k) s[k] = 0.0;
@@ -307,7 +244,7 @@ __global__ __launch_bounds__(PB) void gsum_partial_kernel(const float *__restric
 #pragma unroll 4
     for (int64_t row = r0 + rl; row < r1; row += rlanes) {
       float v[VEC];
-      ldf<VEC>(x + row * ldx + c, v);
+      ldv<VEC>(x + row * ldx + c, v);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) s[k] += (double)v[k];
     }
@@ -351,50 +288,38 @@ __global__ __launch_bounds__(PB) void gpool_bwd_kernel(const float *__restrict__
     const int64_t row = i / ncg;
     const int c = (int)(i - row * ncg) * VEC;
     if (row < lo || row >= hi) {
-      b = pool_sample_of(off, B, row);
+      b = sample_of(off, B, row);
       lo = off[b], hi = off[b + 1];
     }
     float g[VEC];
-    ldf<VEC>(dy + (int64_t)b * C + c, g);
+    ldv<VEC>(dy + (int64_t)b * C + c, g);
     if (MAX) {
       int a[VEC];
-      ldi<VEC>(arg + (int64_t)b * C + c, a);
+      ldv<VEC>(arg + (int64_t)b * C + c, a);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) g[k] = a[k] == (int)row ? g[k] : 0.f;
     }
-    stf<VEC>(dx + i * VEC, g);
+    stv<VEC>(dx + i * VEC, g);
   }
 }
-
-// ------------------------------------------------------------------------------------------------ host side
-inline int pool_chunks(int64_t n, int B) {
-  const int64_t cap = std::max<int64_t>(1, kPoolMaxBlocks / std::max(B, 1));
-  return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256), cap));
-}
-inline unsigned pool_grid(int64_t work) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(work, PB), 1 << 16)); }
-inline bool a16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 }  // namespace mink
 
 using namespace mink;
 
-#define POOL_SHAPE(name, rows, C)                                                                                      \
-  MINK_REQUIRE((rows) >= 0 && (rows) <= 0x7fffffffLL && (C) >= 1 && (C) <= 4096, name ": bad shape (rows=%lld, C=%d; 1 <= C <= 4096)", \
-               (long long)(rows), (int)(C))
-
 extern "C" {
 
 int mink_pool_local_fwd(const float *x, int32_t ldx, int32_t C, const int32_t *nbr, int64_t n_out, int32_t K, int32_t mode,
                         float *y, int32_t *cnt, void *stream) {
-  POOL_SHAPE("pool_local_fwd", n_out, C);
+  MINK_REQUIRE_ROWS_C("pool_local_fwd", n_out, 0x7fffffffLL, C);
   MINK_REQUIRE(K >= 1 && K <= 81 && ldx >= C && (mode == kSum || mode == kAvg), "pool_local_fwd: bad arguments (K=%d, ldx=%d, mode=%d)", K,
                ldx, mode);
   if (n_out == 0) return MINK_OK;
   MINK_REQUIRE(x && nbr && y && (mode == kSum || cnt), "pool_local_fwd: NULL pointer");
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && a16(x) && a16(y);
-  const unsigned grid = pool_grid(n_out * (vec ? C / 4 : C));
+  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && aligned16(x) && aligned16(y);
+  const unsigned grid = flat_grid(n_out * (vec ? C / 4 : C), PB, 1 << 16);
   if (mode == kAvg) {
     if (vec) pool_local_fwd_kernel<4, kAvg><<<dim3(grid), PB, 0, st>>>(x, ldx, C, nbr, n_out, K, y, cnt);
     else pool_local_fwd_kernel<1, kAvg><<<dim3(grid), PB, 0, st>>>(x, ldx, C, nbr, n_out, K, y, cnt);
@@ -408,13 +333,13 @@ int mink_pool_local_fwd(const float *x, int32_t ldx, int32_t C, const int32_t *n
 
 int mink_pool_local_bwd(const float *dy, int32_t C, const int32_t *nbr_t, int64_t n_in, int32_t K, int32_t mode,
                         const int32_t *cnt, float *dx, void *stream) {
-  POOL_SHAPE("pool_local_bwd", n_in, C);
+  MINK_REQUIRE_ROWS_C("pool_local_bwd", n_in, 0x7fffffffLL, C);
   MINK_REQUIRE(K >= 1 && K <= 81 && (mode == kSum || mode == kAvg), "pool_local_bwd: bad arguments (K=%d, mode=%d)", K, mode);
   if (n_in == 0) return MINK_OK;
   MINK_REQUIRE(dy && nbr_t && dx && (mode == kSum || cnt), "pool_local_bwd: NULL pointer");
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = (C & 3) == 0 && a16(dy) && a16(dx);
-  const unsigned grid = pool_grid(n_in * (vec ? C / 4 : C));
+  const bool vec = (C & 3) == 0 && aligned16(dy) && aligned16(dx);
+  const unsigned grid = flat_grid(n_in * (vec ? C / 4 : C), PB, 1 << 16);
   if (mode == kAvg) {
     if (vec) pool_local_bwd_kernel<4, kAvg><<<dim3(grid), PB, 0, st>>>(dy, C, nbr_t, n_in, K, cnt, dx);
     else pool_local_bwd_kernel<1, kAvg><<<dim3(grid), PB, 0, st>>>(dy, C, nbr_t, n_in, K, cnt, dx);
@@ -428,13 +353,13 @@ int mink_pool_local_bwd(const float *dy, int32_t C, const int32_t *nbr_t, int64_
 
 int mink_pool_local_max_fwd(const float *x, int32_t ldx, int32_t C, const int32_t *nbr, int64_t n_out, int32_t K, float *y,
                             int32_t *arg, void *stream) {
-  POOL_SHAPE("pool_local_max_fwd", n_out, C);
+  MINK_REQUIRE_ROWS_C("pool_local_max_fwd", n_out, 0x7fffffffLL, C);
   MINK_REQUIRE(K >= 1 && K <= 81 && ldx >= C, "pool_local_max_fwd: bad arguments (K=%d, ldx=%d)", K, ldx);
   if (n_out == 0) return MINK_OK;
   MINK_REQUIRE(x && nbr && y && arg, "pool_local_max_fwd: NULL pointer");
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && a16(x) && a16(y) && a16(arg);
-  const unsigned grid = pool_grid(n_out * (vec ? C / 4 : C));
+  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && aligned16(x) && aligned16(y) && aligned16(arg);
+  const unsigned grid = flat_grid(n_out * (vec ? C / 4 : C), PB, 1 << 16);
   if (vec) pool_local_max_fwd_kernel<4><<<dim3(grid), PB, 0, st>>>(x, ldx, C, nbr, n_out, K, y, arg);
   else pool_local_max_fwd_kernel<1><<<dim3(grid), PB, 0, st>>>(x, ldx, C, nbr, n_out, K, y, arg);
   MINK_CHECK_LAUNCH();
@@ -443,13 +368,13 @@ int mink_pool_local_max_fwd(const float *x, int32_t ldx, int32_t C, const int32_
 
 int mink_pool_local_max_bwd(const float *dy, const int32_t *arg, int32_t C, const int32_t *nbr_t, int64_t n_in, int32_t K,
                             float *dx, void *stream) {
-  POOL_SHAPE("pool_local_max_bwd", n_in, C);
+  MINK_REQUIRE_ROWS_C("pool_local_max_bwd", n_in, 0x7fffffffLL, C);
   MINK_REQUIRE(K >= 1 && K <= 81, "pool_local_max_bwd: bad arguments (K=%d)", K);
   if (n_in == 0) return MINK_OK;
   MINK_REQUIRE(dy && arg && nbr_t && dx, "pool_local_max_bwd: NULL pointer");
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = (C & 3) == 0 && a16(dy) && a16(arg) && a16(dx);
-  const unsigned grid = pool_grid(n_in * (vec ? C / 4 : C));
+  const bool vec = (C & 3) == 0 && aligned16(dy) && aligned16(arg) && aligned16(dx);
+  const unsigned grid = flat_grid(n_in * (vec ? C / 4 : C), PB, 1 << 16);
   if (vec) pool_local_max_bwd_kernel<4><<<dim3(grid), PB, 0, st>>>(dy, arg, C, nbr_t, n_in, K, dx);
   else pool_local_max_bwd_kernel<1><<<dim3(grid), PB, 0, st>>>(dy, arg, C, nbr_t, n_in, K, dx);
   MINK_CHECK_LAUNCH();
@@ -458,30 +383,27 @@ int mink_pool_local_max_bwd(const float *dy, const int32_t *arg, int32_t C, cons
 
 int64_t mink_global_pool_workspace_bytes(int64_t n, int32_t C, int32_t B) {
   if (n < 0 || C < 1 || B < 1) return 0;
-  return (int64_t)B * pool_chunks(n, B) * C * (int64_t)sizeof(double);  // max: (float, int32) per partial; sum: one double
+  return (int64_t)B * sample_chunks(n, B) * C * (int64_t)sizeof(double);  // max: (float, int32) per partial; sum: one double
 }
 
 #define GPOOL_ARGS(name)                                                                                                           \
-  POOL_SHAPE(name, n, C);                                                                                                          \
+  MINK_REQUIRE_ROWS_C(name, n, 0x7fffffffLL, C);                                                                                   \
   MINK_REQUIRE(B >= 1 && B <= 65535, name ": bad batch size %d (1 <= B <= 65535)", B)
 
 int mink_global_max_fwd(const float *x, int64_t n, int32_t ldx, int32_t C, const int32_t *batch_offsets, int32_t B, float *y,
                         int32_t *arg, void *workspace, int64_t workspace_bytes, void *stream) {
   GPOOL_ARGS("global_max_fwd");
   MINK_REQUIRE(ldx >= C && batch_offsets && y && arg && workspace && (n == 0 || x), "global_max_fwd: NULL pointer or ldx < C");
-  MINK_REQUIRE(workspace_bytes >= mink_global_pool_workspace_bytes(n, C, B) && ((uintptr_t)workspace & 7) == 0,
-               "global_max_fwd: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)workspace_bytes,
-               (long long)mink_global_pool_workspace_bytes(n, C, B));
+  MINK_REQUIRE_WORKSPACE("global_max_fwd", workspace_bytes, mink_global_pool_workspace_bytes(n, C, B), workspace);
   hipStream_t st = (hipStream_t)stream;
-  const int G = pool_chunks(n, B);
+  const int G = sample_chunks(n, B);
   float *pval = (float *)workspace;
   int *parg = (int *)(pval + (int64_t)B * G * C);
-  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && a16(x);
-  const int VEC = vec ? 4 : 1, ncg = C / VEC, tprb = std::min(ncg, PB), rlanes = PB / tprb;
-  const dim3 grid((unsigned)G, (unsigned)B, (unsigned)cdiv(ncg, tprb));
-  const size_t shm = (size_t)rlanes * tprb * VEC * (sizeof(float) + sizeof(int));
-  if (vec) gmax_partial_kernel<4><<<grid, PB, shm, st>>>(x, ldx, batch_offsets, n, C, tprb, pval, parg);
-  else gmax_partial_kernel<1><<<grid, PB, shm, st>>>(x, ldx, batch_offsets, n, C, tprb, pval, parg);
+  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && aligned16(x);
+  const ChunkLaunch l(n, C, B, vec ? 4 : 1, PB);
+  const size_t shm = (size_t)l.rlanes * l.W * (sizeof(float) + sizeof(int));
+  if (vec) gmax_partial_kernel<4><<<l.grid, PB, shm, st>>>(x, ldx, batch_offsets, n, C, l.tprb, pval, parg);
+  else gmax_partial_kernel<1><<<l.grid, PB, shm, st>>>(x, ldx, batch_offsets, n, C, l.tprb, pval, parg);
   MINK_CHECK_LAUNCH();
   gmax_finalize_kernel<<<dim3((unsigned)cdiv(C, 4), (unsigned)B), PB, 0, st>>>(pval, parg, G, C, y, arg);
   MINK_CHECK_LAUNCH();
@@ -494,9 +416,9 @@ int mink_global_max_bwd(const float *dy, const int32_t *arg, int64_t n, int32_t 
   if (n == 0) return MINK_OK;
   MINK_REQUIRE(dy && arg && batch_offsets && dx, "global_max_bwd: NULL pointer");
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = (C & 3) == 0 && a16(dy) && a16(arg) && a16(dx);
-  if (vec) gpool_bwd_kernel<4, true><<<dim3(pool_grid(n * (C / 4))), PB, 0, st>>>(dy, arg, n, C, batch_offsets, B, dx);
-  else gpool_bwd_kernel<1, true><<<dim3(pool_grid(n * C)), PB, 0, st>>>(dy, arg, n, C, batch_offsets, B, dx);
+  const bool vec = (C & 3) == 0 && aligned16(dy) && aligned16(arg) && aligned16(dx);
+  if (vec) gpool_bwd_kernel<4, true><<<dim3(flat_grid(n * (C / 4), PB, 1 << 16)), PB, 0, st>>>(dy, arg, n, C, batch_offsets, B, dx);
+  else gpool_bwd_kernel<1, true><<<dim3(flat_grid(n * C, PB, 1 << 16)), PB, 0, st>>>(dy, arg, n, C, batch_offsets, B, dx);
   MINK_CHECK_LAUNCH();
   return MINK_OK;
 }
@@ -505,17 +427,14 @@ int mink_global_sum_fwd(const float *x, int64_t n, int32_t ldx, int32_t C, const
                         void *workspace, int64_t workspace_bytes, void *stream) {
   GPOOL_ARGS("global_sum_fwd");
   MINK_REQUIRE(ldx >= C && batch_offsets && y && workspace && (n == 0 || x), "global_sum_fwd: NULL pointer or ldx < C");
-  MINK_REQUIRE(workspace_bytes >= mink_global_pool_workspace_bytes(n, C, B) && ((uintptr_t)workspace & 7) == 0,
-               "global_sum_fwd: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)workspace_bytes,
-               (long long)mink_global_pool_workspace_bytes(n, C, B));
+  MINK_REQUIRE_WORKSPACE("global_sum_fwd", workspace_bytes, mink_global_pool_workspace_bytes(n, C, B), workspace);
   hipStream_t st = (hipStream_t)stream;
-  const int G = pool_chunks(n, B);
-  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && a16(x);
-  const int VEC = vec ? 4 : 1, ncg = C / VEC, tprb = std::min(ncg, PB), rlanes = PB / tprb;
-  const dim3 grid((unsigned)G, (unsigned)B, (unsigned)cdiv(ncg, tprb));
-  const size_t shm = (size_t)rlanes * tprb * VEC * sizeof(double);
-  if (vec) gsum_partial_kernel<4><<<grid, PB, shm, st>>>(x, ldx, batch_offsets, n, C, tprb, (double *)workspace);
-  else gsum_partial_kernel<1><<<grid, PB, shm, st>>>(x, ldx, batch_offsets, n, C, tprb, (double *)workspace);
+  const int G = sample_chunks(n, B);
+  const bool vec = (C & 3) == 0 && (ldx & 3) == 0 && aligned16(x);
+  const ChunkLaunch l(n, C, B, vec ? 4 : 1, PB);
+  const size_t shm = (size_t)l.rlanes * l.W * sizeof(double);
+  if (vec) gsum_partial_kernel<4><<<l.grid, PB, shm, st>>>(x, ldx, batch_offsets, n, C, l.tprb, (double *)workspace);
+  else gsum_partial_kernel<1><<<l.grid, PB, shm, st>>>(x, ldx, batch_offsets, n, C, l.tprb, (double *)workspace);
   MINK_CHECK_LAUNCH();
   gsum_finalize_kernel<<<dim3((unsigned)cdiv(C, 4), (unsigned)B), PB, 0, st>>>((const double *)workspace, G, C, y);
   MINK_CHECK_LAUNCH();
@@ -527,9 +446,9 @@ int mink_global_sum_bwd(const float *dy, int64_t n, int32_t C, const int32_t *ba
   if (n == 0) return MINK_OK;
   MINK_REQUIRE(dy && batch_offsets && dx, "global_sum_bwd: NULL pointer");
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = (C & 3) == 0 && a16(dy) && a16(dx);
-  if (vec) gpool_bwd_kernel<4, false><<<dim3(pool_grid(n * (C / 4))), PB, 0, st>>>(dy, nullptr, n, C, batch_offsets, B, dx);
-  else gpool_bwd_kernel<1, false><<<dim3(pool_grid(n * C)), PB, 0, st>>>(dy, nullptr, n, C, batch_offsets, B, dx);
+  const bool vec = (C & 3) == 0 && aligned16(dy) && aligned16(dx);
+  if (vec) gpool_bwd_kernel<4, false><<<dim3(flat_grid(n * (C / 4), PB, 1 << 16)), PB, 0, st>>>(dy, nullptr, n, C, batch_offsets, B, dx);
+  else gpool_bwd_kernel<1, false><<<dim3(flat_grid(n * C, PB, 1 << 16)), PB, 0, st>>>(dy, nullptr, n, C, batch_offsets, B, dx);
   MINK_CHECK_LAUNCH();
   return MINK_OK;
 }

@@ -31,6 +31,21 @@ def batch_scenes(seeds, **kw):
     return torch.from_numpy(np.concatenate(cs)), torch.from_numpy(np.concatenate(fs))
 
 
+def misaligned(x, requires_grad=False):
+    """x [n, C] on the device as a contiguous view that starts 4 bytes into a flat buffer -> (flat leaf, view): C % 4 == 0
+    no longer suffices for the 16-byte lanes, so the kernels must take their dword form.  The view is
+    flat[1:1 + n * C].view(n, C); with `requires_grad` its gradient arrives in flat.grad at the same place."""
+    import torch
+
+    n, C = x.shape
+    flat = torch.zeros(n * C + 4, dtype=x.dtype, device="cuda")
+    flat[1:1 + n * C] = x.reshape(-1).cuda()
+    flat.requires_grad_(requires_grad)
+    view = flat[1:1 + n * C].view(n, C)
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4
+    return flat, view
+
+
 def trunk_node(out):
     """The native-trunk autograd node (minkowski/trunk.py: TrunkFunction) in the graph of `out`, or None when the forward
     pass went module by module.  (`model._trunk_plan` only says the model COULD take the native trunk: a stem too small for

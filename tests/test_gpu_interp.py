@@ -22,6 +22,7 @@ import torch
 
 import interp_restate as IR
 import pool_restate as PR
+from helpers import misaligned
 
 pytestmark = pytest.mark.gpu
 
@@ -167,6 +168,33 @@ def test_interpolation_forward_and_backward(case, C):
         assert bool((y.detach().cpu()[absent] == 0).all()), what  # an all-absent query row is exactly zero
         untouched = torch.bincount(rimap[rimap >= 0], minlength=n) == 0
         assert bool((xd.grad.cpu()[untouched] == 0).all()), what
+
+
+def test_misaligned_rows_take_the_dword_kernels():
+    """C % 4 == 0 but x (the gather) and dy (the segmented sum) start 4 bytes off a 16-byte boundary: both must run their
+    dword form.  Bounds of test_interpolation_forward_and_backward."""
+    from nerf_downstream_amd import minkowski as ME
+    from nerf_downstream_amd.minkowski import functional as Fn
+
+    case, C = "B4", 32
+    q = _queries(case)
+    dy = _randn(q.shape[0], C, 250)
+    for ts in STRIDES:
+        n = _level_coords(case, ts).shape[0]
+        x = _randn(n, C, 150 + ts)
+        rimap, rw = _ref_map(case, ts)
+        imap, w = _manager(case).interpolation_map_weight(ME.CoordinateMapKey(ts), q.cuda())
+        flat, xv = misaligned(x, requires_grad=True)
+        _, dyv = misaligned(dy)
+        assert xv.data_ptr() % 16 == 4 and dyv.data_ptr() % 16 == 4
+        y = Fn.InterpolationFunction.apply(xv, imap, w, Fn.lazy_csr(imap, n))
+        seen = []
+        y.register_hook(lambda g: seen.append(g.data_ptr()))
+        y.backward(dyv)
+        assert seen == [dyv.data_ptr()]  # the segmented sum was handed the misaligned rows themselves
+        what = f"misaligned {case} C={C} ts={ts}"
+        _within(y.detach().cpu(), IR.interp_fwd(x, rimap, rw), _fwd_bound(x, rimap), what + " y")
+        _within(flat.grad[1:1 + n * C].view(n, C).cpu(), IR.interp_bwd(dy, rimap, rw, n), _bwd_bound(dy, rimap, n), what + " dx")
 
 
 def test_interpolate_and_the_module_take_the_same_path():

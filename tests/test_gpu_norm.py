@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 import norm_restate as NR
-from helpers import batch_scenes, trunk_node
+from helpers import batch_scenes, misaligned, trunk_node
 
 pytestmark = pytest.mark.gpu
 
@@ -229,6 +229,38 @@ def test_layer_norm_non_centred_within_what_fp32_inputs_allow(n, C):
             "dbeta": (dbe.double() - rdbe).abs()}
     ratios = _report(f"layer norm n={n} C={C}", errs, {"y": NR.forward_bound(x, invstd, gamma, y_ref), "dx": bx, "dgamma": bga, "dbeta": bbe})
     assert max(ratios.values()) <= BOUND_FACTOR, ratios
+
+
+# ------------------------------------------------------------------------------------------------ alignment fallback
+def test_misaligned_input_takes_the_dword_kernels():
+    """C % 4 == 0 but x starts 4 bytes off a 16-byte boundary: instance norm and layer norm, forward and backward, must run
+    their dword kernels.  The restatements and tolerances of the two *_function_matches_float64 tests above."""
+    from nerf_downstream_amd.minkowski import functional as Fn
+
+    off, C = _offsets(SIZES), 24
+    n = off[-1]
+    x, dy, res, gamma, beta = _inputs(n, C, 15)
+    offd = torch.tensor(off, dtype=torch.int32, device="cuda")
+    for relu, residual in VARIANTS:
+        r = res if residual else None
+        for kind in ("IN", "LN"):
+            flat, xv = misaligned(x, requires_grad=True)
+            ga, be = (t.clone().cuda().requires_grad_(True) for t in (gamma, beta))
+            rd = res.clone().cuda().requires_grad_(True) if residual else None
+            assert xv.data_ptr() % 16 == 4
+            if kind == "IN":
+                eps = 1e-8
+                y = Fn.InstanceNormFunction.apply(xv, ga, be, offd, eps, rd, relu)
+                z = NR.instance_norm_fwd(x, off, gamma, beta, eps, r, False)
+                bwd = lambda mask: NR.instance_norm_bwd(dy, x, off, gamma, beta, eps, r, relu, mask)  # noqa: E731
+            else:
+                eps = 1e-5
+                y = Fn.LayerNormFunction.apply(xv, ga, be, eps, rd, relu)
+                z = NR.layer_norm_fwd(x, gamma, beta, eps, r, False)
+                bwd = lambda mask: NR.layer_norm_bwd(dy, x, gamma, beta, eps, r, relu, mask)  # noqa: E731
+            y.backward(dy.cuda())
+            got = [y.detach().cpu(), flat.grad[1:1 + n * C].view(n, C).cpu(), ga.grad.cpu(), be.grad.cpu(), rd.grad.cpu() if residual else None]
+            _check_centred(got, z.clamp_min(0) if relu else z, bwd, z, relu, residual, f"misaligned {kind} relu={relu} res={residual}")
 
 
 # ------------------------------------------------------------------------------------------------ reproducibility

@@ -14,6 +14,7 @@ import torch
 
 import point_restate as PT
 import pool_restate as PR
+from helpers import misaligned
 
 pytestmark = pytest.mark.gpu
 
@@ -134,6 +135,41 @@ def test_fused_cat_of_slices_equals_torch_cat():
     st = ME.SparseTensor(torch.zeros(m.get_coordinates(ME.CoordinateMapKey(1)).shape[0], 4).cuda(), ME.CoordinateMapKey(1), m)
     with pytest.raises(ValueError, match="mixed"):
         ME.cat(st, tf)
+
+
+def test_misaligned_rows_take_the_dword_kernels():
+    """Widths that are multiples of 4 but rows that start 4 bytes off a 16-byte boundary: one source of the fused cat, and
+    the dy of the .sparse() backward.  Bitwise torch.cat of the slices; one rounding of the division."""
+    from nerf_downstream_amd.minkowski import functional as Fn
+
+    ME, tf, m = _field()
+    coords, C = _case()[0], 8
+    maps, xs = [], []
+    for ts in (2, 8):
+        key = ME.CoordinateMapKey(ts)
+        maps.append(m.field_map(key, tf.C))
+        xs.append(_randn(m.get_coordinates(key).shape[0], C, 600 + ts))
+    _, xv = misaligned(xs[1])
+    assert xv.data_ptr() % 16 == 4
+    y = Fn.FieldGatherCatFunction.apply(maps, xs[0].cuda(), xv)
+    assert torch.equal(y.cpu(), torch.cat([x[idx.cpu().long()] for x, (idx, _) in zip(xs, maps)], 1))
+    # .sparse() of learned features, as test_sparse_backward_of_learned_features, with the gradient rows misaligned
+    vox, inv = PT.quantise(coords)
+    leaf = _randn(coords.shape[0], C, 620).cuda().requires_grad_(True)
+    st = ME.TensorField(coordinates=coords.cuda(), features=leaf).sparse()
+    assert type(st.F.grad_fn).__name__ == "SegmentMeanFunctionBackward"
+    order = PT.field_map(st.C.cpu().float(), vox, 1)
+    dy = _randn(vox.shape[0], C, 621)
+    _, dyv = misaligned(dy)
+    seen = []
+    st.F.register_hook(lambda g: seen.append(g.data_ptr()))
+    assert dyv.data_ptr() % 16 == 4
+    st.F.backward(dyv)
+    assert seen == [dyv.data_ptr()]  # mink_segment_mean_bwd was handed the misaligned rows themselves
+    dy_ref = torch.zeros(vox.shape[0], C, dtype=torch.float64)
+    dy_ref[order] = dy.double()
+    ref = PT.mean_bwd(dy_ref, inv, vox.shape[0])
+    assert bool(((leaf.grad.cpu().double() - ref).abs() <= 2.0 ** -23 * ref.abs()).all())  # one rounding of the division
 
 
 # ------------------------------------------------------------------------------------------------ 3. .sparse() backward

@@ -17,6 +17,7 @@ import torch
 
 import layerwise as LW
 import pool_restate as PR
+from helpers import misaligned
 
 pytestmark = pytest.mark.gpu
 
@@ -185,6 +186,44 @@ def test_global_max_and_sum_pooling(case, C):
     ref = PR.global_sum_fwd(x, off)
     _within(y, ref, EPS * ref.abs() + TINY, f"global sum {case} C={C} y")
     assert torch.equal(dx.double(), PR.global_sum_bwd(dy, off)), f"global sum {case} C={C} dx"
+
+
+# ------------------------------------------------------------------------------------------------ alignment fallback
+def test_misaligned_features_take_the_dword_kernels():
+    """C % 4 == 0 but x starts 4 bytes off a 16-byte boundary: the host side must launch the dword form of every kernel that
+    reads x (a 16-byte access there faults or reads shifted columns).  Restatements and bounds of the aligned tests above."""
+    Fn = _fns()
+    case, C, (k, s) = "B4", 8, (3, 2)
+    off, boff = _offsets(case), _boff(case)
+    n, B = off[-1], len(off) - 1
+    _, _, nbr, nbr_t = _tables(case, k, s)
+    _, table = _ref_maps(case, k, s)
+    x, dy, dyb = _randn(n, C, 1400), _randn(table.shape[0], C, 1401), _randn(B, C, 1402)
+
+    def run(fn, g, *args):
+        flat, xv = misaligned(x, requires_grad=True)
+        assert xv.data_ptr() % 16 == 4
+        out = fn.apply(xv, *args)
+        y, aux = out if isinstance(out, tuple) else (out, None)
+        y.backward(g.cuda())
+        return y.detach().cpu(), None if aux is None else aux.cpu(), flat.grad[1:1 + n * C].view(n, C).cpu()
+
+    y, arg, dx = run(Fn.SparseMaxPoolFunction, dy, nbr, nbr_t)
+    ry, rarg = PR.max_fwd(x, table)
+    assert torch.equal(y.double(), ry) and torch.equal(arg.long(), rarg)
+    _within(dx, PR.max_bwd(dy, rarg, table, n), K * EPS * PR.max_bwd_abs(dy, rarg, table, n), "misaligned max dx")
+    y, cnt, dx = run(Fn.AvgPoolFunction, dy, nbr, nbr_t)
+    assert torch.equal(cnt.long(), PR.counts(table))
+    _within(y, PR.avg_fwd(x, table), (K + 1) * EPS * PR.sum_fwd_abs(x, table, True), "misaligned avg y")
+    _within(dx, PR.avg_bwd(dy, table, n), (K + 1) * EPS * PR.sum_bwd_abs(dy, table, n, True), "misaligned avg dx")
+    y, arg, dx = run(Fn.GlobalMaxPoolFunction, dyb, boff)
+    ry, rarg = PR.global_max_fwd(x, off)
+    assert torch.equal(y.double(), ry) and torch.equal(arg.long(), rarg)
+    assert torch.equal(dx.double(), PR.global_max_bwd(dyb, rarg, n))
+    y, _, dx = run(Fn.GlobalSumPoolFunction, dyb, boff)
+    ref = PR.global_sum_fwd(x, off)
+    _within(y, ref, EPS * ref.abs() + TINY, "misaligned global sum y")
+    assert torch.equal(dx.double(), PR.global_sum_bwd(dyb, off))
 
 
 # ------------------------------------------------------------------------------------------------ ties
