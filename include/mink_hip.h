@@ -1086,6 +1086,37 @@ int mink_edge_bwd(const float *dy, const float *P, const float *Q, const int32_t
                   const int32_t *members, const int32_t *seg, float *dP, float *dQ, float *dgamma, float *dbeta, void *workspace,
                   int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ PAConv (csrc/paconv.hip)
+ * Score-weighted neighbour aggregation (reference co3d_3d/src/models/paconv: feat_trans_dgcnn / feat_trans_pointnet followed
+ * by assign_score_withk / assign_score_withk_halfkernel, aggregate = sum) with the neighbour sum taken in INPUT space:
+ *     A[i][m][:] = sum_j s[i][j][m] x[idx[i][j]][:]     S[i][m] = sum_j s[i][j][m]     CX[i][m][:] = S[i][m] x[i][:]
+ *     y[i][:]    = sum_m (A[i][m][:] Wn_m - CX[i][m][:] Wc_m)           one dense GEMM of [A | CX] with [Wn ; -Wc], the caller's
+ * with Wn_m = K1_m + K2_m, Wc_m = K1_m (DGCNN flavour, weight bank [2 Cin][M][O] = [K1 ; K2]) or Wn_m = 2 K_m, Wc_m = K_m
+ * (PointNet flavour, bank [Cin][M][O]).  No [n][M][O] and no [n][k][.][O] tensor is formed, forward or backward.
+ *
+ * Layouts: x[n][Cin] contiguous; idx int32 [n][k] of global rows (as mink_knn writes them); s[n][k][M]; A, CX, dA, dCX are
+ * [n][M][Cin] with a common row pitch of ldz floats (>= M Cin: the two halves of one [n][2][M][Cin] buffer have ldz = 2 M Cin);
+ * S[n][M]; ds[n][k][M]; dx[n][Cin].  1 <= M <= MINK_PACONV_MAX_M, 1 <= k <= MINK_KNN_MAX_K, any Cin >= 1, n k < 2^31.  A slot
+ * whose idx lies outside [0, n) contributes nothing to A or S, is never followed, and gets ds = 0.  16-byte accesses where
+ * Cin % 4 == 0, ldz % 4 == 0 and the pointers are 16-byte aligned (scores: M % 4 == 0), dwords otherwise.
+ *
+ *   mink_paconv_gather: A, and where the pointers are given S and CX, in one pass.  A group of G lanes (the power of two in
+ *     4..64 covering Cin / VEC) owns a row and a chunk of G VEC channels and holds M accumulators per channel; the k slots
+ *     are walked in ascending order as an fp32 fma chain, S by plain additions in the same order.
+ *   mink_paconv_score_bwd: with dA = g Wn^T and dCX = -g Wc^T (the gradients of the GEMM's two operands),
+ *     ds[i][j][m] = sum_c (dA[i][m][c] x[idx[i][j]][c] + dCX[i][m][c] x[i][c]), c ascending, one lane per slot.
+ *   mink_paconv_scatter_bwd: dx[r][:] = sum_{e in list(r)} sum_m s[e][m] dA[e / k][m][:] + sum_m S[r][m] dCX[r][m][:], where
+ *     (members, seg) = the flat slot ids e = i k + j grouped by idx[e], int32 [n k] / [n + 1], ascending inside a segment (slots
+ *     outside [0, n) behind the last segment): edges ascending, m ascending, then the centre term.
+ * Fixed-order sums, no atomics: two runs give the same bits. */
+#define MINK_PACONV_MAX_M 16
+int mink_paconv_gather(const float *x, const float *s, const int32_t *idx, int64_t n, int32_t k, int32_t M, int32_t Cin, float *A,
+                       float *CX, int64_t ldz, float *S, void *stream);
+int mink_paconv_score_bwd(const float *dA, const float *dCX, int64_t ldz, const float *x, const int32_t *idx, int64_t n, int32_t k,
+                          int32_t M, int32_t Cin, float *ds, void *stream);
+int mink_paconv_scatter_bwd(const float *dA, const float *dCX, int64_t ldz, const float *s, const float *S, const int32_t *members,
+                            const int32_t *seg, int64_t n, int32_t k, int32_t M, int32_t Cin, float *dx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -252,6 +252,9 @@ SIGNATURES = {
         ctypes.c_int,
         [_p, _p, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _p],
     ),
+    "mink_paconv_gather": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _i64, _p, _p]),
+    "mink_paconv_score_bwd": (ctypes.c_int, [_p, _p, _i64, _p, _p, _i64, _i32, _i32, _i32, _p, _p]),
+    "mink_paconv_scatter_bwd": (ctypes.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _p]),
 }
 
 

@@ -7,11 +7,12 @@ from .mink.resnet import ResNet14, ResNet18, ResNet34, ResNet50, ResNet101
 from .mink import res16unet as _unet
 from .mink.dgcnn import DGCNN_cls
 from .mink.fcnn import MinkowskiFCNN, MinkowskiSplatFCNN
+from .mink.paconv import PAConvDGCNN, PAConvPointNet
 from .mink.pointnet import MinkowskiPointNet
 
 MODELS = {c.__name__: c for c in (ResNet14, ResNet18, ResNet34, ResNet50, ResNet101)}
 MODELS.update({n: c for n, c in vars(_unet).items() if n.startswith("Res16UNet") and isinstance(c, type)})
-MODELS.update({c.__name__: c for c in (MinkowskiFCNN, MinkowskiSplatFCNN, MinkowskiPointNet, DGCNN_cls)})  # point-based classifiers
+MODELS.update({c.__name__: c for c in (MinkowskiFCNN, MinkowskiSplatFCNN, MinkowskiPointNet, DGCNN_cls, PAConvPointNet, PAConvDGCNN)})  # point-based classifiers
 
 
 @gin.configurable
