@@ -139,7 +139,7 @@ def _stem_masks_of_hip_run(out, model):
     the batch's (mean, 1 / std) -- and the two kernels that do so round xhat differently (both are valid fp32):
       * gamma / beta gradients (csrc/elementwise.hip, colreduce / bn_relu_pool_bwd_kernel; also the forward's own
         decision):                      xhat = fl(fl(y - mean) * invstd),        z = fma(xhat, gamma, beta)
-      * the weight gradient (csrc/conv.hip, wgrad_stream_kernel<.., FUSE>): xhat = fma(y, invstd, fl(-mean * invstd)), z = fma(xhat, gamma, beta)
+      * the weight gradient (csrc/conv_wgrad.hip, wgrad_stream_kernel<.., FUSE>): xhat = fma(y, invstd, fl(-mean * invstd)), z = fma(xhat, gamma, beta)
     Both are reproduced here in exact fp32 arithmetic on the CPU (an fma through float64: the product of two floats is exact
     there).  -> (mask for bn1.*, mask for conv1.kernel), each [n0, C0] bool."""
     import torch
@@ -167,7 +167,7 @@ def _stem_masks_of_hip_run(out, model):
 
 def _bf16_operands(storage):
     """oracle.me_cpu.OPERAND_HOOK for BASELINE config #4: every convolution GEMM operand rounded to bf16 (round to nearest even, what
-    `(__bf16)v` and the MFMA packers of csrc/conv.hip / stem16.hip do) exactly where the HIP path rounds it -- forward: rows and
+    `(__bf16)v` and the MFMA packers of csrc/conv_common.h / stem16.hip do) exactly where the HIP path rounds it -- forward: rows and
     weights; data gradient: dY and weights, EXCEPT the 1x1x1 strided shortcut, whose data gradient is the exact-fp32 dense GEMM
     mink_dense_xwt (csrc/trunk.hip); weight gradient: rows and dY.  `storage`: the stem's convolution output is also STORED as
     bf16 (set_conv_storage("bf16")): its forward value is rounded, the gradient passes unchanged."""

@@ -26,7 +26,7 @@ DISCRIMINATE = 20.0
 
 # ------------------------------------------------------------------------------------------------ rounding table
 def bf16_rne(t):
-    """Round to bf16, nearest even (`(__bf16)v` and the MFMA packers of csrc/conv.hip / stem16.hip), back in t's dtype."""
+    """Round to bf16, nearest even (`(__bf16)v` and the MFMA packers of csrc/conv_common.h / stem16.hip), back in t's dtype."""
     return t.float().to(torch.bfloat16).to(t.dtype)
 
 
@@ -35,9 +35,9 @@ def bf16_trunc(t):
     return (t.float().contiguous().view(torch.int32) & -65536).view(torch.float32).to(t.dtype)
 
 
-# csrc/conv.hip constants the dispatch below depends on
-BK, BN = 32, 64  # conv.hip:23-24: reduction chunk, output columns per workgroup of the gather-GEMMs
-WT, WROWS = 64, 128  # conv.hip:1606-1607: weight-gradient super-tile, rows per tile
+# csrc/ constants the dispatch below depends on
+BK, BN = 32, 64  # conv_common.h BK / BN: reduction chunk, output columns per workgroup of the gather-GEMMs
+WT, WROWS = 64, 128  # conv_wgrad.hip WT / WROWS: weight-gradient super-tile, rows per tile
 CONV_MATH = {"fp32": 0, "bf16": 1, "bf16s": 1, "bf16x3": 3}  # "bf16s": bf16 math + bf16 storage of the stem (functional.set_conv_storage)
 
 
@@ -46,8 +46,8 @@ def _cdiv(a, b):
 
 
 def wgrad_plan(n_out, K, cin, cout, force=0):
-    """(G, nsplit) of wgrad_plan (conv.hip:2538-2566): offsets per workgroup and row splits.  `force`: set_stagger bits 12-26
-    (g_wgrad_force: bits 0-3 of it the G code 1 / 2 / 3 -> G = 1 / 3 / 9, bits 4.. a forced row-split count)."""
+    """(G, nsplit) of wgrad_plan (conv_wgrad.hip): offsets per workgroup and row splits.  `force`: set_stagger bits 12-26
+    (g_conv.wgrad_force: bits 0-3 of it the G code 1 / 2 / 3 -> G = 1 / 3 / 9, bits 4.. a forced row-split count)."""
     tiles = _cdiv(cin, WT) * _cdiv(cout, WT)
     row_tiles = _cdiv(n_out, WROWS)
     G = 1
@@ -87,8 +87,8 @@ class ConvForm:
 
 def conv_form(op, K, cin, cout, math, n_out=1, ldx=None, ldy=None, row_perm=False, aligned=True, ksplit=1, force_g=0, perm16=True,
               shortcut_dense=True):
-    """The launch form and operand rounding of one convolution operator, restated from the dispatchers of csrc/conv.hip
-    (gather_gemm_impl, conv.hip:2992-3184; wgrad_impl, conv.hip:3234-3300) with the default switches and within their 32-bit
+    """The launch form and operand rounding of one convolution operator, restated from the dispatchers gather_gemm_impl
+    (csrc/conv.hip) and wgrad_impl (csrc/conv_wgrad.hip) with the default switches and within their 32-bit
     size limits.
 
     op: "fwd" (W as [K][cin][cout]), "dgrad" (the same-map or class-permuted gather with the forward weights read transposed),
@@ -107,13 +107,13 @@ def conv_form(op, K, cin, cout, math, n_out=1, ldx=None, ldy=None, row_perm=Fals
         ldy = cout if ldy is None else ldy
         G, nsplit = wgrad_plan(n_out, K, cin, cout, force_g)
         tag = f" G{G}" + (" split" if nsplit > 1 else "")
-        # the streaming kernels take the stem shape (wgrad_stream_ok, conv.hip:3229)
+        # the streaming kernels take the stem shape (wgrad_stream_ok in conv_wgrad.hip)
         stream_ok = K == 27 and cin <= 32 and ldx < 64
         if G == 9 and stream_ok:
-            if m == 1:  # conv.hip:3265 (bf16_stream)
+            if m == 1:  # wgrad_impl in conv_wgrad.hip: bf16_stream
                 return ConvForm("wgrad_stream_bf16" + tag, frozenset({"x", "dy"}))
             return ConvForm("wgrad_stream" + tag, frozenset())
-        if m == 1 and G != 9 and cin % WT == 0 and cout % WT == 0 and aligned and (ldx | ldy) % 4 == 0:  # conv.hip:3285-3289
+        if m == 1 and G != 9 and cin % WT == 0 and cout % WT == 0 and aligned and (ldx | ldy) % 4 == 0:  # wgrad_impl in conv_wgrad.hip: the wgrad16_kernel branch
             return ConvForm(f"wgrad16<{3 if G == 3 else 1}>" + tag, frozenset({"x", "dy"}))
         return ConvForm("wgrad fp32" + tag, frozenset())  # launch_wgrad<G>: exact fp32 under every math (bf16x3 included)
     assert op in ("fwd", "dgrad"), op
@@ -123,16 +123,16 @@ def conv_form(op, K, cin, cout, math, n_out=1, ldx=None, ldy=None, row_perm=Fals
     gin, gout = (cout, cin) if wt else (cin, cout)  # the GEMM's reduction / output widths
     names = {"dy", "w"} if wt else {"x", "w"}
     ldx = gin if ldx is None else ldx
-    vec = aligned and ldx % 4 == 0 and gin % 4 == 0 and (wt or gout % 4 == 0)  # conv.hip:3028-3029 (al, vec)
+    vec = aligned and ldx % 4 == 0 and gin % 4 == 0 and (wt or gout % 4 == 0)  # gather_gemm_impl in conv.hip: al, vec
     if m == 0:
         return ConvForm("fp32", frozenset())
-    # the class-permuted branch (compact_perm_shape, conv.hip:2965; conv.hip:3052): bf16 math takes it for the data gradient only
+    # the class-permuted branch (compact_perm_shape in conv.hip and its use in gather_gemm_impl): bf16 math takes it for the data gradient only
     if (row_perm and wt and m == 1 and perm16 and K >= 8 and gin >= 64 and gin % BK == 0 and gout % BN == 0 and vec
             and gout % 4 == 0):
         return ConvForm("class-permuted compact bf16", frozenset(names))
-    if not vec:  # gather_gemm_kernel (conv.hip:3156): operands that are not 16-byte rows -- no MATH parameter, exact fp32
+    if not vec:  # gather_gemm_kernel (gather_gemm_impl in conv.hip, its last branch): operands that are not 16-byte rows -- no MATH parameter, exact fp32
         return ConvForm("scalar gather_gemm", frozenset())
-    # gather_gemm2_kernel<W_T, STAGE, FLAT, MATH> (conv.hip:3142-3154; the row-compacted forms need fp32 math, conv.hip:3031)
+    # gather_gemm2_kernel<W_T, STAGE, FLAT, MATH> (gather_gemm_impl in conv.hip: flat, MINK_LAUNCH_GG2; the row-compacted forms need fp32 math: compact_ok)
     if row_perm:
         form = "staged gather_gemm2" + (" (transposed weights)" if wt else " (transposed-conv fwd)")
     elif wt:
@@ -174,7 +174,7 @@ def other_reference(fn, ops, cf):
 
 
 def bf16_split(t, rnd=None):
-    """(hi, lo) of split-bf16 (conv.hip pack_bf16 / bf16_residual): hi = rne(v), lo = rne(v - hi), both taken in fp32."""
+    """(hi, lo) of split-bf16 (conv_common.h pack_bf16 / conv.hip bf16_residual): hi = rne(v), lo = rne(v - hi), both taken in fp32."""
     rnd = rnd or bf16_rne
     v = t.float()
     hi = bf16_rne(v)
@@ -314,7 +314,7 @@ def fma32(a, b, c):
 
 def stem_wgrad_operand(g_pool, y, mean, invstd, gamma, beta, dgamma, dbeta, in2out, n):
     """The dY operand the stem's fused weight-gradient kernel recomputes in fp32 from the kernel's own (y, mean, invstd,
-    dgamma, dbeta) (csrc/conv.hip, wgrad_stream*_kernel<FUSE>) -- what it then rounds to bf16 under bf16 math:
+    dgamma, dbeta) (csrc/conv_wgrad.hip, wgrad_stream*_kernel<FUSE>) -- what it then rounds to bf16 under bf16 math:
       xh = fma(y, invstd, fl(-mean * invstd)),  m = fma(xh, gamma, beta) > 0,
       v  = fl(gamma * invstd) * fma(-fl(dgamma / n), xh, fma(dp, m, -fl(dbeta / n)))   (1 / n and the quotients as fl(x * fl(1 / n)))."""
     assert in2out.shape[0] == y.shape[0] and int(in2out.min()) >= 0 and int(in2out.max()) < g_pool.shape[0]

@@ -78,6 +78,44 @@ def test_undersized_workspace_is_refused_before_any_launch():
     assert b"workspace" in L.mink_last_error()
 
 
+def test_conv_switches_reach_both_halves():
+    """The convolution's switches are one object (g_conv, csrc/conv_common.h) written by the setters of csrc/conv.hip and read by the
+    planners of both translation units: a bit set through mink_conv_set_stagger must change what wgrad_plan's callers in
+    csrc/conv_wgrad.hip answer, and mink_conv_set_math what mink_conv_plan in csrc/conv.hip answers.  Host arithmetic only."""
+    from nerf_downstream_amd import _lib
+
+    L = _lib.lib()
+
+    def stem_fused(n):  # the stem shape: wgrad_plan picks G = 9 from 342 row tiles of 128 up
+        return L.mink_conv_wgrad_bn_relu_pool_supported(n, 28, 28, n, 27, 64)
+
+    def plans():
+        return [L.mink_conv_plan(rows, 27, 64, 64, 0) for rows in (2316, 10840, 20000)]
+
+    try:
+        L.mink_conv_set_stagger(0)
+        L.mink_conv_set_math(0)
+        # weight-gradient side
+        assert stem_fused(43649) == 1
+        assert stem_fused(43648) == 0
+        L.mink_conv_set_stagger(1024)  # bit 10: the tiled weight-gradient kernel for the stem
+        assert stem_fused(43649) == 0
+        L.mink_conv_set_stagger(0)
+        assert stem_fused(43649) == 1
+        # forward side
+        assert plans() == [14, 7, 6]
+        L.mink_conv_set_math(1)
+        assert plans() == [14, 6, 3]
+        L.mink_conv_set_math(0)
+        L.mink_conv_set_stagger(1 << 30)  # bit 30: the mid layers back on the dense kernel
+        assert plans() == [14, 6, 3]
+        L.mink_conv_set_stagger(0)
+        assert plans() == [14, 7, 6]
+    finally:
+        L.mink_conv_set_stagger(0)
+        L.mink_conv_set_math(0)
+
+
 def test_trunk_branch_policy():
     """Where the native trunk runs its shortcut branch (minkowski/functional.py: trunk_branch_mode): a stream of its own by
     default; under a data-parallel reducer (fork off, branch-on-side on) the weight-gradient stream with fp32 / split-bf16

@@ -332,7 +332,7 @@ def test_fused_bn_relu_sumpool(oracle_maps):
 
 @pytest.mark.parametrize("cin,ldx,drop", [(28, 28, 0), (28, 32, 1), (20, 20, 3), (32, 32, 0)])
 def test_stem_wgrad_streaming(cin, ldx, drop):
-    """The streaming weight-gradient kernel (K = 27, cin <= 32, >= ~44k rows; conv.hip
+    """The streaming weight-gradient kernel (K = 27, cin <= 32, >= ~44k rows; conv_wgrad.hip
     wgrad_stream_kernel) against the tiled LDS kernel and an fp64 torch restatement of
     dW[k] = X[nbr[:, k]]^T dY on the same neighbour table.  `drop` trims rows so the row count is
     odd / not a tile multiple; ldx > cin exercises a padded feature matrix."""

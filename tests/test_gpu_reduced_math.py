@@ -3,11 +3,11 @@ restatement of exactly what each form computes -- on synthetic tables in the sty
 test_row_compacted_kernel_against_float64: ragged row counts (1, 63, 65, a few thousand), an offset nobody has, one a whole
 64-row tile lacks.
 
-What a form computes is read from the shape-aware rounding table (layerwise.conv_form, a restatement of gather_gemm_impl /
-wgrad_impl in csrc/conv.hip):
+What a form computes is read from the shape-aware rounding table (layerwise.conv_form, a restatement of gather_gemm_impl in
+csrc/conv.hip and wgrad_impl in csrc/conv_wgrad.hip):
   * bf16 forms:    float64 over bf16_rne(x) and bf16_rne(w) (or dY);
   * bf16x3 forms:  float64 over the three products xh*wh + xh*wl + xl*wh, h = rne(v) and l = rne(v - h) taken in fp32
-                   (conv.hip pack_bf16 / bf16_residual; layerwise.bf16_split);
+                   (conv_common.h pack_bf16 / conv.hip bf16_residual; layerwise.bf16_split);
   * fp32 forms:    float64 over the fp32 operands (the scalar gather_gemm_kernel has no MATH parameter, and the weight
                    gradients outside wgrad16_kernel / the bf16 streaming kernel stay exact fp32 under every math mode).
 
@@ -340,7 +340,7 @@ WGRAD_FORMS = {
 @pytest.mark.parametrize("math", ["bf16", "bf16x3"])
 def test_weight_gradient_forms_under_reduced_math_against_float64(math):
     """Weight gradients: wgrad16_kernel (bf16 operands) at K = 27 / 8 / 1 under forced G = 1 / 3 / 9 and forced row splits
-    (set_stagger bits 12-26, conv.hip g_wgrad_force), K = 8 with G = 3 (a partial last group), one and several row splits;
+    (set_stagger bits 12-26, conv_wgrad.hip wgrad_plan, g_conv.wgrad_force), K = 8 with G = 3 (a partial last group), one and several row splits;
     widths that must stay on the exact-fp32 kernel (48, 96, a row stride that is not a multiple of 4); the streaming bf16 stem
     kernel at cin = 3 / 20 / 28 / 32 -- against float64 on the operands the table declares (bf16x3 math: every weight gradient is
     exact fp32)."""

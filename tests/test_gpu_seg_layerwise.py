@@ -28,8 +28,8 @@ pytestmark = [pytest.mark.gpu, pytest.mark.long]
 ROOT = os.path.join(os.path.dirname(__file__), "..")
 CFG = os.path.join(ROOT, "nerf_downstream_amd", "co3d_3d", "configs")
 POINTS = 300_000  # per scene: ~2 x 10^5 voxels of 2 cm before the crop
-BK, BN = 32, 64  # csrc/conv.hip:23-24 (reduction chunk, output columns per workgroup)
-CKP = 9  # csrc/conv.hip:826 (offsets per workgroup of the row-compacted kernel)
+BK, BN = 32, 64  # csrc/conv_common.h BK / BN (reduction chunk, output columns per workgroup)
+CKP = 9  # csrc/conv.hip CKP (offsets per workgroup of the row-compacted kernel)
 # the 4 cats: (block that consumes it, the up-sampling unit, the encoder output it is joined with)
 CATS = [("block5", "convtr4p16s2", "block3"), ("block6", "convtr5p8s2", "block2"), ("block7", "convtr6p4s2", "block1"),
         ("block8", "convtr7p2s2", "conv0p1s1")]
@@ -175,23 +175,23 @@ def _launch_forms(L, n_rows, K, cin, cout, perm, wt, stats):
     (torch allocations are 16-byte aligned and rows contiguous, so the alignment terms hold).  cin / cout are the GEMM's:
     a data gradient's are the convolution's cout / cin."""
     ks = int(L.mink_conv_plan(n_rows, K, cin, cout, int(perm)))  # (functional.py _plan_ksplit: n_rows = the permutation's length)
-    vec = cin % 4 == 0 and (wt or cout % 4 == 0)  # conv.hip:3037-3038
-    # compact_perm_shape (conv.hip:2965) and the class-permuted branch (conv.hip:3046)
+    vec = cin % 4 == 0 and (wt or cout % 4 == 0)  # gather_gemm_impl in conv.hip: al, vec
+    # compact_perm_shape (conv.hip) and the class-permuted branch of gather_gemm_impl
     if perm and not stats and vec and K >= 8 and cin >= 64 and cin % BK == 0 and cout % BN == 0:
         ncc = cin // BK
         return {"class-permuted compact"} | ({"split-K"} if _cdiv(ncc, _cdiv(ncc, ks)) > 1 else set())
     kper = _cdiv(K, ks)
-    zs = _cdiv(K, kper)  # conv.hip:3034
+    zs = _cdiv(K, kper)  # gather_gemm_impl in conv.hip: zs
     forms = {"split-K"} if zs > 1 else set()
-    if vec and not perm and K >= 8 and kper <= CKP and cin >= 64 and cin % BK == 0 and cout % BN == 0:  # conv.hip:3092
+    if vec and not perm and K >= 8 and kper <= CKP and cin >= 64 and cin % BK == 0 and cout % BN == 0:  # gather_gemm_impl in conv.hip: compact_ok, compact
         forms.add("row-compacted")
-    elif vec:  # gather_gemm2_kernel: `stage` = a row permutation (conv.hip:3138)
+    elif vec:  # gather_gemm2_kernel: `stage` = a row permutation (gather_gemm_impl in conv.hip: stage)
         forms.add("staged gather_gemm2" if perm else "dense gather_gemm2")
         if cin % BK:
             forms.add("channel tail")
     else:
         forms.add("scalar gather_gemm")
-    if stats:  # conv.hip:3042-3045
+    if stats:  # gather_gemm_impl in conv.hip: want_stats, stats_direct, stats_split
         if zs == 1 and vec:
             forms.add("stats direct")
         elif zs > 1 and cout % 4 == 0 and cout <= 1024:
@@ -439,9 +439,9 @@ def _check(model, cap, tabs, levels, inverse, L, training, labels=None, before=N
 # ------------------------------------------------------------------------------------------------ the test
 # Against the launch table the segmentation network was expected to take, the planner differs in one place: block7 / block8
 # (96 -> 64, 64 -> 64, stride 1, ~10^6 rows at ts 1) do NOT take the row-compacted kernel.  That kernel holds at most CKP = 9
-# offsets per workgroup, so 27 offsets need >= 3 slabs, and compact_shape (conv.hip:2936) admits a shape only while those
+# offsets per workgroup, so 27 offsets need >= 3 slabs, and compact_shape (conv.hip) admits a shape only while those
 # slabs fit 128 MB (3 x 4 B x 10^6 x 64 = 768 MB does not); mink_conv_plan then answers with mink_conv_plan_ksplit, which has
-# no split for >= 768 row tiles, and un-split 27 offsets exceed CKP: gather_gemm_impl takes dense gather_gemm2 (conv.hip:3092).
+# no split for >= 768 row tiles, and un-split 27 offsets exceed CKP: gather_gemm_impl takes dense gather_gemm2 (conv.hip: compact).
 # The row-compacted stride-1 form is reached at the coarse levels (block3, 64 -> 64), and conv4p8s2 (K = 8) takes it too.
 EXPECT = {"stem padded 3->4", "row-compacted (conv4p8s2)", "row-compacted, stride 1", "dense unsplit at ts 1",
           "class-permuted compact (transposed fwd)",
