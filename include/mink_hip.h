@@ -19,6 +19,11 @@
  *     buffer is passed WITH ITS SIZE (`workspace_bytes`, ABI version 2): the size a launch needs can depend on a
  *     plan (split factors, row splits), so the library checks it against the plan it is about to launch and returns
  *     MINK_EINVAL instead of writing past the end of a buffer sized for another plan;
+ *   - the library writes only the first C columns of the first n rows of an output (the pad columns of a row pitch ld > C, rows
+ *     an accumulating or scattering call does not visit and statistics rows past the count a call reports keep their bits) and
+ *     only the first `workspace_bytes` it asked for; for the entry points of the training step (convolution, weight gradient,
+ *     batch-norm family, pools, head, loss, optimizer) no pad-column or out-of-extent value of an input reaches a result, so
+ *     their pad columns may hold anything, NaN included (tests/test_gpu_guard.py holds them to both, bit for bit);
  *   - return value 0 = success, otherwise a negative MINK_E* code and
  *     mink_last_error() (thread-local) describes the failure;
  *   - coordinates are int32 rows (batch, x, y, z); row counts are int64; feature

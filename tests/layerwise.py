@@ -146,6 +146,46 @@ def conv_form(op, K, cin, cout, math, n_out=1, ldx=None, ldy=None, row_perm=Fals
     return ConvForm(form + (" bf16x3" if m == 3 else " bf16"), frozenset(names), split=m == 3)
 
 
+CKP = 9  # conv_common.h: offsets per workgroup of the row-compacted kernel
+
+
+def gather_launch_form(n_out, K, cin, cout, ldx, ldy, wt, flip, perm, acc, ksplit, math="fp32", pipe=0):
+    """(launch form, slabs written) of one mink_conv_gather_gemm call -- gather_gemm_impl (csrc/conv.hip) for 16-byte aligned
+    operands and default set_stagger switches, fp32 math included (conv_form names the fp32 launches just "fp32": its callers ask
+    which operands are rounded, this one which kernel runs and how many slabs it writes).  cin / cout are the GEMM's reduction /
+    output widths (the ABI's arguments), wt / flip / perm / acc its w_transposed, flip_k bit 0, row_perm and flip_k bit 1, ksplit
+    the split asked for, pipe mink_conv_set_pipeline's mode.  The dense, flat, staged and scalar forms under reduced math are
+    conv_form's."""
+    math = CONV_MATH[math]
+    vec = ldx % 4 == 0 and cin % 4 == 0 and (wt or cout % 4 == 0)
+    mid = K >= 8 and cin >= 64 and cin % BK == 0 and cout % BN == 0 and vec and ldy % 4 == 0 and not acc
+    if perm and mid and (math == 0 or (math == 1 and wt)):
+        ncc = cin // BK
+        zc = _cdiv(ncc, _cdiv(ncc, ksplit))
+        return "class-permuted compact" + (" bf16" if math == 1 else "") + (" three-stage" if wt and pipe & 2 else ""), zc
+    compact_ok = math == 0 and mid and not perm
+    kper = _cdiv(K, ksplit)
+    sk = False
+    if pipe & 8 and ksplit > 1 and compact_ok:  # sk_plan: 1,024 workers, runs of at least five offset-tiles
+        run = _cdiv(n_out, 64) * _cdiv(cout, BN) * K // 1024
+        sk = run >= 5 and _cdiv(K, run) + 1 <= ksplit
+    zs = ksplit if sk else _cdiv(K, kper)
+    if compact_ok and (kper <= CKP or sk):
+        return ("stream-K" if sk else "row-compacted" + (" three-stage" if pipe & 1 else "")), zs
+    if math:
+        conv_cin, conv_cout = (cout, cin) if wt else (cin, cout)
+        cf = conv_form("dgrad" if wt else "fwd", K, conv_cin, conv_cout, {0: "fp32", 1: "bf16", 3: "bf16x3"}[math], n_out=n_out, ldx=ldx, row_perm=perm,
+                          ksplit=ksplit, shortcut_dense=False)
+        return cf.form, zs
+    if not vec:
+        return "scalar gather_gemm", zs
+    if perm:
+        return "staged gather_gemm2" + (" (transposed weights)" if wt else "") + (" accumulate" if acc else ""), zs
+    if cin == 28 and zs == 1 and not flip and not wt and ldx <= 32:
+        return "flat gather_gemm2 (cin 28)", zs
+    return "dense gather_gemm2" + (" (transposed weights)" if wt else ""), zs
+
+
 def rounded_operands(op, K, cin, cout, math, **shape):
     """The operands a kernel rounds to bf16 before its fp32-accumulating products (conv_form: shape-aware -- a scalar-form
     gather and a weight gradient whose widths are not multiples of 64 stay exact fp32 under bf16 math, the K = 1 strided
