@@ -1067,6 +1067,19 @@ int64_t mink_conv_timing_fetch(MinkTimingEntry *out, int64_t max);
  *   cores).  1 <= C <= MINK_KNN_MAX_C, 1 <= k <= MINK_KNN_MAX_K, samples of any size (empty ones included), n k < 2^31.  The
  *   slots of a row whose sample holds fewer than k rows with a comparable (non-NaN) score are -1.
  *
+ * mink_knn_cross: the same search with queries and candidates in two matrices (feature matching between two clouds, reference
+ *   co3d_3d/src/utils/geometry.py find_nn_gpu): idx[i][0..k) = the global rows of c, inside the SAME sample, nearest to row i
+ *   of q.  q[nq][C] (row stride ldq floats), rows of sample b = q_offsets[b] .. q_offsets[b+1]; c[nc][C] (row stride ldc), rows
+ *   of sample b = c_offsets[b] .. c_offsets[b+1]; both offset arrays int32 [B + 1] on the device (entries are clamped to the
+ *   row counts).  Ranking as mink_knn: score ||c_j||^2 - 2 q_i.c_j in fp32, ascending, equal scores in ascending row order;
+ *   slots beyond the number of comparable (non-NaN score) candidates of the sample are -1.  The launch shape, the tile loop
+ *   and the running top-k are mink_knn's (one device function, two instantiations).
+ *   dist (may be NULL): dist[i][s] = sum_c (q_i[c] - c_idx[c])^2 recomputed for the chosen pair by direct differences, one
+ *   fused multiply-add chain, channels ascending, carried in double and rounded to fp32 once (within one fp32 rounding of the
+ *   exact value; an fp32 chain would round every difference too and exceed C u); +inf where idx is -1 (such a slot is never
+ *   followed).  This is not the ranking score, so it carries no cancellation -- and neighbouring slots may be out of exact
+ *   order by less than the ranking error.  1 <= C <= MINK_KNN_MAX_C, 1 <= k <= MINK_KNN_MAX_K, nq k < 2^31, samples of any size on either side.
+ *
  * Edge convolution.  With W = [W1 | W2] the reference's W [x_j - x_i ; x_i] is e[i][j] = P[idx[i][j]] + Q[i], P = X W1^T,
  *   Q = X (W2 - W1)^T, both [n][C] (C = output channels, any C >= 1).  An idx outside [0, n) is clamped, never followed.
  *   mink_edge_stats: per-channel (sum e, sum e^2) over the n k edges as double column partials [mink_edge_stats_rows(n)][2][C]
@@ -1080,6 +1093,8 @@ int64_t mink_conv_timing_fetch(MinkTimingEntry *out, int64_t max);
 #define MINK_KNN_MAX_C 256
 int mink_knn(const float *x, int64_t n, int64_t ldx, int32_t C, const int32_t *batch_offsets, int32_t B, int32_t k, int32_t *idx,
              void *stream);
+int mink_knn_cross(const float *q, int64_t nq, int64_t ldq, const float *c, int64_t nc, int64_t ldc, int32_t C,
+                   const int32_t *q_offsets, const int32_t *c_offsets, int32_t B, int32_t k, int32_t *idx, float *dist, void *stream);
 int32_t mink_edge_stats_rows(int64_t n);
 int mink_edge_stats(const float *P, const float *Q, const int32_t *idx, int64_t n, int32_t k, int32_t C, double *partial,
                     int64_t partial_bytes, void *stream);

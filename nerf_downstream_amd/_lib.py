@@ -244,6 +244,7 @@ SIGNATURES = {
     "mink_conv_timing": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32]),
     "mink_conv_timing_fetch": (_i64, [_p, _i64]),
     "mink_knn": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _i32, _i32, _p, _p]),
+    "mink_knn_cross": (ctypes.c_int, [_p, _i64, _i64, _p, _i64, _i64, _i32, _p, _p, _i32, _i32, _p, _p, _p]),
     "mink_edge_stats_rows": (_i32, [_i64]),
     "mink_edge_stats": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, _p, _i64, _p]),
     "mink_edge_fwd": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),

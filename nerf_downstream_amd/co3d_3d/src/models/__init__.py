@@ -5,6 +5,7 @@ from nerf_downstream_amd import gin_lite as gin
 from .mink.resnet import ResNet14, ResNet18, ResNet34, ResNet50, ResNet101
 
 from .mink import res16unet as _unet
+from .mink import resunet as _resunet
 from .mink.dgcnn import DGCNN_cls
 from .mink.fcnn import MinkowskiFCNN, MinkowskiSplatFCNN
 from .mink.paconv import PAConvDGCNN, PAConvPointNet
@@ -12,6 +13,8 @@ from .mink.pointnet import MinkowskiPointNet
 
 MODELS = {c.__name__: c for c in (ResNet14, ResNet18, ResNet34, ResNet50, ResNet101)}
 MODELS.update({n: c for n, c in vars(_unet).items() if n.startswith("Res16UNet") and isinstance(c, type)})
+MODELS.update({n: c for n, c in vars(_resunet).items()  # registration feature extractors (ResUNet2 itself is abstract)
+               if n.startswith("ResUNet") and isinstance(c, type) and c.NORM_TYPE is not None})
 MODELS.update({c.__name__: c for c in (MinkowskiFCNN, MinkowskiSplatFCNN, MinkowskiPointNet, DGCNN_cls, PAConvPointNet, PAConvDGCNN)})  # point-based classifiers
 
 

@@ -132,3 +132,9 @@ class Bottleneck(BasicBlock):
         h = self.norm3(self.conv3(h))
         h += shortcut
         return self.nonlinearity(h)
+
+
+def get_block(norm_type, inplanes, planes, stride=1, dilation=1, downsample=None, bn_momentum=0.1, D=3, ME=None):
+    """The BasicBlock of the registration networks (reference resnet_block.py:135-156): the norm type comes first."""
+    return BasicBlock(inplanes, planes, stride, dilation, downsample, norm_type, nonlinearity_type="MinkowskiReLU",
+                      bn_momentum=bn_momentum, D=D, ME=ME)

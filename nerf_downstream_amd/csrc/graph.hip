@@ -8,6 +8,10 @@
 //                     ||x_j||^2 - 2 x_i.x_j ranks as the squared distance does.  Every wave keeps the running top-k of 8
 //                     queries sorted across its lanes (lane l = the l-th nearest so far, k <= 64): a candidate is first
 //                     tested against the k-th entry, and only a survivor is inserted (one ballot, one lane shift).
+//   mink_knn_cross  : the same tile loop with the queries in one matrix and the candidates in another (per-sample offsets on
+//                     both sides), and an epilogue that recomputes the squared distance of every chosen pair by direct
+//                     differences, accumulated in double and rounded once (query from the LDS tile, candidate row from memory; a -1
+//                     slot is never followed)
 //   mink_edge_stats : per-channel sum / sum of squares of e[i][j] = P[idx[i][j]] + Q[i] over the n k edges, as the double
 //                     column partials [rows][2][C] that mink_bn_stats_from_partials consumes
 //   mink_edge_fwd   : y[i][c] = max_j lrelu(gamma (e - mean) invstd + beta), arg = the lowest slot attaining it
@@ -28,40 +32,50 @@ constexpr int KQW = KQ / 4;                // queries owned by one of the four w
 
 __device__ __forceinline__ bool knn_before(float d, int j, float dk, int jk) { return d < dk || (d == dk && j < jk); }
 
-__global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ x, int64_t ldx, int C, const int *__restrict__ boff, int B,
-                                                  int k, int *__restrict__ idx) {
+// The tile loop both entry points share.  Queries are rows qs0 .. qs1 of q (sample b of qoff), candidates rows cs0 .. cs1 of c
+// (sample b of coff); CROSS = false is mink_knn, instantiated with q = c and qoff = coff, where the two ranges are one.
+template <bool CROSS>
+__device__ __forceinline__ void knn_body(const float *__restrict__ q, int64_t ldq, int64_t nq, const float *__restrict__ c, int64_t ldc,
+                                         int64_t nc, int C, const int *__restrict__ qoff, const int *__restrict__ coff, int B, int k,
+                                         int *__restrict__ idx, float *__restrict__ dist) {
   extern __shared__ float sQ[];    // [Cpad][KLQ]: the query tile, k-major, zero-padded to a multiple of KK channels
   __shared__ float sB[KK * KLC];   // a candidate chunk [KK][KLC], k-major; then the score tile [KQ][KLC]
   __shared__ float sN[KC];         // ||x_j||^2 of the candidate tile
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int Cpad = (C + KK - 1) / KK * KK;
   // the sample and the tile of this workgroup: tiles are numbered sample by sample
-  int blk = blockIdx.x, b = 0, s0 = 0, s1 = 0;
+  int blk = blockIdx.x, b = 0, qs0 = 0, qs1 = 0;
   for (; b < B; ++b) {
-    s0 = boff[b], s1 = boff[b + 1];
-    const int t = s1 > s0 ? (s1 - s0 + KQ - 1) / KQ : 0;
+    qs0 = qoff[b], qs1 = qoff[b + 1];
+    if (CROSS) qs0 = qs0 < 0 ? 0 : qs0, qs1 = qs1 > nq ? (int)nq : qs1;  // (never outside q, whatever the offsets hold)
+    const int t = qs1 > qs0 ? (qs1 - qs0 + KQ - 1) / KQ : 0;
     if (blk < t) break;
     blk -= t;
   }
   if (b == B) return;  // (the grid is the upper bound n / KQ + B)
-  const int q0 = s0 + blk * KQ;
+  int cs0 = qs0, cs1 = qs1;
+  if (CROSS) {
+    cs0 = coff[b], cs1 = coff[b + 1];
+    cs0 = cs0 < 0 ? 0 : cs0, cs1 = cs1 > nc ? (int)nc : cs1;
+  }
+  const int q0 = qs0 + blk * KQ;
   for (int e = tid; e < KQ * Cpad; e += 256) {
-    const int r = e / Cpad, c = e - r * Cpad;
-    sQ[c * KLQ + r] = (q0 + r < s1 && c < C) ? x[(int64_t)(q0 + r) * ldx + c] : 0.f;
+    const int r = e / Cpad, ch = e - r * Cpad;
+    sQ[ch * KLQ + r] = (q0 + r < qs1 && ch < C) ? q[(int64_t)(q0 + r) * ldq + ch] : 0.f;
   }
   float bd[KQW];
   int bj[KQW];
 #pragma unroll
   for (int qi = 0; qi < KQW; ++qi) bd[qi] = __builtin_inff(), bj[qi] = INT_MAX;
 
-  for (int c0 = s0; c0 < s1; c0 += KC) {
+  for (int c0 = cs0; c0 < cs1; c0 += KC) {
     f32x16 acc = (f32x16){0};
     float nrm = 0.f;
     for (int k0 = 0; k0 < Cpad; k0 += KK) {
       __syncthreads();  // sB is free: the previous chunk's MFMAs / the previous tile's selection are done (and sQ is written)
       for (int e = tid; e < KC * KK; e += 256) {
         const int r = e >> 5, kk = e & 31;
-        sB[kk * KLC + r] = (c0 + r < s1 && k0 + kk < C) ? x[(int64_t)(c0 + r) * ldx + k0 + kk] : 0.f;
+        sB[kk * KLC + r] = (c0 + r < cs1 && k0 + kk < C) ? c[(int64_t)(c0 + r) * ldc + k0 + kk] : 0.f;
       }
       __syncthreads();
       if (tid < KC) {
@@ -91,15 +105,15 @@ __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ x, i
     // selection: wave w owns queries 8 w .. 8 w + 7; candidates ascend, so among equal scores the lower row stays ahead
 #pragma unroll
     for (int qi = 0; qi < KQW; ++qi) {
-      const int q = wave * KQW + qi;
-      if (q0 + q >= s1) continue;  // (uniform)
+      const int qr = wave * KQW + qi;
+      if (q0 + qr >= qs1) continue;  // (uniform)
       float dk = __shfl(bd[qi], k - 1, 64);
       int jk = __shfl(bj[qi], k - 1, 64);
 #pragma unroll
       for (int half = 0; half < KC / 64; ++half) {
         const int cand = c0 + half * 64 + lane;
-        const float s = sB[q * KLC + half * 64 + lane];
-        unsigned long long mask = __ballot(cand < s1 && knn_before(s, cand, dk, jk));
+        const float s = sB[qr * KLC + half * 64 + lane];
+        unsigned long long mask = __ballot(cand < cs1 && knn_before(s, cand, dk, jk));
         while (mask) {
           const int src = __ffsll((long long)mask) - 1;
           mask &= mask - 1;
@@ -120,8 +134,38 @@ __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ x, i
 #pragma unroll
   for (int qi = 0; qi < KQW; ++qi) {
     const int row = q0 + wave * KQW + qi;
-    if (row < s1 && lane < k) idx[(int64_t)row * k + lane] = bj[qi] == INT_MAX ? -1 : bj[qi];  // -1: fewer than k comparable rows
+    if (row < qs1 && lane < k) idx[(int64_t)row * k + lane] = bj[qi] == INT_MAX ? -1 : bj[qi];  // -1: fewer than k comparable rows
+    if (CROSS && dist && row < qs1 && lane < k) {
+      // the squared distance of the chosen pair by direct differences (the ranking score is not reused: it cancels); the
+      // query from the LDS tile (one address per wave: a broadcast), the candidate row from memory; a -1 slot is not followed.
+      // Differences and the fused multiply-add chain in double, rounded to fp32 once: an fp32 chain rounds every difference
+      // as well and is off by up to (C + 2) u, measured 3.15 u at C = 3 against the C u the callers are promised.
+      float d = __builtin_inff();
+      if (bj[qi] != INT_MAX) {
+        const float *cr = c + (int64_t)bj[qi] * ldc;
+        const float *qr = sQ + wave * KQW + qi;
+        double acc = 0.0;
+        for (int ch = 0; ch < C; ++ch) {
+          const double t = (double)qr[ch * KLQ] - (double)cr[ch];
+          acc = fma(t, t, acc);
+        }
+        d = (float)acc;
+      }
+      dist[(int64_t)row * k + lane] = d;
+    }
   }
+}
+
+__global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ x, int64_t ldx, int C, const int *__restrict__ boff, int B,
+                                                  int k, int *__restrict__ idx) {
+  knn_body<false>(x, ldx, 0, x, ldx, 0, C, boff, boff, B, k, idx, nullptr);
+}
+
+__global__ __launch_bounds__(256) void knn_cross_kernel(const float *__restrict__ q, int64_t ldq, int64_t nq, const float *__restrict__ c,
+                                                        int64_t ldc, int64_t nc, int C, const int *__restrict__ qoff,
+                                                        const int *__restrict__ coff, int B, int k, int *__restrict__ idx,
+                                                        float *__restrict__ dist) {
+  knn_body<true>(q, ldq, nq, c, ldc, nc, C, qoff, coff, B, k, idx, dist);
 }
 
 // ---------------------------------------------------------------------------------------------- edge convolution
@@ -288,6 +332,22 @@ int mink_knn(const float *x, int64_t n, int64_t ldx, int32_t C, const int32_t *b
   const int Cpad = (int)align_up(C, KK);
   knn_kernel<<<dim3((unsigned)(cdiv(n, KQ) + B)), 256, (size_t)Cpad * KLQ * sizeof(float), (hipStream_t)stream>>>(x, ldx, C, batch_offsets,
                                                                                                                  B, k, idx);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_knn_cross(const float *q, int64_t nq, int64_t ldq, const float *c, int64_t nc, int64_t ldc, int32_t C,
+                   const int32_t *q_offsets, const int32_t *c_offsets, int32_t B, int32_t k, int32_t *idx, float *dist, void *stream) {
+  MINK_REQUIRE(k >= 1 && k <= MINK_KNN_MAX_K, "knn_cross: k = %d outside 1..%d", k, MINK_KNN_MAX_K);
+  MINK_REQUIRE(C >= 1 && C <= MINK_KNN_MAX_C, "knn_cross: C = %d outside 1..%d", C, MINK_KNN_MAX_C);
+  MINK_REQUIRE(nq >= 0 && nc >= 0 && nc < ((int64_t)1 << 31) && B >= 1 && ldq >= C && ldc >= C && nq * (int64_t)k < ((int64_t)1 << 31),
+               "knn_cross: bad shape (nq %lld, nc %lld, B %d, ldq %lld, ldc %lld, nq k < 2^31)", (long long)nq, (long long)nc, B,
+               (long long)ldq, (long long)ldc);
+  MINK_REQUIRE(q_offsets && c_offsets && (nq == 0 || (q && idx)) && (nc == 0 || c), "knn_cross: NULL pointer");
+  if (nq == 0) return MINK_OK;
+  const int Cpad = (int)align_up(C, KK);
+  knn_cross_kernel<<<dim3((unsigned)(cdiv(nq, KQ) + B)), 256, (size_t)Cpad * KLQ * sizeof(float), (hipStream_t)stream>>>(
+      q, ldq, nq, c, ldc, nc, C, q_offsets, c_offsets, B, k, idx, dist);
   MINK_CHECK_LAUNCH();
   return MINK_OK;
 }

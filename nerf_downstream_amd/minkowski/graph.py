@@ -1,5 +1,5 @@
 """Dynamic graph layers on the rows of a field (csrc/graph.hip): the per-sample k-nearest-neighbour graph in feature space
-and the edge convolution of DGCNN (reference co3d_3d/src/models/mink/dgcnn.py:8-38,81-85) fused with its batch norm,
+(`knn`; `knn_cross` with queries and candidates in two matrices, and distances) and the edge convolution of DGCNN (reference co3d_3d/src/models/mink/dgcnn.py:8-38,81-85) fused with its batch norm,
 LeakyReLU(0.2) and the maximum over the k edges.
 
 With W = [W1 | W2] the reference's 1x1 convolution of [x_j - x_i ; x_i] is e[i][j] = P[idx[i][j]] + Q[i] with P = X W1^T and
@@ -26,6 +26,44 @@ def knn(x, batch_offsets, k):
     idx = torch.empty(n, int(k), dtype=torch.int32, device=x.device)
     check(lib().mink_knn(x.data_ptr(), n, x.stride(0) if n > 1 else C, C, batch_offsets.data_ptr(), B, int(k), idx.data_ptr(), Fn._stream()))
     return idx
+
+
+def _rows_view(x, what):
+    """A float32 [n, C] device matrix with unit column stride (a strided row view is kept: its stride(0) is the leading
+    dimension the kernel takes); anything else is copied."""
+    x = x.detach()
+    assert x.is_cuda and x.dim() == 2, f"{what} [n, C] on the device"
+    if x.dtype != torch.float32 or x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.float().contiguous()
+    return x
+
+
+def knn_cross(q, c, k=1, q_offsets=None, c_offsets=None, return_distance=False):
+    """idx int32 [nq, k]: for every row of q [nq, C] the global rows of the k rows of c [nc, C], inside the same sample, nearest
+    in squared Euclidean distance (csrc/graph.hip mink_knn_cross); ascending ranking score ||c_j||^2 - 2 q_i.c_j, ties to the
+    lower row, -1 in the slots beyond the sample's candidates.  With `return_distance` also dist float32 [nq, k]: the squared
+    distance of every chosen pair recomputed by direct differences (+inf at -1); its slots follow the ranking order, so
+    neighbouring entries may be out of exact order by less than the ranking error.  Not differentiable.
+    `q_offsets` / `c_offsets`: int32 [B + 1] device row ranges of the samples on either side; both None = one sample (the
+    [0, n] offsets are built on the device, nothing is read back).  q and c may be strided row views (the xyz columns of an
+    [n, 4] coordinate matrix, a row slice): stride(0) is passed as the leading dimension, nothing is copied."""
+    q, c = _rows_view(q, "knn_cross: q"), _rows_view(c, "knn_cross: c")
+    assert q.device == c.device and q.shape[1] == c.shape[1], "knn_cross: q [nq, C] and c [nc, C] on one device"
+    (nq, C), nc = q.shape, c.shape[0]
+    if (q_offsets is None) != (c_offsets is None):
+        raise ValueError("knn_cross: give both q_offsets and c_offsets, or neither (one sample)")
+    if q_offsets is None:
+        both = torch.zeros(4, dtype=torch.int32, device=q.device)
+        both[1], both[3] = nq, nc  # (host scalars written by fills: no read-back)
+        q_offsets, c_offsets = both[:2], both[2:]
+    B = Fn._check_offsets(q_offsets)
+    assert Fn._check_offsets(c_offsets) == B, "knn_cross: q_offsets and c_offsets describe the same B samples"
+    idx = torch.empty(nq, int(k), dtype=torch.int32, device=q.device)
+    dist = torch.empty(nq, int(k), dtype=torch.float32, device=q.device) if return_distance else None
+    check(lib().mink_knn_cross(q.data_ptr(), nq, q.stride(0) if nq > 1 else C, c.data_ptr(), nc, c.stride(0) if nc > 1 else C, C,
+                               q_offsets.data_ptr(), c_offsets.data_ptr(), B, int(k), idx.data_ptr(),
+                               dist.data_ptr() if return_distance else None, Fn._stream()))
+    return (idx, dist) if return_distance else idx
 
 
 def check_sample_sizes(sizes, k):

@@ -129,8 +129,12 @@ class MinkowskiConvolutionTranspose(MinkowskiConvolution):
     transposed kernels from the OUT channel count).
 
     On the device this is the data-gradient kernel of the down-sampling convolution run forward: a gather
-    over the transposed neighbour table with rows grouped by parity class, so each 128-row tile multiplies
-    only the one kernel offset its rows can have (kernel_size == stride: one parent per voxel)."""
+    over the transposed neighbour table with rows grouped by parity class (CoordinateManager.class_perm), so a
+    tile multiplies only the kernel offsets its rows can have.  kernel_size == stride (2: the Res16UNet family):
+    one parent per voxel, one offset per tile.  kernel_size 3 over stride 2 (the ResUNet2 registration family): a
+    fine voxel has up to eight parents and a parity class 1, 2, 4 or 8 live offsets among the 27 -- the table shape
+    the data gradient of every stride-2 3x3x3 convolution of the ResNets has, through the same launch plan
+    (tests/test_gpu_resunet.py checks this shape operator by operator against the oracle)."""
 
     def __init__(self, in_channels, out_channels, kernel_size=-1, stride=1, dilation=1, bias=False,
                  kernel_generator=None, expand_coordinates=False, convolution_mode=None, dimension=None):
