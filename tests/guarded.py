@@ -11,8 +11,9 @@ store outside the buffer), every element the header says the call writes no long
 every other payload element -- pad columns of a matrix with ld > C, rows an accumulate or scatter does not visit, statistics
 rows past the count the call reported -- holds exactly what it held before.
 
-The payload starts 256-byte aligned and the back band begins at the first byte after it (no rounding slack: slack would hide an
-overrun of a few bytes).  Each band is one full output tile of the widest kernel, 128 rows x leading dimension x 4 bytes, and
+The payload starts 256-byte aligned -- or, with `skew`, that many bytes behind a 256-byte boundary, for the branch of a host
+lane decision that an unaligned pointer takes -- and the back band begins at the first byte after it (no rounding slack: slack
+would hide an overrun of a few bytes).  Each band is one full output tile of the widest kernel, 128 rows x leading dimension x 4 bytes, and
 never under 64 KiB.  Float sentinels are quiet NaNs with a marker payload, so a NaN a kernel computed is not mistaken for
 "untouched" and an input wrapped by `Guarded.input` poisons every result that an out-of-extent or pad-column read gets into, even
 multiplied by zero."""
@@ -57,9 +58,13 @@ class Guarded:
                      workspace: the call may write any part of the payload or none, only the bands are checked
     init           : values the logical elements hold before the call (accumulate and scatter targets, inputs); anything else
                      holds the sentinel.  `pad` overrides the sentinel of the pad columns (a finite value for an entry point
-                     whose contract asks for finite pads)."""
+                     whose contract asks for finite pads).
+    skew           : bytes (a multiple of the element size, below 256) between a 256-byte boundary and the payload's first
+                     element: skew=4 gives a float pointer that is not 16-byte aligned.  The bands still end and begin at the
+                     payload's first and last byte, and the sentinel pattern stays element-aligned."""
 
-    def __init__(self, shape_or_bytes, dtype=torch.float32, device="cpu", written=None, init=None, cols=None, pad=None, name="buffer"):
+    def __init__(self, shape_or_bytes, dtype=torch.float32, device="cpu", written=None, init=None, cols=None, pad=None, name="buffer",
+                 skew=0):
         self.name, self.dtype, self.device = name, dtype, torch.device(device)
         self.item = torch.empty((), dtype=dtype).element_size()
         if isinstance(shape_or_bytes, int):
@@ -74,11 +79,13 @@ class Guarded:
         assert len(self.shape) < 2 or 0 <= self.cols <= ld, (self.cols, ld)
         band = max(MIN_BAND, TILE_ROWS * max(ld, 1) * 4)
         self.band = -(-band // ALIGN) * ALIGN
+        self.skew = int(skew)
+        assert 0 <= self.skew < ALIGN and self.skew % self.item == 0, (self.skew, self.item)
         total = 2 * self.band + self.nbytes
-        raw = torch.empty(total + ALIGN, dtype=torch.uint8, device=self.device)
-        skew = (-raw.data_ptr()) % ALIGN
-        self.buf = raw[skew : skew + total]
-        assert (self.buf.data_ptr() + self.band) % ALIGN == 0
+        raw = torch.empty(total + 2 * ALIGN, dtype=torch.uint8, device=self.device)
+        start = (-raw.data_ptr()) % ALIGN + self.skew
+        self.buf = raw[start : start + total]
+        assert (self.buf.data_ptr() + self.band) % ALIGN == self.skew
         pat = torch.tensor(list(_SENTINEL[dtype]), dtype=torch.uint8)
         self.buf.copy_(pat.repeat(-(-total // len(pat)))[:total].to(self.device))  # (the band is a multiple of every item size)
         self.sentinel = pat.to(self.device)
@@ -98,15 +105,15 @@ class Guarded:
 
     # ---------------------------------------------------------------------------------------------------------- construction
     @classmethod
-    def input(cls, tensor, ld=None, pad=None, name="input"):
+    def input(cls, tensor, ld=None, pad=None, name="input", skew=0):
         """An operand the call only reads: `tensor` ([n, C] or any shape) inside NaN bands at row pitch `ld` >= C, its pad columns
         NaN too (`pad`: a finite value instead), and after the call not one byte of it may differ."""
         tensor = tensor.detach()
         if ld is None or tensor.dim() != 2:
-            return cls(tuple(tensor.shape), tensor.dtype, tensor.device, written=False, init=tensor, name=name)
+            return cls(tuple(tensor.shape), tensor.dtype, tensor.device, written=False, init=tensor, name=name, skew=skew)
         n, c = tensor.shape
         assert ld >= c
-        return cls((n, ld), tensor.dtype, tensor.device, written=False, init=tensor, cols=c, pad=pad, name=name)
+        return cls((n, ld), tensor.dtype, tensor.device, written=False, init=tensor, cols=c, pad=pad, name=name, skew=skew)
 
     def _mask(self, written):
         n = _prod(self.shape)

@@ -37,6 +37,72 @@ def test_layout():
     assert bool(torch.isnan(whole[:at]).all()) and bool(torch.isnan(whole[at + N * LD :]).all())
 
 
+@pytest.mark.parametrize("skew", [4, 8, 12, 252])
+def test_skewed_payload_keeps_every_check(skew):
+    """A payload that starts `skew` bytes behind the 256-byte boundary (a pointer that is not 16-byte aligned): the bands still touch
+    the payload at both ends, the sentinel stays element-aligned, and all three checks still fire."""
+    def pair():
+        g = torch.Generator().manual_seed(0)
+        x = torch.randn(N, C, generator=g)
+        return Guarded.input(x, ld=LD, name="x", skew=skew), Guarded((N, LD), cols=C, name="y", skew=skew), x
+
+    xg, yg, x = pair()
+    for g in (xg, yg):
+        assert g.ptr % ALIGN == skew and (g.ptr % 16 != 0) == (skew % 16 != 0)
+        assert g.buf.numel() == 2 * g.band + g.nbytes and g.buf.data_ptr() + g.band == g.ptr == g.t.data_ptr()
+        whole, at = g.whole()
+        assert whole[:at].view(torch.int32).unique().tolist() == [0x7FC0BEEF]  # element-aligned sentinel up to the payload
+        assert whole[at + N * LD :].view(torch.int32).unique().tolist() == [0x7FC0BEEF]
+    assert yg.t.view(torch.int32).unique().tolist() == [0x7FC0BEEF]
+    assert torch.equal(xg.logical(), x) and bool(torch.isnan(xg.t[:, C:]).all())
+    _scale(xg, yg)
+    check_all(xg, yg)
+    assert torch.equal(yg.logical(), 2 * x)
+    # one element past the end, one before the start
+    whole, at = yg.whole()
+    whole[at + N * LD] = 1.0
+    with pytest.raises(GuardError, match=rf"back band.*offset {N * LD * 4} .*4 byte"):
+        yg.check()
+    xg, yg, _ = pair()
+    _scale(xg, yg)
+    whole, at = yg.whole()
+    whole[at - 1] = 1.0
+    with pytest.raises(GuardError, match="front band.*offset -4 "):
+        yg.check()
+    # a stale element
+    xg, yg, _ = pair()
+    _scale(xg, yg, rows=N - 1)
+    with pytest.raises(GuardError, match=rf"still holds the sentinel.*offset {(N - 1) * LD * 4} .*{C * 4} byte"):
+        yg.check()
+    # a touched pad column, and a modified input
+    xg, yg, _ = pair()
+    _scale(xg, yg)
+    yg.t[2, C] = 0.0
+    with pytest.raises(GuardError, match=rf"must not write.*offset {(2 * LD + C) * 4} "):
+        yg.check()
+    xg.t[N - 1, C - 1] = 9.0
+    with pytest.raises(GuardError, match="x: .*must not write"):
+        xg.check()
+    # a byte workspace and an int64 buffer skew too
+    ws = Guarded(1001, torch.uint8, written="any", skew=skew)
+    ws.check()
+    ws.buf[ws.band + 1001] = 0
+    with pytest.raises(GuardError, match="back band.*offset 1001 .*1 byte"):
+        ws.check()
+    if skew % 8 == 0:
+        h = Guarded((3,), torch.int64, skew=skew)
+        assert h.ptr % ALIGN == skew and h.t.tolist() == [0x5A5A5A5A5A5A5A5A] * 3
+
+
+def test_skew_must_keep_elements_aligned():
+    with pytest.raises(AssertionError):
+        Guarded((4,), torch.float32, skew=2)
+    with pytest.raises(AssertionError):
+        Guarded((4,), torch.float64, skew=4)
+    with pytest.raises(AssertionError):
+        Guarded((4,), torch.float32, skew=256)
+
+
 def test_correct_kernel_is_accepted():
     xg, yg, x = _operands()
     _scale(xg, yg)
