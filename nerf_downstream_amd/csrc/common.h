@@ -46,6 +46,15 @@ __device__ __forceinline__ uint64_t mix64(uint64_t k) {  // splitmix64 finaliser
   return k;
 }
 
+// Non-finite values follow torch: a NaN goes through ReLU and wins every maximum, so that the training loops' finite-loss
+// guard sees it.  (fmaxf(x, 0.f) returns 0 for a NaN.)  For every number the results are those of fmaxf / `v > m`.
+__device__ __forceinline__ float relu_keep_nan(float x) { return x <= 0.f ? 0.f : x; }
+__device__ __forceinline__ float4 relu_keep_nan(const float4 &v) {
+  return make_float4(relu_keep_nan(v.x), relu_keep_nan(v.y), relu_keep_nan(v.z), relu_keep_nan(v.w));
+}
+// does v replace the running maximum m?  A NaN replaces a number and is never replaced (the first NaN in scan order stays).
+__device__ __forceinline__ bool max_replaces(float v, float m) { return !(v <= m) && m == m; }
+
 // (b,x,y,z) -> 16|16|16|16 bit key; returns false when a field does not fit.
 __device__ __forceinline__ bool pack_key(int b, int x, int y, int z, uint64_t &key) {
   const unsigned ux = (unsigned)(x + 32768), uy = (unsigned)(y + 32768), uz = (unsigned)(z + 32768);

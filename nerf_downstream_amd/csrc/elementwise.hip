@@ -452,7 +452,7 @@ __global__ __launch_bounds__(kSmallT) void bn_small_fwd_kernel(const float *__re
       o.x = (v[u].x - mu.x) * is.x * g.x + b.x, o.y = (v[u].y - mu.y) * is.y * g.y + b.y;
       o.z = (v[u].z - mu.z) * is.z * g.z + b.z, o.w = (v[u].w - mu.w) * is.w * g.w + b.w;
       o.x += rs[u].x, o.y += rs[u].y, o.z += rs[u].z, o.w += rs[u].w;
-      if (relu) o.x = fmaxf(o.x, 0.f), o.y = fmaxf(o.y, 0.f), o.z = fmaxf(o.z, 0.f), o.w = fmaxf(o.w, 0.f);
+      if (relu) o = relu_keep_nan(o);
       st4(out + off[u], o);
     }
   }
@@ -560,7 +560,7 @@ __global__ __launch_bounds__(EB) void bn_apply_kernel(const float *__restrict__ 
       const float4 r = ld4(residual + 4 * i);
       o.x += r.x, o.y += r.y, o.z += r.z, o.w += r.w;
     }
-    if (relu) o.x = fmaxf(o.x, 0.f), o.y = fmaxf(o.y, 0.f), o.z = fmaxf(o.z, 0.f), o.w = fmaxf(o.w, 0.f);
+    if (relu) o = relu_keep_nan(o);
     st4(y + 4 * i, o);
   }
 }
@@ -659,7 +659,7 @@ __global__ __launch_bounds__(EB) void bn_apply_fold_kernel(const float *__restri
       const float4 r = ld4(residual + o_);
       o.x += r.x, o.y += r.y, o.z += r.z, o.w += r.w;
     }
-    if (relu) o.x = fmaxf(o.x, 0.f), o.y = fmaxf(o.y, 0.f), o.z = fmaxf(o.z, 0.f), o.w = fmaxf(o.w, 0.f);
+    if (relu) o = relu_keep_nan(o);
     st4(y + o_, o);
   }
 }
@@ -718,7 +718,7 @@ __global__ __launch_bounds__(EB) void sgd_flat_kernel(float *__restrict__ w, flo
   }
 }
 
-// mode 0: y = max(a,0); mode 1: y = b>0 ? a : 0; mode 2: y = a + b
+// mode 0: y = relu(a) (a NaN stays); mode 1: y = b>0 ? a : 0; mode 2: y = a + b
 __global__ __launch_bounds__(EB) void eltwise_kernel(const float *__restrict__ a, const float *__restrict__ b,
                                                      int64_t count, int mode, float *__restrict__ y) {
   const int64_t n4 = count >> 2;
@@ -726,7 +726,7 @@ __global__ __launch_bounds__(EB) void eltwise_kernel(const float *__restrict__ a
     const float4 va = ld4(a + 4 * i);
     float4 o;
     if (mode == 0) {
-      o = make_float4(fmaxf(va.x, 0.f), fmaxf(va.y, 0.f), fmaxf(va.z, 0.f), fmaxf(va.w, 0.f));
+      o = relu_keep_nan(va);
     } else {
       const float4 vb = ld4(b + 4 * i);
       if (mode == 1)
@@ -739,7 +739,7 @@ __global__ __launch_bounds__(EB) void eltwise_kernel(const float *__restrict__ a
   }
   if (blockIdx.x == 0 && threadIdx.x < (count & 3)) {
     const int64_t i = (n4 << 2) + threadIdx.x;
-    y[i] = mode == 0 ? fmaxf(a[i], 0.f) : (mode == 1 ? (b[i] > 0.f ? a[i] : 0.f) : a[i] + b[i]);
+    y[i] = mode == 0 ? relu_keep_nan(a[i]) : (mode == 1 ? (b[i] > 0.f ? a[i] : 0.f) : a[i] + b[i]);
   }
 }
 
@@ -800,8 +800,8 @@ __global__ __launch_bounds__(EB) void bn_relu_pool_fwd_kernel(const float *__res
   const float4 sh = make_float4(b.x - mu.x * sc.x, b.y - mu.y * sc.y, b.z - mu.z * sc.z, b.w - mu.w * sc.w);
   float4 s = make_float4(0, 0, 0, 0);
   auto add = [&](const float4 &v) {
-    s.x += fmaxf((v.x - mu.x) * is.x * g.x + b.x, 0.f), s.y += fmaxf((v.y - mu.y) * is.y * g.y + b.y, 0.f);
-    s.z += fmaxf((v.z - mu.z) * is.z * g.z + b.z, 0.f), s.w += fmaxf((v.w - mu.w) * is.w * g.w + b.w, 0.f);
+    s.x += relu_keep_nan((v.x - mu.x) * is.x * g.x + b.x), s.y += relu_keep_nan((v.y - mu.y) * is.y * g.y + b.y);
+    s.z += relu_keep_nan((v.z - mu.z) * is.z * g.z + b.z), s.w += relu_keep_nan((v.w - mu.w) * is.w * g.w + b.w);
   };
   if (K == 8) {  // (uniform) the 2^3 pooling of the stem: the eight children's rows are requested together -- one memory
                  // round trip per thread instead of eight dependent index -> row chains (75 -> 5x us at B=16)
@@ -896,10 +896,10 @@ __global__ __launch_bounds__(EB) void pool_max_fwd_kernel(const float *__restric
     const int i = nbr[o * K + k];
     if (i >= 0) {
       const float4 v = ld4(x + (int64_t)i * (4 * C4) + c);
-      if (v.x > m.x || a.x < 0) m.x = v.x, a.x = i;  // (a NaN never wins, like torch keeps the first element then)
-      if (v.y > m.y || a.y < 0) m.y = v.y, a.y = i;
-      if (v.z > m.z || a.z < 0) m.z = v.z, a.z = i;
-      if (v.w > m.w || a.w < 0) m.w = v.w, a.w = i;
+      if (a.x < 0 || max_replaces(v.x, m.x)) m.x = v.x, a.x = i;  // (torch's rule: the first NaN of the window wins, else
+      if (a.y < 0 || max_replaces(v.y, m.y)) m.y = v.y, a.y = i;  //  the first of the largest numbers)
+      if (a.z < 0 || max_replaces(v.z, m.z)) m.z = v.z, a.z = i;
+      if (a.w < 0 || max_replaces(v.w, m.w)) m.w = v.w, a.w = i;
     }
   }
   st4(y + o * (int64_t)(4 * C4) + c, m);

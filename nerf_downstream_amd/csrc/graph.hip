@@ -230,7 +230,8 @@ __global__ __launch_bounds__(256) void edge_fwd_kernel(const float *__restrict__
   int at = 0;
   for (int j = 1; j < k; ++j) {
     const float z = edge_z(edge_xhat(P[edge_row(idx, i * k + j, n) * C + c], q, mu, is), g, bt);
-    if (z > best) best = z, at = j;  // (LeakyReLU is increasing: the maximum of z is the maximum of lrelu(z))
+    if (max_replaces(z, best)) best = z, at = j;  // (LeakyReLU is increasing: the maximum of z is the maximum of lrelu(z);
+                                                  //  the first NaN wins, as in torch)
   }
   y[i * C + c] = best > 0.f ? best : 0.2f * best;
   arg[i * C + c] = (uint8_t)at;

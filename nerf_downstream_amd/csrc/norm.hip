@@ -182,7 +182,7 @@ __global__ __launch_bounds__(NB) void in_apply_kernel(const float *__restrict__ 
     }
     if (relu) {
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) v[k] = fmaxf(v[k], 0.f);
+      for (int k = 0; k < VEC; ++k) v[k] = relu_keep_nan(v[k]);
     }
     stv<VEC>(y + i * VEC, v);
   }
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(NB) void ln_fwd_kernel(const float *__restrict__ x,
         }
         if (relu) {
 #pragma unroll
-          for (int k = 0; k < VEC; ++k) r[k] = fmaxf(r[k], 0.f);
+          for (int k = 0; k < VEC; ++k) r[k] = relu_keep_nan(r[k]);
         }
         stv<VEC>(y + o, r);
       }

@@ -11,16 +11,19 @@
 // nbr[o][k] = i, the windows that contain row i), again k ascending: one owner per element, no atomics, a fixed order.
 //   average: y[o] = (sum of the present rows) / cnt[o], cnt[o] = number of present entries -- NOT the kernel volume; one true
 //            fp32 division per element (dx[i] = sum of dy[o] / cnt[o], the same division per term)
-//   max    : the first present entry in offset order wins a tie (v > m only replaces); arg[o][c] = its input row.  A row
-//            with no present entry gets y = 0, arg = -1.  A NaN never replaces a number.
+//   max    : the first present entry in offset order wins a tie (only a larger value replaces); arg[o][c] = its input row.
+//            A row with no present entry gets y = 0, arg = -1.  A NaN replaces a number and is never replaced, so the
+//            first NaN in offset order is the result and the arg: torch's rule (the value of max_pool1d / amax, the
+//            index of max(dim)).
 //
 // Global pools.  Sample b owns rows [off[b], off[b+1]) (the manager's device-resident offsets; never read by the host).  The
 // launch shape is the per-sample chunked reduction of rowpass.h: grid (G, B, channel slabs), every sample cut into the same
 // number G of row chunks chosen from n and B alone, one partial per workgroup, then one wave per (sample, channel) combines
 // the G partials -- lane l takes partials l, l + 64, ... in order, then a fixed butterfly.  Two launches forward, one
 // backward, whatever B is.  An empty sample finds an empty range: y = 0, arg = -1.
-//   max: the combine rule is a total order (larger value, then lower row), so arg[b][c] is the LOWEST row attaining the
-//        maximum however the rows were spread over threads.  Backward is one pass over the rows of dx that compares the row
+//   max: the combine rule is a total order (a NaN above every number as in torch, then the larger value, then the lower
+//        row), so arg[b][c] is the LOWEST row attaining the maximum -- the first NaN of the sample if it has one -- however
+//        the rows were spread over threads.  Backward is one pass over the rows of dx that compares the row
 //        index with arg: dx[i][c] = arg[b][c] == i ? dy[b][c] : 0 -- no scatter.
 //   sum: accumulated in DOUBLE from the first add on and rounded to fp32 once; backward dx[i] = dy[b].
 // Determinism: rows -> threads -> partials -> results is a fixed assignment in a fixed order: two runs are bitwise equal.
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(PB) void pool_local_max_fwd_kernel(const float *__r
         ldv<VEC>(x + (int64_t)i * ldx + c, v);
 #pragma unroll
         for (int j = 0; j < VEC; ++j)
-          if (a[j] < 0 || v[j] > m[j]) m[j] = v[j], a[j] = i;  // (the lowest k wins a tie)
+          if (a[j] < 0 || max_replaces(v[j], m[j])) m[j] = v[j], a[j] = i;  // (the lowest k wins a tie)
       }
     }
     stv<VEC>(y + o * C + c, m);
@@ -158,10 +161,12 @@ __global__ __launch_bounds__(PB) void pool_local_max_bwd_kernel(const float *__r
 }
 
 // ------------------------------------------------------------------------------------------------ global pools
-// (m, a) <- the better of (m, a) and (v, r): a present candidate (r >= 0) beats an absent one, then the larger value, then
-// the lower row.  Symmetric, so both sides of a butterfly exchange end with the same pair.
+// (m, a) <- the better of (m, a) and (v, r): a present candidate (r >= 0) beats an absent one, then a NaN beats a number,
+// then the larger value, then the lower row (also between two NaNs).  A total order, so both sides of a butterfly exchange
+// end with the same pair, NaN or not.
 __device__ __forceinline__ void max_take(float &m, int &a, float v, int r) {
-  if (r >= 0 && (a < 0 || v > m || (v == m && r < a))) m = v, a = r;
+  const bool tie = v == m || (v != v && m != m);
+  if (r >= 0 && (a < 0 || max_replaces(v, m) || (tie && r < a))) m = v, a = r;
 }
 
 // Chunk g of sample b -> pval / parg [b][g][C].  A thread owns VEC channels (column group cg) and the rows rl, rl + rlanes,
@@ -187,7 +192,7 @@ __global__ __launch_bounds__(PB) void gmax_partial_kernel(const float *__restric
       ldv<VEC>(x + row * ldx + c, v);
 #pragma unroll
       for (int k = 0; k < VEC; ++k)
-        if (a[k] < 0 || v[k] > m[k]) m[k] = v[k], a[k] = (int)row;
+        if (a[k] < 0 || max_replaces(v[k], m[k])) m[k] = v[k], a[k] = (int)row;
     }
   }
   if (rl < rlanes) {

@@ -738,7 +738,7 @@ class BatchNormFunction(torch.autograd.Function):
         n, C = x.shape
         dev = x.device
         if not ctx.training:  # eval-mode BN is an affine map; rarely differentiated
-            g = gy * (y > 0) if ctx.relu else gy
+            g = torch.where(y > 0, gy, torch.zeros_like(gy)) if ctx.relu else gy  # (0 where masked, whatever gy holds)
             xhat = (x - mean) * invstd
             return (g * (gamma * invstd), (g * xhat).sum(0), g.sum(0), None, None, None, None, None,
                     g if ctx.has_res else None, None, None)

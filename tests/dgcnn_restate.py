@@ -96,7 +96,8 @@ def edges(x, W, idx):
 
 def first_argmax(z):
     """The lowest slot attaining the maximum over dim 1 of z [n, k, C] -> int64 [n, C]."""
-    hit = z == z.max(1, keepdim=True).values
+    top = z.max(1, keepdim=True).values  # (a NaN is the maximum, the first one the arg: torch's rule)
+    hit = (z == top) | (torch.isnan(z) & torch.isnan(top))
     k = z.shape[1]
     slots = torch.arange(k).reshape(1, k, 1).expand_as(z)
     return torch.where(hit, slots, torch.full_like(slots, k)).min(1).values

@@ -63,7 +63,7 @@ def instance_norm_bwd(dy, x, offsets, gamma, beta, eps, residual=None, relu=Fals
     if relu:
         if mask is None:
             mask = instance_norm_fwd(x, offsets, gamma, beta, eps, residual, True) > 0
-        g = dy * _f64(mask)
+        g = torch.where(mask.cpu().bool(), dy, torch.zeros_like(dy))  # (torch's threshold_backward: 0, also for a NaN dy)
     off = [int(o) for o in offsets]
     dx = torch.empty_like(x)
     for b in range(len(off) - 1):
@@ -95,7 +95,7 @@ def layer_norm_bwd(dy, x, gamma, beta, eps, residual=None, relu=False, mask=None
     if relu:
         if mask is None:
             mask = layer_norm_fwd(x, gamma, beta, eps, residual, True) > 0
-        g = dy * _f64(mask)
+        g = torch.where(mask.cpu().bool(), dy, torch.zeros_like(dy))  # (torch's threshold_backward: 0, also for a NaN dy)
     gh = g * gamma
     dx = invstd * (gh - gh.mean(1, keepdim=True) - xhat * (gh * xhat).mean(1, keepdim=True))
     return dx, (g * xhat).sum(0), g.sum(0), g

@@ -10,7 +10,8 @@ floor(c / (ts s)) (ts s), unique, in first-occurrence order (the backend's order
 Operators, all float64 torch (the forwards are differentiable, the backwards are the explicit formulas):
   sum    y[o] = sum of the present x[table[o][j]]                         dx[i] = sum over (o, j) with table[o][j] = i of dy[o]
   avg    y[o] = that sum / cnt[o], cnt[o] = number of present entries     dx[i] = sum ... of dy[o] / cnt[o]
-  max    y[o][c] = max over the present entries, arg[o][c] = its row, the lowest j on a tie; no entry: 0 / -1
+  max    y[o][c] = max over the present entries, arg[o][c] = its row, the lowest j on a tie; no entry: 0 / -1; a NaN is the
+         maximum (torch's max_pool1d, amax, max(dim)) and the first NaN the arg (torch's max(dim))
          dx[i][c] = sum over the windows o that contain i of dy[o][c] where arg[o][c] = i
   global max / sum over the row ranges [off[b], off[b+1]): the lowest row wins a tie; an empty sample gives 0 / -1
 `*_abs` return the sum of the absolute values entering every output entry -- what an fp32 summation's rounding is
@@ -114,7 +115,9 @@ def max_fwd(x, table):
     v = _gather(x, table)
     v = torch.where((table >= 0)[:, :, None], v, torch.full_like(v, -float("inf")))
     y = v.max(1).values
-    first = torch.where(v == y[:, None, :], torch.arange(K)[None, :, None], K).min(1).values  # lowest j attaining the maximum
+    # the lowest present j attaining the maximum; a NaN is the maximum (torch's rule) and `==` does not find it
+    hit = ((v == y[:, None, :]) | (torch.isnan(v) & torch.isnan(y)[:, None, :])) & (table >= 0)[:, :, None]
+    first = torch.where(hit, torch.arange(K)[None, :, None], K).min(1).values
     empty = counts(table) == 0
     arg = torch.gather(table, 1, first.clamp_max(K - 1))
     y = torch.where(empty[:, None], torch.zeros_like(y), y)
@@ -131,7 +134,8 @@ def max_fwd_forced(x, arg):
 
 def max_bwd(dy, arg, table, n_in):
     """dx[i][c] = sum over the windows o containing i of dy[o][c] where arg[o][c] = i."""
-    terms = dy.to(F64)[:, None, :] * (arg[:, None, :] == table[:, :, None]).to(F64)
+    g = dy.to(F64)[:, None, :]
+    terms = torch.where(arg[:, None, :] == table[:, :, None], g, torch.zeros_like(g))  # (a row not chosen receives 0, not 0 x dy)
     return _scatter(terms, table, n_in)
 
 
@@ -149,7 +153,8 @@ def global_max_fwd(x, off):
         if hi > lo:
             seg = x[lo:hi].to(F64)
             y[b] = seg.max(0).values
-            arg[b] = torch.where(seg == y[b][None], torch.arange(hi - lo)[:, None], hi - lo).min(0).values + lo
+            hit = (seg == y[b][None]) | (torch.isnan(seg) & torch.isnan(y[b])[None])  # (a NaN is the maximum, the first one the arg)
+            arg[b] = torch.where(hit, torch.arange(hi - lo)[:, None], hi - lo).min(0).values + lo
     return y, arg
 
 

@@ -23,13 +23,15 @@ def ce(z, labels, weight=None, ignore=-100):
     lse = mx + np.log(np.exp(z - mx[:, None]).sum(1))
     y = np.where(valid, np.asarray(labels).astype(np.int64), 0)
     wy = np.where(valid, w[y], 0.0)
-    num = float((wy * (lse - z[np.arange(n), y])).sum())
+    with np.errstate(invalid="ignore"):
+        num = float(np.where(valid, wy * (lse - z[np.arange(n), y]), 0.0).sum())  # (a row left out contributes 0, whatever it holds)
     den = float(wy.sum())
     with np.errstate(invalid="ignore", divide="ignore"):
         loss = np.float64(num) / np.float64(den)
     onehot = np.zeros_like(z)
     onehot[np.arange(n), y] = 1.0
-    grad = (wy / den)[:, None] * (np.exp(z - lse[:, None]) - onehot) if den != 0 else np.zeros_like(z)
+    with np.errstate(invalid="ignore"):
+        grad = np.where(valid[:, None], (wy / den)[:, None] * (np.exp(z - lse[:, None]) - onehot), 0.0) if den != 0 else np.zeros_like(z)
     return {"loss": float(loss), "num": num, "den": den, "lse": lse, "grad": grad, "wy": wy}
 
 

@@ -360,7 +360,7 @@ def _write_co3d_scenes(root, n_scenes=16):
 
 
 @pytest.mark.long
-@pytest.mark.timeout(120)
+@pytest.mark.timeout(240)  # (host-bound: five train() runs with DataLoader workers, 45-90 s inside the whole suite, more on a busy host)
 def test_train_on_co3d_format_compact_equals_decoded(tmp_path, monkeypatch):
     """train() on a tiny tree in the reference's on-disk format, DataLoader workers included: the
     compact path (GPU-side decode) and the ordinary path (CPU decode) give the same loss history -- and so do the three ways a
