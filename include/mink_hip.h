@@ -1137,6 +1137,44 @@ int mink_paconv_score_bwd(const float *dA, const float *dCX, int64_t ldz, const 
 int mink_paconv_scatter_bwd(const float *dA, const float *dCX, int64_t ldz, const float *s, const float *S, const int32_t *members,
                             const int32_t *seg, int64_t n, int32_t k, int32_t M, int32_t Cin, float *dx, void *stream);
 
+/* ------------------------------------------------------------------ scene sub-sampling (csrc/sample.hip)
+ * Farthest-point sampling of every scene of a batch (reference co3d_3d/src/data/transforms.py FarthestPointSample.sample: a loop
+ * of num_points iterations over all voxels of a scene, on the CPU).  Nothing is read back by the call.
+ *
+ * mink_fps_scenes: xyz[n][ld] row-major fp32, 3 <= ld <= MINK_FPS_MAX_LD, only columns 0..2 are read (a [n][3] matrix, or columns 1..3 of a float
+ *   [n][4] coordinate matrix through a pointer one float in: no alignment beyond 4 bytes is asked for).  Scene b = rows
+ *   offsets[b] .. offsets[b+1] (int32 [B + 1], device, never read by the host); start[b] (int32 [B], device) = the scene-local
+ *   row of its first pick.  idx[b][0..m) (int32 [B][m]) = the GLOBAL rows (offsets[b] + local row) picked, in pick order.  Per scene:
+ *       dist[i] = 1e10f;  cur = start[b];
+ *       m times:  emit cur;  for every row i: d = ((dx dx) + (dy dy)) + (dz dz) with dx = x_i - x_cur, ..., every difference,
+ *                 product and sum rounded to fp32 on its own (no fused multiply-add);  dist[i] = d where d < dist[i];
+ *                 cur = the row with the largest dist, ties to the LOWEST row (as torch.argmax).
+ *   So with fewer distinct positions than m, once all are taken every distance is 0 and the remaining picks are local row 0; and
+ *   a coincident point is never picked while a point at positive distance remains.  m may exceed the scene's size.
+ *   One workgroup of MINK_FPS_THREADS threads per scene; no workgroup waits for another.  Where a scene's coordinates and
+ *   running distances live depends on its size alone, and the picks do not depend on it:
+ *       rows <= MINK_FPS_XYZ_REG_ROWS_SMALL, <= MINK_FPS_XYZ_REG_ROWS : both in registers (2 / 8 rows per thread)
+ *       rows <= MINK_FPS_DIST_REG_ROWS : distances in registers (56 per thread), coordinates re-read from memory every pick
+ *       larger : distances in `workspace` (n_max floats per scene), coordinates re-read every pick
+ *   Each of the four is a launch of its own over the B scenes (a workgroup whose scene belongs to another leaves at once; one that
+ *   no scene of at most n_max rows can need is not launched), so scenes of different residencies run one group after the other.
+ *   n = rows of xyz (1 <= n < 2^31); n_max = the caller's bound on the largest scene (1 <= n_max <= n; n itself always serves);
+ *   workspace_bytes >= mink_fps_workspace_bytes(n_max, B) (0 up to MINK_FPS_DIST_REG_ROWS: workspace may then be NULL); B m < 2^31.
+ *   status (int32 [1], device; zeroed by the call, then OR-ed): a scene that is empty or whose offsets leave [0, n]
+ *   (MINK_FPS_EMPTY_SCENE), whose start lies outside it (MINK_FPS_BAD_START) or that holds more than n_max rows
+ *   (MINK_FPS_SCENE_TOO_LARGE) is not read at all: its m picks are -1 and the bit is set; the other scenes are sampled. */
+#define MINK_FPS_THREADS 1024
+#define MINK_FPS_MAX_LD 4096
+#define MINK_FPS_XYZ_REG_ROWS_SMALL 2048
+#define MINK_FPS_XYZ_REG_ROWS 8192
+#define MINK_FPS_DIST_REG_ROWS 57344
+#define MINK_FPS_EMPTY_SCENE 1
+#define MINK_FPS_BAD_START 2
+#define MINK_FPS_SCENE_TOO_LARGE 4
+int64_t mink_fps_workspace_bytes(int64_t n_max, int32_t B);
+int mink_fps_scenes(const float *xyz, int64_t n, int64_t ld, const int32_t *offsets, const int32_t *start, int32_t B, int32_t m,
+                    int64_t n_max, int32_t *idx, int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

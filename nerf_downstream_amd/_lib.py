@@ -256,7 +256,13 @@ SIGNATURES = {
     "mink_paconv_gather": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _i64, _p, _p]),
     "mink_paconv_score_bwd": (ctypes.c_int, [_p, _p, _i64, _p, _p, _i64, _i32, _i32, _i32, _p, _p]),
     "mink_paconv_scatter_bwd": (ctypes.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _p]),
+    "mink_fps_workspace_bytes": (_i64, [_i64, _i32]),
+    "mink_fps_scenes": (ctypes.c_int, [_p, _i64, _i64, _p, _p, _i32, _i32, _i64, _p, _p, _p, _i64, _p]),
 }
+
+# MINK_FPS_* of include/mink_hip.h: the scene sizes at which mink_fps_scenes changes where a scene lives, and its status bits
+FPS_XYZ_REG_ROWS_SMALL, FPS_XYZ_REG_ROWS, FPS_DIST_REG_ROWS = 2048, 8192, 57344
+FPS_EMPTY_SCENE, FPS_BAD_START, FPS_SCENE_TOO_LARGE = 1, 2, 4
 
 
 def build(force=False):

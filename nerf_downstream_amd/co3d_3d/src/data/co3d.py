@@ -8,7 +8,9 @@ Scene directory `<data_root>/plenoxel_co3d_<scene>/data.npz` holds
 `filelist/<phase>.txt` (relative to the CWD, like the reference :100) lists "<class> <scene>".
 Sample dict / feature selection follow co3d.py:185-242.  Augmentations (`train_transformations`, names of
 classes in transforms.py as in configs/co3d_aug3.gin) are only DRAWN here: the sample carries its
-parameter row (`aug_params`, `aug_stream`) and the batch is transformed on the GPU (transforms.py)."""
+parameter row (`aug_params`, `aug_stream`) and the batch is transformed on the GPU (transforms.py).  A recipe may also name
+one sampler of data/sampling.py (`FarthestPointSample`, `RandomSample`): its plan travels the same way (`fps_start` or
+`sample_rows`, `sample_points`) and the rows are taken on the GPU before the program runs."""
 import os
 
 import numpy as np
@@ -18,7 +20,7 @@ from torch.utils.data import Dataset
 from nerf_downstream_amd import gin_lite as gin
 from nerf_downstream_amd.safe_load import load_checkpoint_file
 
-from . import transforms
+from . import sampling, transforms
 
 CLASSES = (
     "apple backpack ball banana baseballbat baseballglove bench bicycle book bottle bowl broccoli cake car carrot "
@@ -122,10 +124,13 @@ class Co3DDatasetBase(Dataset):
         batch reaches the model (`MinkowskiBaseModel.process_input`), "xyzs" (a per-scene reduction) included."""
         phase = "test" if phase in ("val", "test") else "train"  # reference :84 (val == test list)
         names = list(train_transformations if phase == "train" else eval_transformations)
-        unknown = [t for t in names if not hasattr(getattr(transforms, t, None), "draw")]
+        # names are looked up in transforms first, then in sampling (FarthestPointSample / RandomSample: no stage of the program)
+        unknown = [t for t in names if not hasattr(getattr(transforms, t, None), "draw") and t not in sampling.SAMPLERS]
         if unknown:
             raise NotImplementedError(f"augmentations {unknown} have no GPU counterpart (supported: the classes of "
                                       "data/transforms.py)")
+        names, sampler = sampling.split_recipe(names)
+        self.sampler = getattr(sampling, sampler)() if sampler else None
         self.transformations = transforms.Compose([getattr(transforms, t)() for t in names]) if names else None
         self.phase, self.data_root, self.features = phase, data_root, list(features)
         self.compact = bool(compact)
@@ -176,7 +181,7 @@ class Co3DDatasetBase(Dataset):
                 sample = dict(sample, links=sample["links"][k], density=sample["density"][k], sh_q=sample["sh_q"][k])
             sample["labels"] = np.array([self.CLASS_LABELS.index(label)])
             sample["feature_names"] = tuple(self.features)
-            return self._with_program(sample)
+            return self._with_program(sample, int(sample["links"].shape[0]))
         links, density, sh, reso = self.load_data(inst_id)
         keep = self.transformations.row_mask(density.numpy()) if self.transformations is not None else None
         if keep is not None:
@@ -188,7 +193,7 @@ class Co3DDatasetBase(Dataset):
         feats, xyzs = select_features(coordinates, density.reshape(-1, 1), sh.reshape(len(links), -1), self.features)
         return self._with_program({"coordinates": coordinates, "features": feats, "xyzs": xyzs,
                                    "labels": np.array([self.CLASS_LABELS.index(label)]),
-                                   "feature_names": tuple(self.features)})
+                                   "feature_names": tuple(self.features)}, int(coordinates.shape[0]))
 
     def sample_lengths(self):
         """Voxel count of every scene, read from the `links` array header inside each data.npz (no array data is
@@ -209,7 +214,9 @@ class Co3DDatasetBase(Dataset):
             self._lengths = out
         return self._lengths
 
-    def _with_program(self, sample):
+    def _with_program(self, sample, n_rows):
+        if self.sampler is not None:  # which rows to keep: drawn here over the rows the filters left, taken on the GPU
+            sample.update(self.sampler.plan(n_rows))
         if self.transformations is not None:  # drawn here (DataLoader worker), applied on the GPU
             params, stream = self.transformations.sample()
             sample["aug_params"], sample["aug_stream"] = torch.from_numpy(params), stream

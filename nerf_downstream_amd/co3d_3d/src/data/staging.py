@@ -196,6 +196,8 @@ class DirectCompactLoader:
         import os
 
         t = getattr(dataset, "transformations", None)
+        if getattr(dataset, "sampler", None) is not None:  # (the sampler's plan is drawn per sample and batched by collate_mink)
+            return False
         if not (bool(getattr(dataset, "compact", False)) and hasattr(dataset, "files") and (t is None or not getattr(t, "prefilters", ()))):
             return False
         n = len(dataset.files)

@@ -37,7 +37,7 @@ def collate_mink(list_data):
         if len(resos) != 1:
             raise ValueError(f"one batch mixes grid resolutions {sorted(resos)} (data.npz scenes are 128^3, last.ckpt scenes 256^3)")
         package["reso"] = resos.pop()
-        return _with_programs(package, list_data, n)
+        return _with_sampler(_with_programs(package, list_data, n), list_data, n)
     coords, feats = me_utils.sparse_collate(
         [d["coordinates"] for d in list_data], [d["features"] for d in list_data], dtype=torch.float32
     )
@@ -49,7 +49,7 @@ def collate_mink(list_data):
         if key in list_data[0]:
             package[key] = [d[key] for d in list_data]
     n = [int(d["coordinates"].shape[0]) for d in list_data]
-    return _with_points(_with_programs(package, list_data, n), list_data, n)
+    return _with_sampler(_with_points(_with_programs(package, list_data, n), list_data, n), list_data, n)
 
 
 def _with_programs(package, list_data, n):
@@ -61,6 +61,23 @@ def _with_programs(package, list_data, n):
         package["aug_streams"] = torch.from_numpy(streams.view(np.int32).copy())
         package["aug_seed"] = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64))
         package.setdefault("scene_offsets", torch.tensor(np.concatenate([[0], np.cumsum(n)]), dtype=torch.int32))
+        package.setdefault("feature_names", list_data[0].get("feature_names"))
+    return package
+
+
+def _with_sampler(package, list_data, n):
+    """The plan of the recipe's sampler (data/sampling.py), one per scene: `fps_start` int32 [B], the scene-local row of the
+    first farthest-point pick, or `sample_rows` int64 [B, m], the drawn rows as GLOBAL rows of the batch; `sample_points` = m
+    and `sample_n_max`, the largest scene (host ints).  The rows are taken on the GPU in process_input."""
+    if "sample_points" in list_data[0]:
+        offs = np.concatenate([[0], np.cumsum(n)])
+        package["sample_points"], package["sample_n_max"] = int(list_data[0]["sample_points"]), int(max(n))
+        if "fps_start" in list_data[0]:
+            package["fps_start"] = torch.tensor([int(d["fps_start"]) for d in list_data], dtype=torch.int32)
+        else:
+            package["sample_rows"] = torch.from_numpy(np.stack([np.asarray(d["sample_rows"], np.int64) + offs[j]
+                                                                 for j, d in enumerate(list_data)]))
+        package.setdefault("scene_offsets", torch.tensor(offs, dtype=torch.int32))
         package.setdefault("feature_names", list_data[0].get("feature_names"))
     return package
 

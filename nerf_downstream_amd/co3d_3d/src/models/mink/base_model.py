@@ -25,6 +25,7 @@ class MinkowskiBaseModel(_HIP_ME.MinkowskiNetwork, InputInterface):
         self._coord_plan = None
         self._recent_traces = []  # map-request traces of the last few fields (filled by their forward pass)
         self._side = None
+        self._sampler_status = None  # (pinned status word of the last mink_fps_scenes call, event recorded after its copy)
         # (MINK_PREPARE_AHEAD=0: every batch's maps are built on the compute stream, on demand -- the A/B switch of the trainer CLI)
         self.prepare_ahead = os.environ.get("MINK_PREPARE_AHEAD", "1") != "0"
 
@@ -38,6 +39,9 @@ class MinkowskiBaseModel(_HIP_ME.MinkowskiNetwork, InputInterface):
             with self._prepare_stream_ctx(batch["links"], fence=batch.get("h2d_event", True)):
                 coords, feats = ME.utils.decode_plenoxel_batch(batch)
             batch = dict(batch, coordinates=coords, features=feats)
+        if "sample_points" in batch:  # the recipe's sampler (data/sampling.py): a fixed number of rows per scene, taken here
+            with self._prepare_stream_ctx(batch["coordinates"], fence=batch.get("h2d_event", True)):
+                batch = self._sample(batch, status_async=defer)
         if "ds_params" in batch:  # raw point clouds (ScannetDataset): down-sampled, then the drawn programs, all on the device
             if not getattr(ME, "SUPPORTS_PREPARE_AHEAD", False):
                 raise RuntimeError("point clouds are prepared by the HIP backend (mink_voxel_downsample_scenes)")
@@ -74,6 +78,44 @@ class MinkowskiBaseModel(_HIP_ME.MinkowskiNetwork, InputInterface):
             tf = ME.TensorField(coordinates=coords, features=feats, plan=self._coord_plan or [], defer=defer)
         self._recent_traces = [tf.coordinate_manager.trace] + self._recent_traces[:2]
         return _with_rows(tf, batch)
+
+    def _sample(self, batch, status_async=False):
+        """The batch cut down to `sample_points` rows per scene: the farthest-point picks from `fps_start` (mink_fps_scenes)
+        or the host-drawn `sample_rows`, gathered in pick order; `scene_offsets` becomes the new one.  Both sizes are fixed, so
+        nothing is waited for: with `status_async` the kernel's status word is looked at when the next batch comes in."""
+        import torch
+
+        ME, coords, m = self._ME, batch["coordinates"], int(batch["sample_points"])
+        if self._sampler_status is not None:  # the previous batch's: long there
+            self._check_sampler_status()
+        if "fps_start" not in batch:
+            idx = batch["sample_rows"].to(coords.device).long().reshape(-1, m)
+        elif getattr(ME, "SUPPORTS_PREPARE_AHEAD", False):
+            if not coords.is_cuda:
+                raise RuntimeError("FarthestPointSample runs on the GPU: move the batch to cuda first")
+            out = ME.utils.farthest_point_sample(coords[:, 1:4], batch["scene_offsets"], m, batch["fps_start"],
+                                                 n_max=batch.get("sample_n_max"), status_async=status_async)
+            idx = out[0] if status_async else out
+            if status_async:
+                self._sampler_status = out[1]
+        else:  # the CPU backend of the trainer tests
+            from nerf_downstream_amd.co3d_3d.src.data.sampling import fps_numpy
+
+            idx = torch.from_numpy(fps_numpy(coords[:, 1:4].float().numpy(), batch["scene_offsets"].numpy(), m,
+                                             batch["fps_start"].numpy()))
+        from nerf_downstream_amd.minkowski.utils import sample_scene_rows
+
+        drop = ("sample_points", "sample_rows", "fps_start", "sample_n_max", "links", "density", "sh_q")
+        out = {k: v for k, v in batch.items() if k not in drop}
+        out["coordinates"], out["features"], out["scene_offsets"] = sample_scene_rows(coords, batch["features"], idx)
+        return out
+
+    def _check_sampler_status(self):
+        from nerf_downstream_amd.minkowski.utils import fps_status_check
+
+        (host, event), self._sampler_status = self._sampler_status, None
+        event.synchronize()
+        fps_status_check(host)
 
     def _augment(self, batch, count_async=False):
         """-> (coordinates, features, source rows or None, pending count or None)"""

@@ -344,6 +344,72 @@ def prepare_point_batch(batch, count_async=False):
     return c[:k], f[:k], labels[:k], src[:k]
 
 
+class SampleSceneError(RuntimeError):
+    """`mink_fps_scenes` left a scene unsampled: it is empty (or its offsets leave the matrix), its first pick lies outside
+    it, or it holds more rows than the caller's bound."""
+
+
+def fps_status_check(status):
+    """Raise on the status word of `mink_fps_scenes` (a host int or a one-element tensor)."""
+    from .._lib import FPS_BAD_START, FPS_EMPTY_SCENE, FPS_SCENE_TOO_LARGE
+
+    s = int(status)
+    if s:
+        why = [t for bit, t in ((FPS_EMPTY_SCENE, "an empty scene (or offsets outside the matrix)"),
+                                (FPS_BAD_START, "a first pick outside its scene"),
+                                (FPS_SCENE_TOO_LARGE, "a scene above the n_max bound")) if s & bit]
+        raise SampleSceneError("farthest_point_sample: " + ", ".join(why) + f" (status {s}); such a scene's picks are -1")
+
+
+def farthest_point_sample(xyz, offsets, num_points, start, n_max=None, status_async=False):
+    """Farthest-point sampling of every scene of a batch with `mink_fps_scenes` (reference transforms.py:597-630, one scene at
+    a time on the CPU): -> int64 [B, num_points] on the device, the GLOBAL rows picked, in pick order.
+
+    xyz f32 [n, >= 3] on the device, rows of any pitch with unit column stride (a `[:, 1:4]` view of float coordinates goes in
+    without a copy; int32 coordinates are converted); offsets int32 [B + 1]; start int32 [B] = the scene-local row of every
+    scene's first pick (the reference's `np.random.randint(0, N)`).  `n_max`: a bound on the largest scene (default: all rows),
+    which sizes the workspace.  The status word is read back (one small synchronisation) and a rejected scene raises
+    `SampleSceneError`, unless `status_async`: then (idx, (pinned status, event)) comes back for `fps_status_check` later."""
+    from .._lib import check, lib
+
+    if not xyz.is_cuda:
+        raise RuntimeError("farthest_point_sample runs on the GPU: move the batch to cuda first")
+    dev = xyz.device
+    if xyz.dim() != 2 or xyz.shape[1] < 3:
+        raise ValueError(f"farthest_point_sample: xyz of shape {tuple(xyz.shape)}, [n, >= 3] expected")
+    if xyz.dtype != torch.float32 or xyz.stride(1) != 1 or xyz.stride(0) < 3:
+        xyz = xyz[:, :3].float().contiguous()
+    n, ld, m = int(xyz.shape[0]), int(xyz.stride(0)), int(num_points)
+    offs = offsets.to(dev, torch.int32, non_blocking=True).contiguous()
+    first = torch.as_tensor(start).to(dev, torch.int32, non_blocking=True).contiguous()
+    B = offs.numel() - 1
+    if first.numel() != B:
+        raise ValueError(f"farthest_point_sample: {first.numel()} first picks for {B} scenes")
+    n_max = n if n_max is None else min(int(n_max), n)
+    idx = torch.empty(B, m, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(1, lib().mink_fps_workspace_bytes(n_max, B)), dtype=torch.uint8, device=dev)
+    check(lib().mink_fps_scenes(xyz.data_ptr(), n, ld, offs.data_ptr(), first.data_ptr(), B, m, n_max, idx.data_ptr(),
+                                status.data_ptr(), ws.data_ptr(), ws.numel(), torch._C._cuda_getCurrentRawStream(dev.index)))
+    if status_async:
+        host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+        host.copy_(status, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return idx.long(), (host, ev)
+    fps_status_check(status.item())
+    return idx.long()
+
+
+def sample_scene_rows(batch_coords, feats, idx):
+    """Keep the rows `idx` (int64 [B, m], global rows, scene by scene) of a batch: -> (coordinates [B m, .], features [B m, C],
+    scene_offsets int32 [B + 1] = arange(B + 1) * m), the survivors in pick order."""
+    B, m = idx.shape
+    rows = idx.reshape(-1)
+    offsets = torch.arange(B + 1, dtype=torch.int32, device=idx.device) * m
+    return batch_coords[rows], feats[rows], offsets
+
+
 def kaiming_normal_(tensor, a=0, mode="fan_in", nonlinearity="leaky_relu"):
     """ME.utils.kaiming_normal_ for convolution kernels laid out (K, Cin, Cout): fan_in = K * Cin, fan_out = K * Cout."""
     import math
