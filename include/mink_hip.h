@@ -1175,6 +1175,38 @@ int64_t mink_fps_workspace_bytes(int64_t n_max, int32_t B);
 int mink_fps_scenes(const float *xyz, int64_t n, int64_t ld, const int32_t *offsets, const int32_t *start, int32_t B, int32_t m,
                     int64_t n_max, int32_t *idx, int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ weight-sparse convolution (csrc/wsconv.hip)
+ * Inference with pruned kernels (reference co3d_3d/src/models/mink/modules/sparse_conv.py: WeightSparseConvolution(Transpose)
+ * .forward -> one `spmm` per kernel offset over the CSR that `sparsify("csr")` keeps).  Forward only, fp32, no atomics:
+ *
+ *     y[r][0..cout) = bias + sum over the valid offsets k = koffs[v], v ascending, with i = nbr[r][k] >= 0,
+ *                            of sum over the nonzeros (ci, co, w) of W[k]:  x[i][ci] * w
+ *
+ * one fp32 fma chain per output element (offsets ascending, input channels ascending inside an offset), bitwise reproducible.
+ * Only products with a STORED weight are formed: an input channel all of whose weights were pruned is never read into a result, so
+ * a NaN there does not reach y (mink_conv_gather_gemm on the masked weights would multiply it by zero).  A row without a neighbour
+ * at an offset is staged as zeros, so the stored weights must be finite.
+ *
+ *   x[n_in][ldx], cin <= ldx; y[n_out][ldy], cout <= ldy: pad columns of x are never read, pad columns of y never written.
+ *   nbr[n_out][K]: entries -1 or < n_in, as for mink_conv_gather_gemm.  A transposed convolution passes its transposed table.
+ *   koffs[n_valid]: the offsets that hold a nonzero, ascending, each < K.  n_valid <= K.
+ *   rowptr[n_valid][cout + 1], colidx[nnz], vals[nnz]: CSR of W[koffs[v]]^T per valid offset -- rows are output channels, column
+ *     indices input channels, ascending inside a row; rowptr values index the concatenated colidx / vals (rowptr[0][0] = 0, the
+ *     last one = nnz, row v+1 begins where row v ends).
+ *   cptr[n_valid][cout][nchunks + 1], nchunks = ceil(cin / MINK_WSCONV_CHUNK): derived from the CSR -- cptr[v][co][j] = the first
+ *     nonzero of row (v, co) whose column is >= j MINK_WSCONV_CHUNK (the last entry = the row's end).  The kernel stages
+ *     MINK_WSCONV_CHUNK input channels at a time; read only when cin > MINK_WSCONV_CHUNK, may be NULL otherwise.
+ *   bias[cout] or NULL.
+ * n_out == 0: MINK_OK without a launch.  n_valid == 0 or nnz == 0: every row of y is the bias, or zero (no table is read; the
+ * sparse operands may be NULL).  Tile: 64 rows (n_out < MINK_WSCONV_WIDE_ROWS) or 256 rows x MINK_WSCONV_COUT_TILE channels per
+ * workgroup; 16-byte accesses to x / y where the pointer and the pitch allow, dwords otherwise. */
+#define MINK_WSCONV_CHUNK 64
+#define MINK_WSCONV_COUT_TILE 64
+#define MINK_WSCONV_WIDE_ROWS 32768
+int mink_wsconv_fwd(const float *x, int64_t n_in, int32_t ldx, int32_t cin, const int32_t *nbr, int64_t n_out, int32_t K,
+                    const int32_t *koffs, int32_t n_valid, const int32_t *rowptr, const int32_t *cptr, const int32_t *colidx,
+                    const float *vals, int64_t nnz, float *y, int32_t ldy, int32_t cout, const float *bias, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

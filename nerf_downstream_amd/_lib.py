@@ -258,7 +258,11 @@ SIGNATURES = {
     "mink_paconv_scatter_bwd": (ctypes.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _p]),
     "mink_fps_workspace_bytes": (_i64, [_i64, _i32]),
     "mink_fps_scenes": (ctypes.c_int, [_p, _i64, _i64, _p, _p, _i32, _i32, _i64, _p, _p, _p, _i64, _p]),
+    "mink_wsconv_fwd": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _i64, _i32, _p, _i32, _p, _p, _p, _p, _i64, _p, _i32, _i32, _p, _p]),
 }
+
+# MINK_WSCONV_* of include/mink_hip.h: input channels staged at a time, and the row count from which a workgroup owns 256 rows
+WSCONV_CHUNK, WSCONV_COUT_TILE, WSCONV_WIDE_ROWS = 64, 64, 32768
 
 # MINK_FPS_* of include/mink_hip.h: the scene sizes at which mink_fps_scenes changes where a scene lives, and its status bits
 FPS_XYZ_REG_ROWS_SMALL, FPS_XYZ_REG_ROWS, FPS_DIST_REG_ROWS = 2048, 8192, 57344

@@ -11,8 +11,18 @@ One validation pass with batches of one scene, the confusion matrix accumulated 
                                   the table every ScanNet paper reports (reference IoUMeter.compute convention; classes in
                                   index order),
 and, with --visualize, <save_path>/figure/<tag>/<scene>.pth (coordinates, logits, labels) for every second batch.
-An existing <tag>.json is kept unless --replace is given.  The reference's pruning / sparsify / powernorm / --device cpu /
---profile options belong to its pruning study and are refused here."""
+An existing <tag>.json is kept unless --replace is given.
+
+Pruned checkpoints (reference eval.py:49-83): when a state-dict key contains `_mask` the prunable parameters are identity-pruned
+so the `*_orig` / `*_mask` pairs load, the `num_params, total=..., net=..., ratio=...` line is printed, the masks are made
+permanent and every module that has `sparsify` is sparsified with `evaluate.layout` ("csr", "coo" or "strided"); <tag>.json then
+also carries `val/total_params`, `val/pruned_params` and `val/gflops`.  The weight-sparse layers come from the binding the
+reference's `--sparsify --sparse_mode 1,1,1,1,1,1,1,1,1` boils down to:
+
+        --ginb "get_model.sparse=[1,1,1,1,1,1,1,1,1]" --ginb "evaluate.layout='csr'"
+
+The command-line flags --sparsify / --sparse_mode / --layout themselves, and the reference's powernorm / --device cpu / --profile
+options, are refused here."""
 import argparse
 import json
 import logging
@@ -28,10 +38,13 @@ from nerf_downstream_amd.co3d_3d import train as T
 from nerf_downstream_amd.co3d_3d.src.data.data_module import DataModule
 from nerf_downstream_amd.co3d_3d.src.models import get_model
 from nerf_downstream_amd.co3d_3d.src.modules.segmentation_training import per_class_metrics
+from nerf_downstream_amd.co3d_3d.src.utils import prune as P
 
 logger = logging.getLogger(__name__)
 
 OUT_OF_SCOPE = ("convert_powernorm", "sparsify", "sparse_mode", "layout", "profile", "device")
+SPARSE_HINT = ("a pruned checkpoint is evaluated through gin bindings, not through --sparsify / --sparse_mode / --layout: "
+               "--ginb \"get_model.sparse=[1,1,1,1,1,1,1,1,1]\" --ginb \"evaluate.layout='csr'\"")
 
 
 def _gin_or(name, default):
@@ -50,9 +63,11 @@ def _scene_name(batch, index):
 
 @gin.configurable
 def evaluate(save_path, load_path, training_module: str = "SegmentationTraining", tag="default", visualize=False, replace=False,
-             val_phase="val", val_num_workers=None, ME=None, device=None, seed: int = 777):
+             val_phase="val", val_num_workers=None, ME=None, device=None, seed: int = 777, layout="csr"):
     """-> the `val/*` dict written to <save_path>/<tag>.json, or None when that file exists and `replace` is not set.
-    `ME` / `device` are test hooks, as in train(): the CPU tests inject the oracle namespace."""
+    `ME` / `device` are test hooks, as in train(): the CPU tests inject the oracle namespace.  `layout`: what `sparsify()` is
+    called with when the checkpoint is a pruned one ("csr" / "coo": the sparse kernel, "strided": the dense one on the masked
+    weights)."""
     os.makedirs(save_path, exist_ok=True)
     json_path = os.path.join(save_path, f"{tag}.json")
     if not replace and os.path.isfile(json_path):
@@ -68,7 +83,22 @@ def evaluate(save_path, load_path, training_module: str = "SegmentationTraining"
         raise ValueError(f"evaluate.training_module = {training_module!r}: only SegmentationTraining has an evaluation table")
     torch.manual_seed(seed)
     model = (get_model(ME=ME) if ME is not None else get_model()).to(device)
+    is_pruned = any("_mask" in k for k in T.load_checkpoint_file(load_path)["state_dict"])
+    if is_pruned:  # identity pruning gives every prunable parameter the `_orig` / `_mask` pair the checkpoint holds
+        logger.info("received checkpoint of pruned network")
+        to_prune = P.get_parameters_to_prune(model)
+        P.register_prune_buffers(to_prune)
     T.load_checkpoint(load_path, model, weights_only=True)  # tensors and plain containers only: nothing from the file is executed
+    sparsified = False
+    if is_pruned:
+        num = P.count_parameters(model)
+        net = num["total"] - num["pruned"]
+        print(f"num_params, total={num['total']}, net={net}, ratio={net / num['total'] * 100:.2f}")
+        P.remove(to_prune)  # the pruned state becomes permanent: the zeros are in the parameters
+        for _, m in model.named_modules():
+            if hasattr(m, "sparsify"):
+                m.sparsify(layout)
+                sparsified = True
     model.eval()
     workers = val_num_workers if val_num_workers is not None else _gin_or("train.val_num_workers", 0)
     data = DataModule(val_batch_size=1, val_phase=val_phase, val_num_workers=workers)
@@ -92,6 +122,9 @@ def evaluate(save_path, load_path, training_module: str = "SegmentationTraining"
     tot = T.validation_pass(module, loader, device, 1, on_batch=on_batch)
     module.keep_val_logits, module.last_val = False, None
     results = module.val_metrics(tot)
+    if sparsified:
+        results["val/total_params"], results["val/pruned_params"] = num["total"], num["pruned"]
+        results["val/gflops"] = P.count_flops(model)  # of the last scene's forward pass
     elapsed = time.time() - t0
     logger.info(f"elapsed time: {elapsed:.2f} s, iter time: {elapsed / max(len(loader), 1):.4f} s")
 
@@ -145,6 +178,8 @@ def main(argv=None):
     bad = refused_options(args)
     if bad:
         print("out of scope here (the reference's pruning / sparse-layout / profiling study): --" + ", --".join(bad), file=sys.stderr)
+        if any(b in ("sparsify", "sparse_mode", "layout") for b in bad):
+            print(SPARSE_HINT, file=sys.stderr)
         return 2
     if not args.load_path:
         print("--load_path is required", file=sys.stderr)

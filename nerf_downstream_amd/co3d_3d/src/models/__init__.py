@@ -20,6 +20,15 @@ MODELS.update({c.__name__: c for c in (MinkowskiFCNN, MinkowskiSplatFCNN, Minkow
 
 @gin.configurable
 def get_model(name: str, in_channel, out_channel, sparse=None, ME=None):
+    """`sparse`: the nine SparseConvMode values of the Res16UNet family (`sparse_mode`, reference res16unet.py:42; what the
+    reference's `eval.py --sparsify --sparse_mode ...` binds).  Deliberate deviation: the reference's get_model
+    (models/__init__.py:18-20) accepts the binding and drops it; here it reaches the network, and a model without weight-sparse
+    layers raises when any entry is non-zero.  None or all zeros builds the dense model, unchanged."""
     if name not in MODELS:
         raise KeyError(f"model {name!r} is not implemented; available: {sorted(MODELS)}")
+    modes = [int(getattr(v, "value", v)) for v in sparse] if sparse is not None else []
+    if any(modes):
+        if not issubclass(MODELS[name], _unet.Res16UNet):
+            raise ValueError(f"get_model.sparse={list(sparse)!r}: only the Res16UNet family has weight-sparse layers, {name} does not")
+        return MODELS[name](in_channel=in_channel, out_channel=out_channel, ME=ME, sparse_mode=modes)
     return MODELS[name](in_channel=in_channel, out_channel=out_channel, ME=ME)

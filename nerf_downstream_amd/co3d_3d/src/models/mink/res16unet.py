@@ -48,9 +48,15 @@ class Res16UNet(MinkowskiBaseModel):
     NORM_TYPE = "BN"
 
     def __init__(self, in_channel, out_channel, PLANES=None, LAYERS=None, BLOCK=None, NORM_TYPE=None,
-                 nonlinearity="MinkowskiReLU", bn_momentum=0.1, D=3, ME=None):
+                 nonlinearity="MinkowskiReLU", bn_momentum=0.1, D=3, ME=None, sparse_mode=(0,) * 9):
+        """`sparse_mode` (reference res16unet.py:42,67): nine SparseConvMode values -- entry 0 for the stem, the down- and
+        up-sampling convolutions and `final`, entries 1..8 for block1..block8 (their shortcut convolutions included)."""
         super().__init__(D, ME=ME)
         ME = self._ME
+        sm = [int(getattr(v, "value", v)) for v in sparse_mode]
+        if len(sm) != 9:
+            raise ValueError(f"sparse_mode takes nine entries (stem / sampling / final, block1..block8), got {len(sm)}")
+        self.sparse_mode = tuple(sm)
         self.D, self.bn_momentum, self.nonlinearity = D, bn_momentum, nonlinearity
         self.PLANES, self.LAYERS = tuple(PLANES or self.PLANES), tuple(LAYERS or self.LAYERS)
         self.BLOCK, self.NORM_TYPE = BLOCK or self.BLOCK, NORM_TYPE or self.NORM_TYPE
@@ -67,34 +73,35 @@ class Res16UNet(MinkowskiBaseModel):
             return u
 
         def down(c):
-            return unit(conv(c, c, kernel_size=2, stride=2, D=D, ME=ME))
+            return unit(conv(c, c, kernel_size=2, stride=2, D=D, conv_mode=sm[0], ME=ME))
 
         def up(cin, cout):
-            return unit(conv_tr(cin, cout, kernel_size=2, upsample_stride=2, D=D, ME=ME))
+            return unit(conv_tr(cin, cout, kernel_size=2, upsample_stride=2, D=D, conv_mode=sm[0], ME=ME))
 
-        self.conv0p1s1 = unit(conv(in_channel, P[0], kernel_size=3, D=D, ME=ME), conv(P[0], P[0], kernel_size=3, D=D, ME=ME))
+        self.conv0p1s1 = unit(conv(in_channel, P[0], kernel_size=3, D=D, conv_mode=sm[0], ME=ME),
+                              conv(P[0], P[0], kernel_size=3, D=D, conv_mode=sm[0], ME=ME))
         self.conv1p1s2 = down(P[0])
         self.inplanes = P[0]
-        self.block1 = self._make_layer(P[0], self.LAYERS[0])
+        self.block1 = self._make_layer(P[0], self.LAYERS[0], sm[1])
         self.conv2p2s2 = down(self.inplanes)
-        self.block2 = self._make_layer(P[1], self.LAYERS[1])
+        self.block2 = self._make_layer(P[1], self.LAYERS[1], sm[2])
         self.conv3p4s2 = down(self.inplanes)
-        self.block3 = self._make_layer(P[2], self.LAYERS[2])
+        self.block3 = self._make_layer(P[2], self.LAYERS[2], sm[3])
         self.conv4p8s2 = down(self.inplanes)
-        self.block4 = self._make_layer(P[3], self.LAYERS[3])
+        self.block4 = self._make_layer(P[3], self.LAYERS[3], sm[4])
         self.convtr4p16s2 = up(self.inplanes, P[4])
         self.inplanes = P[4] + P[2] * exp
-        self.block5 = self._make_layer(P[4], self.LAYERS[4])
+        self.block5 = self._make_layer(P[4], self.LAYERS[4], sm[5])
         self.convtr5p8s2 = up(self.inplanes, P[5])
         self.inplanes = P[5] + P[1] * exp
-        self.block6 = self._make_layer(P[5], self.LAYERS[5])
+        self.block6 = self._make_layer(P[5], self.LAYERS[5], sm[6])
         self.convtr6p4s2 = up(self.inplanes, P[6])
         self.inplanes = P[6] + P[0] * exp
-        self.block7 = self._make_layer(P[6], self.LAYERS[6])
+        self.block7 = self._make_layer(P[6], self.LAYERS[6], sm[7])
         self.convtr7p2s2 = up(self.inplanes, P[7])
         self.inplanes = P[7] + P[0]
-        self.block8 = self._make_layer(P[7], self.LAYERS[7])
-        self.final = conv(P[7] * exp, out_channel, kernel_size=1, stride=1, bias=True, D=D, ME=ME)
+        self.block8 = self._make_layer(P[7], self.LAYERS[7], sm[8])
+        self.final = conv(P[7] * exp, out_channel, kernel_size=1, stride=1, bias=True, D=D, conv_mode=sm[0], ME=ME)
         if self.INSSEG:
             raise NotImplementedError("the instance-segmentation offset head is out of scope")
         for m in self.modules():  # reference weight_initialization (res16unet.py:384-389), extended to the affine
@@ -103,15 +110,16 @@ class Res16UNet(MinkowskiBaseModel):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
 
-    def _make_layer(self, planes, blocks):
+    def _make_layer(self, planes, blocks, conv_mode=0):
         ME, out_planes = self._ME, planes * self.BLOCK.expansion
         shortcut = None
         if self.inplanes != out_planes:
             shortcut = nn.Sequential(
-                conv(self.inplanes, out_planes, kernel_size=1, stride=1, D=self.D, ME=ME),
+                conv(self.inplanes, out_planes, kernel_size=1, stride=1, D=self.D, conv_mode=conv_mode, ME=ME),
                 get_norm(self.NORM_TYPE, out_planes, D=self.D, bn_momentum=self.bn_momentum, ME=ME),
             )
-        mk = dict(norm_type=self.NORM_TYPE, nonlinearity_type=self.nonlinearity, bn_momentum=self.bn_momentum, D=self.D, ME=ME)
+        mk = dict(norm_type=self.NORM_TYPE, nonlinearity_type=self.nonlinearity, bn_momentum=self.bn_momentum, D=self.D,
+                  conv_mode=conv_mode, ME=ME)
         seq = [self.BLOCK(self.inplanes, planes, stride=1, downsample=shortcut, **mk)]
         self.inplanes = out_planes
         seq += [self.BLOCK(self.inplanes, planes, stride=1, **mk) for _ in range(1, blocks)]
