@@ -56,6 +56,9 @@ extern "C" {
                                         (when CLEAR the rows were their own unique rows and level 0's hash map was left empty) */
 
 const char *mink_last_error(void);
+/* 2: every scratch buffer is passed with its size; 3: MinkStem.xb (bf16 storage); 4: mink_net_* (the whole trunk per call).
+ * A caller compiled or bound against this header refuses a library that answers another number. */
+#define MINK_ABI_VERSION 4
 int mink_abi_version(void);
 
 /* ------------------------------------------------------------------ coordinate maps

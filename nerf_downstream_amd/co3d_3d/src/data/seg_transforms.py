@@ -26,13 +26,12 @@ import random
 import numpy as np
 
 from nerf_downstream_amd import gin_lite as gin
+from nerf_downstream_amd._lib import constants
 
 from .transforms import (CoordinateDropout, CoordinateUniformTranslation, RandomAffine, RandomFeatureJitter,  # noqa: F401
                          RandomHorizontalFlip, RandomRotation, RandomScale, RandomTranslation)
 
-SEG = dict(A0=0, a0=9, CROP=12, CROP_SIZE=13, CROP_TRIES=16, CROP_U=17, A1=65, a1=74, DROPOUT=77, FLIP=78, FLIP_ALL=81, B=82,
-           b=91, FEAT_STD=94, FEAT_START=95, FEAT_DIM=96, ELASTIC=97, GRID_BOUND=101, EXTENT=104, PARAMS=108, MAX_TRIES=16,
-           MAX_ELASTIC=2)  # include/mink_hip.h MINK_SEGAUG_*
+SEG = constants("MINK_SEGAUG_")  # columns of a scene's parameter row, and the limits of the device program
 RAW_COLUMNS = {"xyzs": [0, 1, 2], "dists": [3], "density": [4], "sh": list(range(5, 32)), "ones": [-1]}  # reference scannet.py:623-635
 # |Box-Muller normal| <= sqrt(-2 ln 2^-24) = sqrt(48 ln 2) = 5.7683 (the device's u1 is at least 2^-24)
 NORMAL_MAX = 5.77
@@ -75,7 +74,7 @@ class ElasticDistortion:
             stages.append(("elastic", self.distortion_params))
 
 
-COLOR = dict(COUNT=0, OPS=1, OP_STRIDE=8, MAX_OPS=4, PARAMS=33, TRANSLATE=1, JITTER=2, NORMALIZE=3)  # MINK_COLORAUG_*
+COLOR = constants("MINK_COLORAUG_")  # layout of a scene's colour program, and its op kinds
 # colour stages of the reference (transforms.py) that have no device counterpart here
 UNSUPPORTED_COLOR = ("ChromaticAutoContrast", "HueSaturationTranslation", "RandomDropout", "ChromaticJitterPerChannel")
 

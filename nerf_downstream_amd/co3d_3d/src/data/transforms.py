@@ -16,9 +16,9 @@ import random
 import numpy as np
 
 from nerf_downstream_amd import gin_lite as gin
+from nerf_downstream_amd._lib import constants
 
-AUG = dict(A=0, a=9, FLIP=12, B=15, b=24, BJ=27, JITTER=36, DROPOUT=37, FEAT_STD=38, FEAT_START=39, FEAT_DIM=40,
-           FLIP_ALL=41, PARAMS=44)  # include/mink_hip.h MINK_AUG_*
+AUG = constants("MINK_AUG_")  # columns of a scene's parameter row
 _AXIS = {"x": 0, "y": 1, "z": 2}
 RAW_COLUMNS = {"xyzs": [0, 1, 2], "density": [3], "sh": list(range(4, 31)), "ones": [-1]}  # reference co3d.py:205-214
 

@@ -83,6 +83,7 @@ def augment_batch(coords, feats, scene_offsets, params, streams, seed, raw_cols,
     import torch
 
     from .._lib import check, lib
+    from ..co3d_3d.src.data.transforms import AUG
 
     if not coords.is_cuda:
         raise RuntimeError("augment_batch runs on the GPU: move the batch to cuda first")
@@ -110,8 +111,8 @@ def augment_batch(coords, feats, scene_offsets, params, streams, seed, raw_cols,
             kept.data_ptr(), ws.data_ptr(), ws.numel(), stream,
         )
     )
-    # column 37 = MINK_AUG_DROPOUT: without dropout every voxel survives and the count is known on the host
-    if host_params is not None and not bool((host_params[:, 37] != 0).any()):
+    # without dropout every voxel survives and the count is known on the host
+    if host_params is not None and not bool((host_params[:, AUG["DROPOUT"]] != 0).any()):
         return (out_c, out_f, None) if count_async else (out_c, out_f)
     if count_async:
         count = torch.empty(1, dtype=torch.int32, pin_memory=True)
@@ -212,8 +213,10 @@ class VoxelRangeError(RuntimeError):
 def points_status_check(status):
     """Raise on a failed point-cloud preparation (status = host int32 [survivors, elastic passes evaluated without a stored
     grid, elastic passes not applied, MINK_STATUS_* bits of the down-sampling])."""
+    from .._lib import CONSTANTS
+
     seg_status_check(status)
-    if int(status[3]) & 1:
+    if int(status[3]) & CONSTANTS["MINK_STATUS_RANGE"]:
         raise VoxelRangeError("voxel_downsample: a voxel key outside [-32768, 32767] (coordinates / quantisation size too large)")
 
 
@@ -226,7 +229,7 @@ def voxel_downsample_batch(coords, feats, labels, scene_offsets, params):
     MINK_STATUS_* bits))."""
     import torch
 
-    from .._lib import check, lib
+    from .._lib import check, constants, lib
 
     if not coords.is_cuda:
         raise RuntimeError("voxel_downsample_batch runs on the GPU: move the batch to cuda first")
@@ -238,8 +241,9 @@ def voxel_downsample_batch(coords, feats, labels, scene_offsets, params):
     labels = labels.to(dev, torch.int32).contiguous()
     offs = scene_offsets.to(dev, torch.int32).contiguous()
     P = params.to(dev, torch.float64).contiguous()
-    if P.shape != (n_scenes, 4):
-        raise ValueError(f"voxel_downsample_batch: parameter rows {tuple(P.shape)}, ({n_scenes}, 4) expected")
+    width = constants("MINK_VOXDS_")["PARAMS"]
+    if P.shape != (n_scenes, width):
+        raise ValueError(f"voxel_downsample_batch: parameter rows {tuple(P.shape)}, ({n_scenes}, {width}) expected")
     out_c = torch.empty(n, 4, dtype=torch.float32, device=dev)
     out_f = torch.empty(n, C, dtype=torch.float32, device=dev)
     out_l = torch.empty(n, dtype=torch.int32, device=dev)
@@ -301,6 +305,7 @@ def prepare_point_batch(batch, count_async=False):
     scene whose dropout ratio (2) removes every row."""
     import torch
 
+    from .._lib import constants
     from ..co3d_3d.src.data.seg_transforms import SEG
 
     coords, feats = batch["coordinates"], batch["features"]
@@ -311,7 +316,7 @@ def prepare_point_batch(batch, count_async=False):
     n_scenes = offs.numel() - 1
     c, f, raw, src, ds_offs, ds_status = voxel_downsample_batch(coords.float(), feats.float(), batch["labels"], offs, batch["ds_params"])
     lut = batch["class_lut"].to(dev, torch.int64)
-    ignore = batch["ds_params"][0, 2]  # MINK_VOXDS_IGNORE
+    ignore = batch["ds_params"][0, constants("MINK_VOXDS_")["IGNORE"]]
     raw = raw.long()
     labels = torch.where((raw >= 0) & (raw < lut.numel()), lut[raw.clamp(0, lut.numel() - 1)], ignore.to(dev, torch.int64))
     if "color_params" in batch:

@@ -1,4 +1,5 @@
-"""CPU: the C-ABI library builds, loads and exports every symbol include/mink_hip.h declares."""
+"""CPU: the C-ABI library builds, loads and exports every symbol include/mink_hip.h declares, and the Python bindings are what
+that header says (signatures, struct layouts, hook types, constants, ABI version)."""
 import ctypes
 import os
 import re
@@ -176,3 +177,149 @@ def test_net_sizes_follow_the_documented_arena_layout():
     # a block that strides past the last level given is refused
     assert L.mink_net_sizes(ctypes.byref(net), levels, 2, ctypes.byref(a), ctypes.byref(g), ctypes.byref(w)) != 0
     assert b"level" in L.mink_last_error()
+
+
+# ---------------------------------------------------------------- the bindings are read from include/mink_hip.h (_lib.parse_header)
+_SNIPPET = """
+#ifndef SNIPPET_H
+#define SNIPPET_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define X 4u
+#define Y (-2) /* a negative code */
+enum {
+  MINK_T_A = 0,  /* 9 */
+  MINK_T_b = 9,  // 3
+  MINK_T_PARAMS = 12
+};
+const char *mink_name(void);
+int mink_three(const float *x, /* [n][ld] */ int64_t n,
+               uint64_t seed, uint64_t *keys, // one per row
+               uint32_t *const *tables, float eps, double scale, uint32_t flags, int mode, int32_t K,
+               const uint8_t *arg, void *stream);
+typedef struct MinkInner {
+  const float *gamma, *beta; /* [C] */
+  int32_t K, cin;
+  float eps;
+} MinkInner;
+typedef struct {
+  MinkInner conv;
+  MinkInner *blocks;
+  int32_t offsets[81];
+  const int32_t *nbr;
+  int64_t n;
+  void *compute, *branch;
+} MinkOuter;
+typedef void (*MinkTHook)(int32_t stage, int32_t backward);
+int mink_set_t_hook(MinkTHook hook);
+int64_t mink_sizes(const MinkOuter *net, int64_t *act_floats);
+#ifdef __cplusplus
+}
+#endif
+#endif /* SNIPPET_H */
+"""
+
+
+def test_reader_on_snippets():
+    from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+
+    from nerf_downstream_amd import _lib
+
+    sig, structs, hooks, consts = _lib.parse_header(_SNIPPET)
+    assert consts == {"X": 4, "Y": -2, "MINK_T_A": 0, "MINK_T_b": 9, "MINK_T_PARAMS": 12}
+    assert sig == {
+        "mink_name": (c_char_p, []),
+        "mink_three": (c_int, [c_void_p, c_int64, c_uint64, c_void_p, c_void_p, c_float, c_double, c_uint32, c_int, c_int32,
+                               c_void_p, c_void_p]),
+        "mink_set_t_hook": (c_int, [c_void_p]),
+        "mink_sizes": (c_int64, [c_void_p, c_void_p]),
+    }
+    assert sorted(structs) == ["Inner", "Outer"]
+    inner, outer = structs["Inner"], structs["Outer"]
+    assert inner.__name__ == "Inner" and issubclass(outer, ctypes.Structure)
+    assert inner._fields_ == [("gamma", c_void_p), ("beta", c_void_p), ("K", c_int32), ("cin", c_int32), ("eps", c_float)]
+    assert outer._fields_ == [("conv", inner), ("blocks", POINTER(inner)), ("offsets", c_int32 * 81), ("nbr", c_void_p),
+                              ("n", c_int64), ("compute", c_void_p), ("branch", c_void_p)]
+    assert list(hooks) == ["MinkTHook"]
+    assert hooks["MinkTHook"]._restype_ is None and hooks["MinkTHook"]._argtypes_ == (c_int32, c_int32)
+
+
+@pytest.mark.parametrize("text, names", [
+    ("int mink_f(const float *x, size_t n);", "size_t"),  # an unknown scalar type
+    ("#define MINK_Z (1 << 3)", "1 << 3"),  # a constant that is an expression
+    ("typedef struct { int32_t a : 3; } MinkBits;", "a : 3"),  # a bit-field
+    ("int mink_g(int32_t n, void (*)(int32_t));", "mink_g"),  # an unnamed function-pointer parameter
+])
+def test_reader_raises_on_what_it_does_not_know(text, names):
+    from nerf_downstream_amd import _lib
+
+    with pytest.raises(_lib.HeaderError, match=re.escape(names)):
+        _lib.parse_header(text)
+
+
+_STRUCTS = ("KernelMapDesc", "ConvLayer", "NormLayer", "Exec", "Stem", "BasicBlock", "LevelMaps", "Net", "ClassPartitionDesc",
+            "TimingEntry")
+
+
+def test_struct_layout_against_the_c_compiler(tmp_path):
+    """sizeof of every struct, offsetof and sizeof of every field, as the host C compiler lays include/mink_hip.h out, against
+    the ctypes classes: the numbers come from gcc, not from the reader's reading of the types."""
+    import subprocess
+
+    from nerf_downstream_amd import _lib
+
+    assert sorted(_lib.STRUCTS) == sorted(_STRUCTS)
+    lines, want = [], []
+    for name in _STRUCTS:
+        cls = getattr(_lib, name)
+        lines.append(f'  printf("%zu\\n", sizeof(Mink{name}));')
+        want.append(ctypes.sizeof(cls))
+        for field, _ in cls._fields_:
+            lines.append(f'  printf("%zu %zu\\n", offsetof(Mink{name}, {field}), sizeof(((Mink{name} *)0)->{field}));')
+            want.append((getattr(cls, field).offset, getattr(cls, field).size))
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include "mink_hip.h"\nint main(void) {\n' + "\n".join(lines) + "\n  return 0;\n}\n")
+    exe = str(tmp_path / "layout")
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", exe, str(src)])
+    out = subprocess.check_output([exe], text=True).splitlines()
+    got = [tuple(map(int, row.split())) if " " in row else int(row) for row in out]
+    assert len(want) == len(_STRUCTS) + sum(len(getattr(_lib, n)._fields_) for n in _STRUCTS) > 100
+    assert got == want
+
+
+def test_whole_header_is_read():
+    from nerf_downstream_amd import _lib
+
+    assert len(_lib.SIGNATURES) >= 141
+    for name, (res, args) in _lib.SIGNATURES.items():
+        assert res in (ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_char_p), name
+        assert isinstance(args, list), name
+    assert len(_lib.SIGNATURES["mink_wsconv_fwd"][1]) == 19
+    assert _lib.SIGNATURES["mink_set_stage_hook"] == (ctypes.c_int, [ctypes.c_void_p])
+    assert _lib.STAGE_HOOK._argtypes_ == (ctypes.c_int32, ctypes.c_int32) and _lib.BLOCK_DONE_HOOK._argtypes_ == (ctypes.c_int32,)
+    assert _lib.Net.blocks.size == ctypes.sizeof(ctypes.c_void_p) and dict(_lib.Net._fields_)["blocks"] is ctypes.POINTER(_lib.BasicBlock)
+    for family, some in (("MINK_AUG_", ("A", "a", "DROPOUT", "PARAMS", "MAX_CHANNELS")),
+                         ("MINK_SEGAUG_", ("A0", "CROP_U", "PARAMS", "MAX_ELASTIC")),
+                         ("MINK_COLORAUG_", ("COUNT", "OP_STRIDE", "NORMALIZE")), ("MINK_VOXDS_", ("Q", "VOXEL", "IGNORE", "PARAMS")),
+                         ("MINK_WSCONV_", ("CHUNK", "COUT_TILE", "WIDE_ROWS")), ("MINK_FPS_", ("THREADS", "DIST_REG_ROWS", "BAD_START")),
+                         ("MINK_STATUS_", ("RANGE", "UNSORTED")), ("MINK_", ("OK", "EINVAL", "ELAUNCH", "ABI_VERSION"))):
+        assert set(some) <= set(_lib.constants(family)), family
+    assert _lib.CONSTANTS["MINK_EINVAL"] == -1 and _lib.CONSTANTS["MINK_STATUS_NOT_ASCENDING"] == 4
+    assert _lib.constants("MINK_AUG_")["a"] == 9 and _lib.constants("MINK_AUG_")["A"] == 0
+
+
+def test_library_of_another_abi_is_refused(monkeypatch):
+    """lib() on a fresh module state, over a handle whose mink_abi_version answers 3: MinkHipError naming both numbers."""
+    from nerf_downstream_amd import _lib
+
+    stale = ctypes.CDLL(_lib.LIB_PATH)  # (a handle object of its own: the attribute set here is not seen by other handles)
+    stale.mink_abi_version = ctypes.CFUNCTYPE(ctypes.c_int)(lambda: 3)
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib.ctypes, "CDLL", lambda path: stale)
+    with pytest.raises(_lib.MinkHipError, match=r"ABI version 3\b.*declares 4\b.*make -C"):
+        _lib.lib()
+    assert _lib._lib is None
+    monkeypatch.undo()
+    assert _lib.lib().mink_abi_version() == 4
