@@ -1210,6 +1210,27 @@ int mink_wsconv_fwd(const float *x, int64_t n_in, int32_t ldx, int32_t cin, cons
                     const int32_t *koffs, int32_t n_valid, const int32_t *rowptr, const int32_t *cptr, const int32_t *colidx,
                     const float *vals, int64_t nnz, float *y, int32_t ldy, int32_t cout, const float *bias, void *stream);
 
+/* ------------------------------------------------------------------ positional encoding (csrc/posenc.hip)
+ * MinkowskiPositionalEncoding (reference co3d_3d/src/models/mink/modules/encoding.py:74-209), fp32, no atomics.  With
+ * Q = 2 L C encoded columns, column q reads input channel q / (2L):
+ *
+ *     y[i][q]          = sin(freq[q] * x[i][q / (2L)] + phase[q])      0 <= q < Q   (one fused multiply-add, then sinf)
+ *     y[i][Q + c - lo] = x[i][c]                                       lo <= c < hi (the pass-through columns, bit-equal)
+ *     dx[i][c]         = sum over q in [2L c, 2L (c + 1)), ascending, of freq[q] * cos(freq[q] * x[i][c] + phase[q]) * dy[i][q]
+ *                        (+ dy[i][Q + c - lo] when lo <= c < hi, added last)
+ *
+ * freq[Q] and phase[Q] are device arrays (the module's `frequencies` and `offset`); which entries hold sines and which
+ * cosines is the caller's business.  x[n][ldx], C <= ldx; y and dy have n rows of pitch ldy >= Q + hi - lo and nothing beyond
+ * those columns is read or written, so the layer can fill the left columns of a wider matrix; dx[n][lddx], C <= lddx.
+ * 1 <= C <= 4096, 1 <= L <= 32, 0 <= lo <= hi <= C, n < 2^28.  n == 0: MINK_OK without a launch.  Forward: one lane per column
+ * group; backward: one lane per (row, channel), which owns the channel's 2L contiguous columns, so two runs are bitwise equal.
+ * 16-byte accesses to y / dy / freq / phase when 2L % 4 == 0, ldy % 4 == 0 and those pointers are 16-byte aligned, dwords
+ * otherwise; x, dx and the pass-through columns always move as dwords. */
+int mink_posenc_fwd(const float *x, int64_t n, int32_t C, int32_t ldx, const float *freq, const float *phase, int32_t L, int32_t lo,
+                    int32_t hi, float *y, int32_t ldy, void *stream);
+int mink_posenc_bwd(const float *dy, int32_t ldy, const float *x, int64_t n, int32_t C, int32_t ldx, const float *freq,
+                    const float *phase, int32_t L, int32_t lo, int32_t hi, float *dx, int32_t lddx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

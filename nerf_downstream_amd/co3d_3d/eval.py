@@ -37,7 +37,7 @@ from nerf_downstream_amd import gin_lite as gin
 from nerf_downstream_amd.co3d_3d import train as T
 from nerf_downstream_amd.co3d_3d.src.data.data_module import DataModule
 from nerf_downstream_amd.co3d_3d.src.models import get_model
-from nerf_downstream_amd.co3d_3d.src.modules.segmentation_training import per_class_metrics
+from nerf_downstream_amd.co3d_3d.src.modules.segmentation_training import per_class_metrics, refuse_instance_head
 from nerf_downstream_amd.co3d_3d.src.utils import prune as P
 
 logger = logging.getLogger(__name__)
@@ -83,6 +83,7 @@ def evaluate(save_path, load_path, training_module: str = "SegmentationTraining"
         raise ValueError(f"evaluate.training_module = {training_module!r}: only SegmentationTraining has an evaluation table")
     torch.manual_seed(seed)
     model = (get_model(ME=ME) if ME is not None else get_model()).to(device)
+    refuse_instance_head(model, "co3d_3d.eval")
     is_pruned = any("_mask" in k for k in T.load_checkpoint_file(load_path)["state_dict"])
     if is_pruned:  # identity pruning gives every prunable parameter the `_orig` / `_mask` pair the checkpoint holds
         logger.info("received checkpoint of pruned network")

@@ -13,6 +13,7 @@ from .mink.pointnet import MinkowskiPointNet
 
 MODELS = {c.__name__: c for c in (ResNet14, ResNet18, ResNet34, ResNet50, ResNet101)}
 MODELS.update({n: c for n, c in vars(_unet).items() if n.startswith("Res16UNet") and isinstance(c, type)})
+MODELS.update({c.__name__: c for c in (_unet.EncodedRes16UNet, _unet.EncodedRes16UNet2)})  # (the *Ins variants come by name above)
 MODELS.update({n: c for n, c in vars(_resunet).items()  # registration feature extractors (ResUNet2 itself is abstract)
                if n.startswith("ResUNet") and isinstance(c, type) and c.NORM_TYPE is not None})
 MODELS.update({c.__name__: c for c in (MinkowskiFCNN, MinkowskiSplatFCNN, MinkowskiPointNet, DGCNN_cls, PAConvPointNet, PAConvDGCNN)})  # point-based classifiers

@@ -13,7 +13,11 @@ Reference quirk kept visible: the size-named subclasses read `self.PLANES`, whic
 variants define (res16unet.py:438-453 vs :528-575); here the base class carries the constructor default
 (32, 48, 64, 96, 96, 96, 64, 64) as a class attribute so Res16UNet14/18/34 are constructible; and the
 classifier takes PLANES[7] * BLOCK.expansion inputs (the reference passes PLANES[7], res16unet.py:343-351,
-which only fits the BasicBlock variants)."""
+which only fits the BasicBlock variants).
+
+The `*Ins` variants (reference res16unet.py:584-601) add `offset_block` on block8's output and return (offsets, logits);
+EncodedRes16UNet / EncodedRes16UNet2 (:604-795) wrap the U between two per-point MLPs behind a positional encoding."""
+import torch
 import torch.nn as nn
 
 from nerf_downstream_amd import gin_lite as gin
@@ -102,8 +106,14 @@ class Res16UNet(MinkowskiBaseModel):
         self.inplanes = P[7] + P[0]
         self.block8 = self._make_layer(P[7], self.LAYERS[7], sm[8])
         self.final = conv(P[7] * exp, out_channel, kernel_size=1, stride=1, bias=True, D=D, conv_mode=sm[0], ME=ME)
-        if self.INSSEG:
-            raise NotImplementedError("the instance-segmentation offset head is out of scope")
+        if self.INSSEG:  # the offset head of the *Ins variants (reference res16unet.py:308-321), on the width after block8
+            w = self.inplanes
+            self.offset_block = nn.Sequential(
+                conv(w, w, kernel_size=1, stride=1, bias=True, D=D, ME=ME),
+                get_norm(self.NORM_TYPE, w, D, bn_momentum=bn_momentum, ME=ME),
+                get_nonlinearity(nonlinearity, ME)(),
+                conv(w, 3, kernel_size=1, stride=1, bias=True, D=D, ME=ME),
+            )
         for m in self.modules():  # reference weight_initialization (res16unet.py:384-389), extended to the affine
             # parameters of NORM_TYPE "LN" (nn.LayerNorm) and "IN" (weight / bias of shape (1, C))
             if isinstance(m, (nn.BatchNorm1d, nn.LayerNorm, ME.MinkowskiInstanceNorm)):
@@ -125,9 +135,10 @@ class Res16UNet(MinkowskiBaseModel):
         seq += [self.BLOCK(self.inplanes, planes, stride=1, **mk) for _ in range(1, blocks)]
         return nn.Sequential(*seq)
 
-    def forward(self, x):
+    def _unet(self, x):
+        """The U from the tensor-stride-1 SparseTensor `x` to the output of block8, without the classifier."""
         cat = self._ME.cat
-        out_p1 = self.conv0p1s1(x.sparse())
+        out_p1 = self.conv0p1s1(x)
         out_b1p2 = self.block1(self.conv1p1s2(out_p1))
         out_b2p4 = self.block2(self.conv2p2s2(out_b1p2))
         out_b3p8 = self.block3(self.conv3p4s2(out_b2p4))
@@ -135,7 +146,12 @@ class Res16UNet(MinkowskiBaseModel):
         out = self.block5(cat(self.convtr4p16s2(out), out_b3p8))  # 8
         out = self.block6(cat(self.convtr5p8s2(out), out_b2p4))   # 4
         out = self.block7(cat(self.convtr6p4s2(out), out_b1p2))   # 2
-        out = self.block8(cat(self.convtr7p2s2(out), out_p1))     # 1
+        return self.block8(cat(self.convtr7p2s2(out), out_p1))    # 1
+
+    def forward(self, x):
+        out = self._unet(x.sparse())
+        if self.INSSEG:  # (offsets [N, 3], logits [N, out_channel]), both read back through the field's one inverse map
+            return self.offset_block(out).slice(x).F, self.final(out).slice(x).F
         return self.final(out).slice(x).F
 
 
@@ -215,3 +231,76 @@ class Res16UNet34B(Res16UNet34):
 
 class Res16UNet34C(Res16UNet34):
     PLANES = (32, 64, 128, 256, 256, 128, 96, 96)
+
+
+class Res16UNet14AIns(Res16UNet14A):
+    INSSEG = True
+
+
+class Res16UNet14BIns(Res16UNet14B):
+    INSSEG = True
+
+
+class Res16UNet18AIns(Res16UNet18A):
+    INSSEG = True
+
+
+class Res16UNet18BIns(Res16UNet18B):
+    INSSEG = True
+
+
+class Res16UNet34CIns(Res16UNet34C):
+    INSSEG = True
+
+
+@gin.configurable
+class EncodedRes16UNet(Res16UNet):
+    """Res16UNet on learned per-point features (reference res16unet.py:604-706): the input channels are positionally encoded
+    (no gradient), a per-point MLP `enc_mlp` brings them to ENC_PLANES[-1] channels, `.sparse()` averages the points of a voxel,
+    the U runs up to block8, and a per-point MLP `dec_mlp` on [enc_mlp output | block8 output read back at the points] feeds the
+    classifier.  `final` is a MinkowskiLinear here (keys final.linear.weight / .bias), not the U-Net's 1x1 convolution."""
+
+    def __init__(self, in_channel, out_channel, ENC_PLANES=(32, 32), DEC_PLANES=(48, 48), D=3, ME=None, sparse_mode=(0,) * 9):
+        Res16UNet.__init__(self, in_channel=ENC_PLANES[-1], out_channel=out_channel, D=D, ME=ME, sparse_mode=sparse_mode)
+        self.ENC_PLANES, self.DEC_PLANES = tuple(ENC_PLANES), tuple(DEC_PLANES)
+        ME = self._ME
+        self.encoding = ME.MinkowskiPositionalEncoding(in_channel)
+        self.enc_mlp = self._mlp((self.encoding.out_channels, *self.ENC_PLANES))
+        self.dec_mlp = self._mlp((self._dec_in_channel(), *self.DEC_PLANES))
+        self.final = ME.MinkowskiLinear(self.DEC_PLANES[-1], out_channel, bias=True)
+
+    def _dec_in_channel(self):
+        return self.inplanes + self.ENC_PLANES[-1]  # (inplanes: the width after block8)
+
+    def _mlp(self, widths):
+        ME = self._ME
+        return nn.Sequential(*[nn.Sequential(ME.MinkowskiLinear(a, b, bias=True), get_nonlinearity(self.nonlinearity, ME)())
+                               for a, b in zip(widths[:-1], widths[1:])])
+
+    def _encode(self, x):
+        """-> (the encoded field, enc_mlp of it, block8's output)"""
+        ME = self._ME
+        with torch.no_grad():
+            enc = self.encoding(x)
+        feat = self.enc_mlp(enc)
+        return enc, feat, self._unet(feat.sparse(quantization_mode=ME.SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE))
+
+    def forward(self, x):
+        _, feat, out = self._encode(x)
+        return self.final(self.dec_mlp(self._ME.cat(feat, out.slice(feat)))).F
+
+
+@gin.configurable
+class EncodedRes16UNet2(EncodedRes16UNet):
+    """The second form (reference res16unet.py:709-795): `dec_mlp` reads [the raw encoding | block8 output at the points]."""
+
+    def __init__(self, in_channel, out_channel, ENC_PLANES=(32, 32), DEC_PLANES=(48, 48), D=3, ME=None, sparse_mode=(0,) * 9):
+        EncodedRes16UNet.__init__(self, in_channel, out_channel, ENC_PLANES=ENC_PLANES, DEC_PLANES=DEC_PLANES, D=D, ME=ME,
+                                  sparse_mode=sparse_mode)
+
+    def _dec_in_channel(self):
+        return self.encoding.out_channels + self.inplanes
+
+    def forward(self, x):
+        enc, feat, out = self._encode(x)
+        return self.final(self.dec_mlp(self._ME.cat(enc, out.slice(feat)))).F

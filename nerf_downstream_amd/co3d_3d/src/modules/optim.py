@@ -28,7 +28,8 @@ OPTIMIZERS = {c.__name__: c for c in (SGD, Adam, AdamW)}
 def get_optimizer(optimizer_name, parameters, lr, weight_decay):
     if optimizer_name not in OPTIMIZERS:
         raise ValueError(f"optimizer {optimizer_name} not recognized in {sorted(OPTIMIZERS)}.")
-    parameters = list(parameters)
+    # (constants registered as parameters -- the positional encoding's int64 `coo` -- have no update and no place in a fused step)
+    parameters = [p for p in parameters if p.requires_grad]
     kw = {}
     if optimizer_name == "SGD" and parameters and all(p.is_cuda for p in parameters):
         kw["fused"] = True  # same update rule, one multi-tensor kernel instead of four foreach passes

@@ -54,12 +54,21 @@ def per_class_metrics(hist, void_last=False):
             "miou": 100.0 * float(iou[:k].mean()), "macc": 100.0 * float(acc[:k].mean())}
 
 
+def refuse_instance_head(model, who):
+    """The *Ins networks return (offsets, logits); the reference holds no loss for the offsets, so nothing here trains or
+    scores them.  Refused where the model is handed over, not later on the tuple."""
+    if getattr(getattr(model, "module", model), "INSSEG", False):
+        raise ValueError(f"{who}: {type(getattr(model, 'module', model)).__name__} is an instance-segmentation variant (INSSEG): its "
+                         "forward returns (offsets, logits) and there is no loss for the offsets; use the network without `Ins`")
+
+
 @gin.configurable
 class SegmentationTraining:
     monitor = "val/mIoU"
 
     def __init__(self, model, ignore_label=255, void_weight=None):
-        self.model, self.ignore_label, self.void_weight = model, ignore_label, void_weight
+        refuse_instance_head(model, "SegmentationTraining")
+        self.model,self.ignore_label, self.void_weight = model, ignore_label, void_weight
         self._weight = None
         self._last = None  # (logits, hist, stats) of the last loss(): what train_metrics reads at a log step
         self.keep_val_logits, self.last_val = False, None  # (co3d_3d/eval.py --visualize: the last validation batch's logits, labels)

@@ -24,6 +24,7 @@ from .modules import (  # noqa: F401
     MinkowskiLinear,
     MinkowskiMaxPooling,
     MinkowskiNetwork,
+    MinkowskiPositionalEncoding,
     MinkowskiPReLU,
     MinkowskiReLU,
     MinkowskiSELU,

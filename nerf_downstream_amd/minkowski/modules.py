@@ -6,6 +6,7 @@ import math
 import torch
 import torch.nn as nn
 
+from .. import gin_lite as gin
 from . import functional as Fn
 from .coords import ORIGIN_TS, CoordinateMapKey, _as_int
 from .tensor import SparseTensor, TensorField
@@ -401,6 +402,69 @@ class MinkowskiLinear(nn.Module):
 
     def forward(self, input):
         return _same_kind(input, self.linear(_features(input)))
+
+
+@gin.configurable
+class MinkowskiPositionalEncoding(nn.Module):
+    """Sinusoidal encoding of every feature channel of a SparseTensor or a TensorField (reference
+    models/mink/modules/encoding.py:74-209); the result is of the same kind on the same manager.
+
+    With L = num_encoding_functions and C = in_channel there are Q = 2 L C encoded columns, and column q is
+    sin(frequencies[q] * x[:, q // (2L)] + offset[0, q]) with frequencies[q] = f[q mod L].  f_j = 2^j, or with `min_resolution`
+    f = 2 ** linspace(m - L - 1, m, L), m = log2(0.5 / min_resolution): L + 1 octaves in L steps, not L - 1 -- a quirk of the
+    reference that trained weights depend on, kept.  A second one, kept for the same reason: the phase is 0 for q < C L and
+    pi / 2 for q >= C L, a split by COLUMN, not per channel -- so the channels of the first half get their L sines twice and
+    those of the second half their L cosines twice (the middle channel of an odd C gets both).
+    `include_original_channel_range = (lo, hi)` appends x[:, lo:hi] after the Q columns.  L < 1: the identity, no state.
+
+    State dict as the reference's three non-trainable parameters: `coo` int64 [2, Q] = rows (q // (2L), q) (the layout of the
+    reference's sparse matrix; not read here), `frequencies` fp32 [Q], `offset` fp32 [1, Q].  The kernel (mink_posenc_fwd)
+    reads `frequencies` and `offset`, so a loaded checkpoint's values rule."""
+
+    def __init__(self, in_channel, num_encoding_functions=4, include_original_channel_range=None, min_resolution=None):
+        super().__init__()
+        C, L = int(in_channel), int(num_encoding_functions)
+        self.num_encoding_functions, self.include_original_channel_range = L, include_original_channel_range
+        if L < 1:
+            self.shape = (C, C)
+            return
+        if include_original_channel_range is not None:
+            lo, hi = (int(v) for v in include_original_channel_range)
+            if not 0 <= lo <= hi <= C:
+                raise ValueError(f"include_original_channel_range={include_original_channel_range}: 0 <= lo <= hi <= {C}")
+            self.include_original_channel_range = (lo, hi)
+        if min_resolution is not None:
+            if not isinstance(min_resolution, (int, float)) or min_resolution <= 0:
+                raise ValueError(f"min_resolution={min_resolution!r} must be a positive number")
+            top = math.log2(0.5 / min_resolution)
+            f = 2.0 ** torch.linspace(top - L - 1, top, L)
+        else:
+            f = 2.0 ** torch.arange(L)
+        Q = 2 * L * C
+        q = torch.arange(Q)
+        self.out_enc_channel = Q
+        self.coo = nn.Parameter(torch.stack([q // (2 * L), q]), requires_grad=False)
+        self.frequencies = nn.Parameter(f.float()[q % L].contiguous(), requires_grad=False)
+        self.offset = nn.Parameter(((q >= C * L).float() * (math.pi / 2)).view(1, Q), requires_grad=False)
+        lo, hi = self.include_original_channel_range or (0, 0)
+        self.shape = (C, Q + hi - lo)
+
+    @property
+    def out_channels(self):
+        return self.shape[1]
+
+    def extra_repr(self):
+        return f"in_channel={self.shape[0]}, out_channel={self.shape[1]}, num_encoding_functions={self.num_encoding_functions}"
+
+    def forward(self, input):
+        if self.num_encoding_functions < 1:
+            return input
+        F = _features(input)
+        if F.dim() != 2 or F.shape[1] != self.shape[0]:
+            raise ValueError(f"MinkowskiPositionalEncoding: {tuple(F.shape)} features, in_channel = {self.shape[0]}")
+        lo, hi = self.include_original_channel_range or (0, 0)
+        out = Fn.PositionalEncodingFunction.apply(F, self.frequencies, self.offset.view(-1), self.num_encoding_functions, lo, hi)
+        return _same_kind(input, out)
 
 
 class MinkowskiDropout(nn.Module):

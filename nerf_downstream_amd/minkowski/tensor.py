@@ -117,6 +117,12 @@ def _field_members(m):
     return m.field_members
 
 
+def _check_quantization_mode(who, qm):
+    if qm is not None and getattr(qm, "name", str(qm)) != "UNWEIGHTED_AVERAGE":
+        raise NotImplementedError(f"{who}(quantization_mode={qm}): only UNWEIGHTED_AVERAGE (the ME default the "
+                                  "reference relies on) is implemented")
+
+
 def _is_one(ts):
     return all(int(t) == 1 for t in (ts if isinstance(ts, (list, tuple)) else [ts]))
 
@@ -146,10 +152,7 @@ class TensorField:
             self._pending = kwargs.get("_pending")
             return
         assert features is not None and coordinates is not None
-        qm = kwargs.get("quantization_mode")
-        if qm is not None and getattr(qm, "name", str(qm)) != "UNWEIGHTED_AVERAGE":
-            raise NotImplementedError(f"TensorField(quantization_mode={qm}): only UNWEIGHTED_AVERAGE (the ME default the "
-                                      "reference relies on) is implemented")
+        _check_quantization_mode("TensorField", kwargs.get("quantization_mode"))
         if not coordinates.is_cuda:
             raise RuntimeError("nerf_downstream_amd.minkowski runs on the GPU only: move the batch to cuda first")
         self._F, self._C = features, coordinates
@@ -221,7 +224,10 @@ class TensorField:
                 m.xb[1].record_stream(cur)
             root._ready = None
 
-    def sparse(self):
+    def sparse(self, quantization_mode=None):
+        """`quantization_mode` (reference res16unet.py:707,781 pass UNWEIGHTED_AVERAGE): the mode the field averages with anyway;
+        any other is refused as the constructor refuses it."""
+        _check_quantization_mode("TensorField.sparse", quantization_mode)
         m = self._manager
         self._settle()
         n_unique = m.levels[1].n
