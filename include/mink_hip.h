@@ -801,6 +801,37 @@ int mink_color_augment_scenes(float *feats, int64_t ldf, const int32_t *cols_hos
                               int32_t n_scenes, const double *params, const uint32_t *streams, uint64_t seed,
                               const int32_t *key_rows, const int32_t *key_offsets, void *stream);
 
+/* ------------------------------------------------------------------ LiDAR scans
+ * What the reference's SemanticKITTIDataset (co3d_3d/src/data/semantic_kitti.py:165-222) does to a raw scan around the
+ * down-sampling and the recipe, for a whole batch.  Both are row passes: one thread per row, 16-byte row accesses when every
+ * pointer and pitch involved is a multiple of 16 bytes and dwords otherwise, every output element written once from its own
+ * row's inputs (bitwise repeatable).
+ *
+ * mink_lidar_decode_scans: scan [n][4] float32 is the .bin file (x, y, z, intensity), raw_labels [n] the .label words, or
+ * NULL = every word 0 (a scan without its .label file); scene_offsets [n_scenes+1], lut [lut_size] on the device.  Writes
+ *     coords [n][4]   = (scene of the row, x, y, z)
+ *     feats  [n][ldo] = x, y, z, intensity in columns 0..3 (ldo >= 4; further columns are not touched)
+ *     labels [n]      = lut[word & 0xFFFF]   -- the table comes BEFORE the voxel vote (:183-196), the upper 16 bits (the
+ *                       instance id) are dropped; a semantic id >= lut_size gets ignore_label and is counted
+ * and the device int32 *status = the number of rows whose semantic id the table does not hold (zeroed by the call; the
+ * reference raises an IndexError there).  n == 0 and empty scenes are legal.
+ *
+ * mink_lidar_finish_rows: the step after the geometric program (:200-209), in place, for every row i < min(n, *n_rows) with
+ * n_rows a DEVICE int32 (the survivor count mink_augment_seg_scenes or mink_voxel_downsample_scenes left in its status):
+ *     feats[i][c0 .. c0+2] = coords[i][1..3]                  the transformed metric coordinates, as float
+ *     coords[i][1..3]      = coords[i][1..3] / voxel_size     one IEEE float division (as mink_voxel_downsample_scenes' VOXEL)
+ * Rows at or past the count are neither read nor written.  In the 16-byte form (coords and feats 16-byte aligned, ldf % 4 == 0,
+ * c0 % 4 == 0) a row's coords[i][0] and feats[i][c0+3] are stored back with the bits that were read; in the dword form they are
+ * not touched.  Both calls refuse (MINK_EINVAL) operands whose byte ranges overlap -- scan / raw_labels against coords [n][4],
+ * feats [n][ldo] and labels, and those three against each other; coords, feats [n][ldf] and n_rows here.  The program computes in double and writes float, so the voxel
+ * coordinate is f32(r) / f32(voxel_size): without a recipe bit for bit the reference's float32 array / python float; with
+ * one the reference divides in double before its single rounding, which can differ by one float ulp. */
+int mink_lidar_decode_scans(const float *scan, const uint32_t *raw_labels, int64_t n, const int32_t *scene_offsets, int32_t n_scenes,
+                            const int32_t *lut, int32_t lut_size, int32_t ignore_label, float *coords, float *feats, int64_t ldo,
+                            int32_t *labels, int32_t *status, void *stream);
+int mink_lidar_finish_rows(float *coords, int64_t n, const int32_t *n_rows, float voxel_size, float *feats, int64_t ldf, int32_t c0,
+                           void *stream);
+
 /* ------------------------------------------------------------------ optimizer step over flat buffers
  * torch.optim.SGD's update with momentum and weight decay (the reference's optimizer: co3d_3d/src/modules/optim.py:12-14,
  * co3d_3d/configs/co3d_cls.gin) for parameters w, gradients g and momentum buffers m that each live in ONE flat fp32 buffer of

@@ -38,6 +38,8 @@ def collate_mink(list_data):
             raise ValueError(f"one batch mixes grid resolutions {sorted(resos)} (data.npz scenes are 128^3, last.ckpt scenes 256^3)")
         package["reso"] = resos.pop()
         return _with_sampler(_with_programs(package, list_data, n), list_data, n)
+    if "scan" in list_data[0]:  # raw LiDAR scans (SemanticKITTIDataset): decoded, down-sampled and augmented on the GPU later
+        return _collate_scans(list_data)
     coords, feats = me_utils.sparse_collate(
         [d["coordinates"] for d in list_data], [d["features"] for d in list_data], dtype=torch.float32
     )
@@ -50,6 +52,29 @@ def collate_mink(list_data):
             package[key] = [d[key] for d in list_data]
     n = [int(d["coordinates"].shape[0]) for d in list_data]
     return _with_sampler(_with_points(_with_programs(package, list_data, n), list_data, n), list_data, n)
+
+
+def _collate_scans(list_data):
+    """Raw LiDAR scans (data/semantic_kitti.py): the .bin records and the .label words of every scan one after the other,
+    one (down-sampling voxel size, voxel size, ignore label) row per scan and the raw-id -> class table.  `raw_labels` is
+    left out when no scan of the batch had a .label file (every word is 0 then); a scan without one among others gets zeros."""
+    n = [int(d["scan"].shape[0]) for d in list_data]
+    package = {
+        "scan": _cat([d["scan"] for d in list_data]),
+        "scene_offsets": torch.tensor(np.concatenate([[0], np.cumsum(n)]), dtype=torch.int32),
+        # a numpy array, not a tensor: the trainer moves tensors to the device, and these host values size and steer the
+        # launches (as `aug_params`, which it keeps on the host by name)
+        "lidar_params": np.stack([np.asarray(d["lidar_params"], np.float64) for d in list_data]),
+        "label_lut": list_data[0]["label_lut"],
+        "feature_names": list_data[0].get("feature_names"),
+    }
+    if any(d.get("raw_labels") is not None for d in list_data):
+        package["raw_labels"] = _cat([d["raw_labels"] if d.get("raw_labels") is not None else torch.zeros(k, dtype=torch.int32)
+                                      for d, k in zip(list_data, n)])
+    for key in ("metadata", "dataset"):
+        if key in list_data[0]:
+            package[key] = [d[key] for d in list_data]
+    return _with_programs(package, list_data, n)
 
 
 def _with_programs(package, list_data, n):

@@ -51,6 +51,15 @@ class MinkowskiBaseModel(_HIP_ME.MinkowskiNetwork, InputInterface):
             batch["coordinates"], batch["features"], batch["row_labels"], batch["point_rows"] = out[:4]
             if defer:  # the row count is still on its way to the host
                 return _PendingField(self, batch, out[4])
+        if "scan" in batch:  # raw LiDAR scans (SemanticKITTIDataset): label table, down-sampling, the drawn program, xyzi features
+            if not getattr(ME, "SUPPORTS_PREPARE_AHEAD", False):
+                raise RuntimeError("LiDAR scans are prepared by the HIP backend (mink_lidar_decode_scans)")
+            with self._prepare_stream_ctx(batch["scan"], fence=batch.get("h2d_event", True)):
+                out = ME.utils.prepare_lidar_batch(batch, count_async=defer)
+            batch = {k: v for k, v in batch.items() if not k.startswith("aug_") and k not in ("scan", "raw_labels", "lidar_params", "label_lut")}
+            batch["coordinates"], batch["features"], batch["row_labels"], batch["point_rows"] = out[:4]
+            if defer:  # the row count is still on its way to the host
+                return _PendingField(self, batch, out[4])
         if "aug_params" in batch:  # augmentation programs drawn by the loader: applied to the whole batch here
             with self._prepare_stream_ctx(batch["coordinates"], fence=batch.get("h2d_event", True)):
                 coords, feats, rows, pending = self._augment(batch, count_async=defer)
@@ -196,7 +205,11 @@ class _PendingField:
 
     def materialise(self):
         self.event.synchronize()
-        if self.count.numel() > 3:  # point cloud: (survivors, direct elastic grids, passes not applied, down-sampling status)
+        if self.count.numel() > 4:  # LiDAR scans: the point cloud's four words, then the label words outside the table
+            from nerf_downstream_amd.minkowski.utils import lidar_batch_status_check
+
+            lidar_batch_status_check(self.count)
+        elif self.count.numel() > 3:  # point cloud: (survivors, direct elastic grids, passes not applied, down-sampling status)
             from nerf_downstream_amd.minkowski.utils import points_status_check
 
             points_status_check(self.count)

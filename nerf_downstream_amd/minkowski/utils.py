@@ -349,6 +349,153 @@ def prepare_point_batch(batch, count_async=False):
     return c[:k], f[:k], labels[:k], src[:k]
 
 
+class LidarLabelError(RuntimeError):
+    """A raw label word of `mink_lidar_decode_scans` carries a semantic id (its low 16 bits) past the end of the table."""
+
+
+def lidar_status_check(status):
+    """Raise on the status word of `mink_lidar_decode_scans` (a host int or a one-element tensor): the number of rows whose
+    semantic id the table does not hold.  The reference's `label_map[all_labels & 0xFFFF]` raises an IndexError there."""
+    s = int(status)
+    if s:
+        raise LidarLabelError(f"lidar_decode: {s} raw label word(s) with a semantic id past the end of the label table "
+                              "(those rows got the ignore label)")
+
+
+def lidar_decode_batch(scan, raw_labels, scene_offsets, lut, ignore_label):
+    """`mink_lidar_decode_scans` on the current stream: scan f32 [n,4] (x, y, z, intensity: the .bin file), raw_labels int32 /
+    uint32 words [n] or None (no .label file: every word 0), scene_offsets int32 [S+1], lut int [lut_size], all on the device.
+    Nothing is read back: returns (coords f32 [n,4] = (scene, x, y, z), feats f32 [n,4] = xyzi, labels
+    int32 [n] = lut[word & 0xFFFF], device status int32 [1] for `lidar_status_check`)."""
+    import torch
+
+    from .._lib import check, lib
+
+    if not scan.is_cuda:
+        raise RuntimeError("lidar_decode_batch runs on the GPU: move the batch to cuda first")
+    if scan.dtype != torch.float32 or scan.dim() != 2 or scan.shape[1] != 4:
+        raise TypeError(f"lidar_decode_batch: scan of shape {tuple(scan.shape)} {scan.dtype}, float32 [n, 4] expected")
+    dev, n = scan.device, scan.shape[0]
+    scan = scan.contiguous()
+    if raw_labels is not None:
+        if raw_labels.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or raw_labels.numel() != n:
+            raise TypeError(f"lidar_decode_batch: {raw_labels.numel()} label words of {raw_labels.dtype} for {n} points (32-bit words)")
+        raw_labels = raw_labels.to(dev).contiguous()
+    offs = scene_offsets.to(dev, torch.int32).contiguous()
+    table = lut.to(dev, torch.int32).contiguous()
+    coords = torch.empty(n, 4, dtype=torch.float32, device=dev)
+    feats = torch.empty(n, 4, dtype=torch.float32, device=dev)
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    check(
+        lib().mink_lidar_decode_scans(
+            scan.data_ptr(), None if raw_labels is None else raw_labels.data_ptr(), n, offs.data_ptr(), offs.numel() - 1,
+            table.data_ptr(), table.numel(), int(ignore_label), coords.data_ptr(), feats.data_ptr(), 4, labels.data_ptr(),
+            status.data_ptr(), torch._C._cuda_getCurrentRawStream(dev.index),
+        )
+    )
+    return coords, feats, labels, status
+
+
+def lidar_finish_rows(coords, feats, n_rows, voxel_size):
+    """`mink_lidar_finish_rows` IN PLACE on the current stream: for every row below the DEVICE int32 count `n_rows` (a
+    one-element tensor or view), feats[:, 0:3] = coords[:, 1:4] and coords[:, 1:4] /= f32(voxel_size).  Returns (coords, feats)."""
+    import torch
+
+    from .._lib import check, lib
+
+    if not (coords.is_cuda and coords.dtype == torch.float32 and coords.is_contiguous() and coords.dim() == 2 and coords.shape[1] == 4):
+        raise TypeError("lidar_finish_rows: contiguous float32 coordinates [n, 4] on the GPU")
+    if not (feats.is_cuda and feats.dtype == torch.float32 and feats.is_contiguous() and feats.shape[0] == coords.shape[0]):
+        raise TypeError("lidar_finish_rows: contiguous float32 features on the GPU, one row per coordinate row")
+    if not (n_rows.is_cuda and n_rows.dtype == torch.int32 and n_rows.numel() == 1):
+        raise TypeError("lidar_finish_rows: the row count is one int32 on the device")
+    check(lib().mink_lidar_finish_rows(coords.data_ptr(), coords.shape[0], n_rows.data_ptr(), float(voxel_size), feats.data_ptr(),
+                                       feats.shape[1], 0, torch._C._cuda_getCurrentRawStream(coords.device.index)))
+    return coords, feats
+
+
+def lidar_batch_status_check(status):
+    """Raise on a failed LiDAR preparation (status = host int32 [survivors, elastic passes evaluated without a stored grid,
+    elastic passes not applied, MINK_STATUS_* bits of the down-sampling, label words outside the table])."""
+    points_status_check(status[:4])
+    lidar_status_check(status[4])
+
+
+def prepare_lidar_batch(batch, count_async=False):
+    """The input of a batch of SemanticKITTIDataset (data/semantic_kitti.py), on the current stream, in the reference's order
+    (semantic_kitti.py:183-209): the label table (`mink_lidar_decode_scans`), voxel down-sampling with the vote over the
+    MAPPED classes (`mink_voxel_downsample_scenes`, VOXEL = 1: the coordinates stay in metres), the drawn geometric program
+    (MINK_SEGAUG_*, in metres) when there is one, then `mink_lidar_finish_rows`: the transformed coordinates become the xyz
+    of the `xyzi` feature and are divided by the voxel size.
+
+    batch (device): scan f32 [N,4], raw_labels int32 [N] (absent: no scan had a .label file), scene_offsets int32 [S+1],
+    label_lut int [lut_size]; on the HOST lidar_params f64 [S,3] (numpy) = (down-sampling voxel size, voxel size, ignore label;
+    one voxel size and ignore label per batch) and the optional aug_params f64 [S, MINK_SEGAUG_PARAMS]; aug_streams, aug_seed.
+    Nothing is read back from the device before the status word: with `count_async=True` the call never blocks.
+    Returns (coords f32 [k,4], feats f32 [k,4] = xyzi, labels int64 [k] (classes), raw row int32 [k]); with `count_async=True`
+    full-length buffers and (pinned host status int32 [5], event) instead, for the caller to slice (`lidar_batch_status_check`
+    on the status).  Rows past the representatives run through the geometric program as one more scene whose dropout ratio
+    (2) removes every row, as in `prepare_point_batch`.  A semantic id the table does not hold raises `LidarLabelError`."""
+    import torch
+
+    from .._lib import constants
+    from ..co3d_3d.src.data.seg_transforms import SEG
+
+    feature_names = list(batch.get("feature_names") or ["xyzi"])
+    if feature_names != ["xyzi"]:
+        raise NotImplementedError(f"features {feature_names}: the LiDAR preparation produces ['xyzi']")
+    scan = batch["scan"]
+    if not scan.is_cuda:
+        raise RuntimeError("the LiDAR input is prepared on the GPU: move the batch to cuda first")
+    n, dev = scan.shape[0], scan.device
+    offs = batch["scene_offsets"].to(dev, torch.int32)
+    n_scenes = offs.numel() - 1
+    lp = batch["lidar_params"]
+    if torch.is_tensor(lp):
+        if lp.is_cuda:  # (a read-back here would stall the host behind the batch's copies: what the deferred count exists to avoid)
+            raise TypeError("prepare_lidar_batch: lidar_params are host values (a numpy array or a CPU tensor), not a device tensor")
+        lp = lp.detach().numpy()
+    lp = np.asarray(lp, np.float64).reshape(n_scenes, 3)
+    voxel_size, ignore = float(lp[0, 1]), int(lp[0, 2])
+    if not ((lp[:, 1] == lp[0, 1]).all() and (lp[:, 2] == lp[0, 2]).all()):
+        raise ValueError("prepare_lidar_batch: one voxel size and one ignore label per batch")
+    c, f, mapped, lut_status = lidar_decode_batch(scan.float(), batch.get("raw_labels"), offs, batch["label_lut"], ignore)
+    VD = constants("MINK_VOXDS_")
+    ds = np.zeros((n_scenes, VD["PARAMS"]), np.float64)
+    ds[:, VD["Q"]], ds[:, VD["VOXEL"]], ds[:, VD["IGNORE"]] = np.maximum(lp[:, 0], 0.0), 1.0, ignore
+    c, f, labels, src, ds_offs, ds_status = voxel_downsample_batch(c, f, mapped, offs, torch.from_numpy(ds).pin_memory().to(dev, non_blocking=True))
+    labels = labels.long()
+    status = torch.zeros(5, dtype=torch.int32, device=dev)
+    status[3:4] = ds_status[1:]
+    status[4:] = lut_status
+    if "aug_params" in batch:
+        P = batch["aug_params"].detach().cpu().numpy().astype(np.float64) if torch.is_tensor(batch["aug_params"]) else np.array(batch["aug_params"], np.float64)
+        sink = np.zeros((1, SEG["PARAMS"]), np.float64)
+        for M in ("A0", "A1", "B"):
+            sink[0, SEG[M]:SEG[M] + 9] = np.eye(3).reshape(-1)
+        sink[0, SEG["DROPOUT"]] = 2.0  # (coins are < 1: the tail past the representatives is dropped)
+        streams = torch.cat([batch["aug_streams"].to(dev, torch.int32), torch.zeros(1, dtype=torch.int32, device=dev)])
+        c, f, rows, seg_status = _augment_seg_launch(c, f, ds_offs, np.concatenate([P, sink]), streams, batch["aug_seed"],
+                                                     [-1] * f.shape[1])
+        rows = rows.long().clamp_(0, max(n - 1, 0))  # (rows past the survivors are not written: any index will do there)
+        labels, src = labels[rows], src[rows]
+        status[:3] = seg_status
+    else:
+        status[0] = ds_status[0]
+    lidar_finish_rows(c, f, status[:1], voxel_size)
+    if count_async:
+        host = torch.empty(5, dtype=torch.int32, pin_memory=True)
+        host.copy_(status, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return c, f, labels, src, (host, ev)
+    st = status.cpu()
+    lidar_batch_status_check(st)
+    k = int(st[0])
+    return c[:k], f[:k], labels[:k], src[:k]
+
+
 class SampleSceneError(RuntimeError):
     """`mink_fps_scenes` left a scene unsampled: it is empty (or its offsets leave the matrix), its first pick lies outside
     it, or it holds more rows than the caller's bound."""
