@@ -1262,6 +1262,40 @@ int mink_posenc_fwd(const float *x, int64_t n, int32_t C, int32_t ldx, const flo
 int mink_posenc_bwd(const float *dy, int32_t ldy, const float *x, int64_t n, int32_t C, int32_t ldx, const float *freq,
                     const float *phase, int32_t L, int32_t lo, int32_t hi, float *dx, int32_t lddx, void *stream);
 
+/* ------------------------------------------------------------------ multi-head self-attention (csrc/attn.hip)
+ * The attention of a Vision Transformer block (timm's Attention.forward between its `qkv` and `proj` linears; the reference
+ * builds these networks in co3d_2d/src/model/models.py:37-54), fp32, on token rows: B samples of N tokens, H heads of D channels.
+ *
+ *     qkv [B N][ldq]  row b N + t is one token; column s H D + h D + d holds q (s = 0), k (s = 1) or v (s = 2) of head h --
+ *                     what nn.Linear(dim, 3 dim) writes; ldq >= 3 H D
+ *     out [B N][ldo]  column h D + d, what `proj` reads; ldo >= H D:
+ *                     out[b N + i][h D + d] = sum_j softmax_j(scale q_i . k_j) v_j[d]        (per sample b and head h)
+ *     lse [B][H][N]   max_j s_ij + log sum_j exp(s_ij - max_j s_ij) with s_ij = scale q_i . k_j (scaled-score units)
+ *     dout[B N][lddo] the gradient of out, lddo >= H D
+ *     dqkv[B N][lddq] the gradient of qkv in qkv's layout, lddq >= 3 H D; every logical element is written exactly once
+ *
+ * No N x N matrix reaches memory: the backward recomputes P = exp(s - lse).  Every product runs on the fp32 MFMA (an fmaf chain,
+ * one rounding per product), the row maximum (forward) or lse (backward) is subtracted before every exponential, `scale` is
+ * applied to the finished dot product.  mink_set_conv_math does not reach these entry points.  No atomics, every sum in a fixed
+ * order: two calls on the same inputs give the same bits.  mink_attn_bwd launches three kernels: delta = rowsum(dout * out) into
+ * the workspace ([B][H][N] floats), then one whose workgroups own 64 keys (dk, dv) and one whose workgroups own 64 queries (dq);
+ * both recompute the scores.
+ *
+ * D == MINK_ATTN_HEAD_DIM, 1 <= N <= MINK_ATTN_MAX_TOKENS, 1 <= H <= MINK_ATTN_MAX_HEADS, B >= 1 with B H N < 2^31 and
+ * B N < 2^31 / 192; pointers 4-byte aligned, the workspace 8-byte aligned and of at least mink_attn_bwd_workspace_bytes() bytes.
+ * Anything else is MINK_EINVAL before any launch.  Only the logical columns of the logical rows are read or written: pad
+ * columns may hold NaN and keep their bits, token rows past N of a tile are neither read nor stored.  16-byte accesses when
+ * every matrix pointer of the call is 16-byte aligned and every pitch a multiple of 4, dwords otherwise. */
+#define MINK_ATTN_HEAD_DIM 64
+#define MINK_ATTN_MAX_TOKENS 4096
+#define MINK_ATTN_MAX_HEADS 1024
+int64_t mink_attn_bwd_workspace_bytes(int64_t B, int64_t N, int32_t H, int32_t D);
+int mink_attn_fwd(const float *qkv, int32_t ldq, int64_t B, int32_t N, int32_t H, int32_t D, float scale, float *out, int32_t ldo,
+                  float *lse, void *stream);
+int mink_attn_bwd(const float *qkv, int32_t ldq, const float *out, int32_t ldo, const float *lse, const float *dout, int32_t lddo,
+                  int64_t B, int32_t N, int32_t H, int32_t D, float scale, float *dqkv, int32_t lddq, void *workspace,
+                  int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

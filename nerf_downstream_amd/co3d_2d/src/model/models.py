@@ -2,14 +2,16 @@
 torchvision ResNet (zero_init_residual=True) with its `fc` replaced by Identity, followed by Dropout and
 Linear(in_features, 51).  The ResNet itself is defined here on the dense layers of model/dense.py with torchvision's
 module and parameter names (`model.conv1.weight`, `model.layer1.0.bn2.running_var`, `model.layer2.0.downsample.0.weight`
-...), so a torchvision checkpoint loads unchanged.  ViT variants (timm) are out of scope of the sparse-vs-dense
-comparison row."""
+...), so a torchvision checkpoint loads unchanged.  `ViTBased` (:37-54) wraps the Vision Transformer of model/vit.py, which
+keeps timm's parameter names (`model.blocks.0.attn.qkv.weight` ...) and runs its attention in csrc/attn.hip; `select_model`
+routes the three `vit_*_patch16_224` names of the reference's configs to it.  The `deit3_*` names of the reference's list
+(layer scale, in no config) and the Bottleneck / wide / ResNeXt networks stay unknown names."""
 import torch
 import torch.nn as nn
 
 from nerf_downstream_amd import gin_lite as gin
 
-from . import dense
+from . import dense, vit
 
 
 class BasicBlock(nn.Module):
@@ -99,7 +101,26 @@ class ResNetBased(nn.Module):
         return self.fc(self.dropout(self.model(x)))
 
 
+@gin.configurable
+class ViTBased(nn.Module):
+    """`img_size` (extension, for tests and small runs): a multiple of 16; `pos_embed` is sized to it."""
+
+    def __init__(self, model="vit_small_patch16_224", pretrained=False, img_size=224):
+        super().__init__()
+        if model not in vit.SIZES:
+            raise NameError(f"Unknown model name : {model} (Vision Transformers {sorted(vit.SIZES)} are built here)")
+        if pretrained:
+            raise NotImplementedError("no network access for pretrained weights: load a timm state dict instead")
+        dim, depth, heads = vit.SIZES[model]
+        self.model = vit.VisionTransformer(img_size=img_size, dim=dim, depth=depth, heads=heads, num_classes=51)
+
+    def forward(self, x):
+        return self.model(x)
+
+
 def select_model(model_name):
     if model_name is None:
         raise NameError("Oops?")
+    if model_name in vit.SIZES:
+        return ViTBased(model_name)
     return ResNetBased(model_name)

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Trainer of the 2-D comparison network: same command line (--ginc / --ginb / --ckpt_path / --resume / --seed) and
-gin names (`run.*`, `LitModel.*`, `DataModule.*`, `ResNetBased.*`) as the reference's co3d_2d/train.py:39-122,164-171,
+gin names (`run.*`, `LitModel.*`, `DataModule.*`, `ResNetBased.*`, `ViTBased.*`) as the reference's co3d_2d/train.py:39-122,164-171,
 as a plain loop instead of a Lightning Trainer.  `run.precision = 16` runs the convolutions on the bf16 matrix cores
 (fp32 accumulate and storage); every convolution, batch norm and pooling is a hand-written gfx950 kernel
-(src/model/dense.py).
+(src/model/dense.py).  The Vision Transformers (configs/vit*.gin, src/model/vit.py) run in fp32 only: `run.precision = 16` with
+one of them is refused.
 
     python -m nerf_downstream_amd.co3d_2d.train --ginc nerf_downstream_amd/co3d_2d/configs/resnet18.gin"""
 import argparse
@@ -16,6 +17,7 @@ import torch
 from nerf_downstream_amd import gin_lite as gin
 from nerf_downstream_amd.safe_load import load_checkpoint_file
 from nerf_downstream_amd.co3d_2d.src.data.loader import DataModule
+from nerf_downstream_amd.co3d_2d.src.model.models import ViTBased
 from nerf_downstream_amd.co3d_2d.src.modules.classification import LitModel, lr_at
 
 logger = logging.getLogger("co3d_2d")
@@ -39,6 +41,9 @@ def run(ckpt_path, resume_training, seed, run_name="resnet18", num_gpus=1, log_e
     os.makedirs(out_dir, exist_ok=True)
     data = DataModule()
     model = LitModel().to(dev)
+    if int(precision) == 16 and isinstance(model.model, ViTBased):
+        raise NotImplementedError(f"{model.model_name}: the attention kernel is fp32 only and a ViT does not run mixed; "
+                                  "set run.precision = 32 (configs/vit*.gin do)")
     opt = model.configure_optimizers()
     step, epoch0 = 0, 0
     if resume_training and ckpt_path:
