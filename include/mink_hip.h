@@ -55,13 +55,14 @@ extern "C" {
 #define MINK_STATUS_NOT_ASCENDING 4u /* mink_coords_build_levels, informational: the input rows' keys are not strictly ascending
                                         (when CLEAR the rows were their own unique rows and level 0's hash map was left empty) */
 
+/* ------------------------------------------------------------------ error text and ABI version (csrc/coords.hip) */
 const char *mink_last_error(void);
 /* 2: every scratch buffer is passed with its size; 3: MinkStem.xb (bf16 storage); 4: mink_net_* (the whole trunk per call).
  * A caller compiled or bound against this header refuses a library that answers another number. */
 #define MINK_ABI_VERSION 4
 int mink_abi_version(void);
 
-/* ------------------------------------------------------------------ coordinate maps
+/* ------------------------------------------------------------------ coordinate maps (csrc/coords.hip)
  * Coordinate hash map: open addressing, linear probing, 64-bit packed keys
  * (16 bits each for batch | x+2^15 | y+2^15 | z+2^15), int32 values.
  * Replaces ME's CoordinateMapCPU/GPU (insert_and_map / stride / kernel_map) behind
@@ -213,7 +214,7 @@ int mink_class_partition_batch(int32_t n_maps, const MinkClassPartitionDesc *des
 int mink_batch_offsets(const int32_t *coords, int64_t n, int32_t B, int32_t *batch_offsets,
                        uint32_t *status, void *stream);
 
-/* ------------------------------------------------------------------ sparse convolution
+/* ------------------------------------------------------------------ sparse convolution (csrc/conv.hip, csrc/conv_wgrad.hip)
  * Replaces ME ConvolutionForward/BackwardKernel behind ME.MinkowskiConvolution
  * (modules/common.py:116-125; the algorithm is re-stated by the reference at
  * sparse_conv.py:122-144): out[o] = sum_k in[nbr[o][k]] @ W[k]  (+ bias).
@@ -278,6 +279,12 @@ int mink_conv_gather_gemm(const float *x, int64_t n_in, int32_t ldx, int32_t cin
                           const int32_t *row_perm, int64_t n_virtual, float *y, int32_t ldy,
                           int32_t cout, const float *bias, int32_t ksplit, float *workspace,
                           int64_t workspace_bytes, void *stream);
+/* mink_conv_gather_gemm that LEAVES a split launch's partial slabs in `workspace`: described with its consumers,
+ * mink_bn_small_fwd / mink_bn_small_bwd / mink_bn_bwd_slabs, in the batch-norm section below. */
+int mink_conv_gather_gemm_slabs(const float *x, int64_t n_in, int32_t ldx, int32_t cin, const float *w, int32_t w_transposed,
+                                int32_t flip_k, const int32_t *nbr, int64_t n_out, int32_t K, const int32_t *row_perm,
+                                int64_t n_virtual, float *y, int32_t ldy, int32_t cout, int32_t ksplit, float *workspace,
+                                int64_t workspace_bytes, int32_t *slabs_out, void *stream);
 /* Forward convolution that also emits the column statistics of its output for the batch norm that
  * follows (reference resnet_block.py:53-60: every 3x3x3 convolution feeds a norm): the un-split
  * kernel sums its tile in the epilogue, the split-K reduce sums while it adds the slabs -- y is
@@ -310,6 +317,7 @@ int mink_conv_wgrad_bn_relu_pool(const float *x, int64_t n_in, int32_t ldx, int3
                                  const float *dgamma, const float *dbeta, const int32_t *nbr, int64_t n_out,
                                  int32_t K, float *dw, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ dense GEMM, classifier head and loss (csrc/dense.hip) */
 /* Data gradient of a 1x1x1 convolution as a plain GEMM: y[n][N] = x[n][Kd] @ W^T with the FORWARD kernel W[N = cin][Kd = cout]
  * (the `downsample` convolution of a residual block, models/mink/resnet.py:120-128), one fp32 MFMA accumulator chain per
  * element, k ascending -- the same sum mink_conv_gather_gemm forms for a one-column table.  Kd a multiple of 4. */
@@ -318,22 +326,6 @@ int mink_dense_xwt(const float *x, const float *w, int64_t n, int32_t Kd, int32_
  * With idx = the forward table of a kernel-volume-1 strided convolution this adds the shortcut's data gradient into the
  * rows of the block-input gradient it reaches (about one in eight). */
 int mink_rows_scatter_add(const float *src, const int32_t *idx, int64_t n_src, int32_t C, float *dst, void *stream);
-
-/* ------------------------------------------------------------------ pooling / reductions
- * MinkowskiSumPooling(k=2,s=2) (resnet.py:62-64): out[o] = sum_k in[nbr[o][k]] with the
- * 2^3 children table; backward dIn[i] = dOut[in2out[i]].
- */
-int mink_pool_sum_fwd(const float *x, int32_t ldx, int32_t C, const int32_t *nbr, int64_t n_out, int32_t K,
-                      float *y, void *stream);
-int mink_pool_sum_bwd(const float *dy, int32_t C, const int32_t *in2out, int64_t n_in, float *dx,
-                      void *stream);
-
-/* MinkowskiGlobalAvgPooling (resnet.py:15-22,175): y[b] = mean of rows
- * [batch_offsets[b], batch_offsets[b+1]); backward dx[i] = dy[b]/N_b. */
-int mink_global_avg_fwd(const float *x, int32_t C, const int32_t *batch_offsets, int32_t B, float *y,
-                        void *stream);
-int mink_global_avg_bwd(const float *dy, int32_t C, const int32_t *batch_offsets, int32_t B, int64_t n,
-                        float *dx, void *stream);
 
 /* Classifier head in one launch each way: logits[b] = mean_{rows of batch b} x[row] @ W + bias, i.e.
  * MinkowskiGlobalAvgPooling followed by the kernel-volume-1 `final` convolution with bias (models/mink/resnet.py:15-22,
@@ -351,141 +343,21 @@ int mink_softmax_ce_forward(const float *logits, const int64_t *labels, int32_t 
 int mink_softmax_ce_backward(const float *prob, const int64_t *labels, const float *grad_loss, int32_t B, int32_t ncls,
                              float *dlogits, void *stream);
 
-/* TensorField.sparse() feature averaging (ME UNWEIGHTED_AVERAGE, resnet.py:164):
- * y[u] = mean_{j in [seg[u],seg[u+1])} x[members[j]] (members sorted by input row). */
-int mink_segment_mean(const float *x, int32_t ldx, int32_t C, const int32_t *members, const int32_t *seg,
-                      int64_t n_out, float *y, void *stream);
-
-/* ------------------------------------------------------------------ segmentation tail (csrc/seghead.hip)
- * SparseTensor.slice() (reference res16unet.py:435), any C >= 1.  Forward: y[i][:] = x[idx[i]][:], i < n (an index outside
- * [0, n_src) gives a zero row).  Backward: y[r][:] = sum of x[members[j]][:] over j in [seg[r], seg[r+1]), in member
- * order (fixed-order fp32 sum: bitwise reproducible), with the (members, seg) pair TensorField.sparse() builds for
- * mink_segment_mean. */
-int mink_rows_gather(const float *x, int64_t ldx, int64_t n_src, int32_t C, const int32_t *idx, int64_t n, float *y, void *stream);
-int mink_segment_sum(const float *x, int32_t ldx, int32_t C, const int32_t *members, const int32_t *seg,
-                     int64_t n_out, float *y, void *stream);
-
-/* torch.nn.functional.cross_entropy(z, labels, weight=w, ignore_index=ignore_label) (mean reduction) over per-point logits
- * z[n][C] (fp32, row stride ldz >= C), 2 <= C <= 128, with the prediction, the confusion matrix and the label counts out
- * of the same pass over the logits (reference modules/segmentation_training.py SegLoss :27-44, utils fast_hist).
- *   labels        : int64 [n] (labels_int64 != 0) or int32 [n]
- *   w             : class weights [C], NULL = all ones
- *   a row is VALID when 0 <= label < C and label != ignore_label, IGNORED when label == ignore_label and BAD otherwise;
- *   bad rows are counted and otherwise treated like ignored ones (no device-side assert)
- *   lse[n]        : log sum exp of every row -- all the backward pass needs besides the logits
- *   pred[n]       : int32 argmax (lowest index on ties); NULL to skip
- *   hist[C*C]     : int64, hist[label * C + pred] over the valid rows (zeroed here); NULL to skip
- *   stats         : 40 bytes, 8-byte aligned: double num = sum_valid w[y] * (lse - z[y]); double den = sum_valid w[y];
- *                   int64 n_valid; int64 n_ignored; int64 n_bad -- in this order
- *   loss          : fp32 device scalar num / den (NaN when nothing is valid, as torch gives)
- *   workspace     : >= mink_seg_ce_workspace_bytes(n, C), 8-byte aligned (per-workgroup partial sums)
- * The assignment of rows to workgroups is fixed, every workgroup writes one (num, den) partial in double and a second
- * launch adds the partials in index order: the result is bitwise the same from run to run.  n == 0 writes loss = NaN,
- * a zero histogram and zero stats.
- * Backward: dz[i][j] = g / den * valid_i * w[y_i] * (exp(z[i][j] - lse[i]) - [j == y_i]); g = *grad_loss and den = stats'
- * second double are read on the device; every element of the dense dz[n][C] is written (zeros on ignored / bad rows, and
- * everywhere when den == 0, where torch writes NaN). */
-int64_t mink_seg_ce_workspace_bytes(int64_t n, int32_t C);
-int mink_seg_ce_forward(const float *z, int64_t ldz, const void *labels, int32_t labels_int64, const float *w, int64_t ignore_label,
-                        int64_t n, int32_t C, float *lse, int32_t *pred, int64_t *hist, void *stats, float *loss, void *workspace,
-                        int64_t workspace_bytes, void *stream);
-int mink_seg_ce_backward(const float *z, int64_t ldz, const void *labels, int32_t labels_int64, const float *w, int64_t ignore_label,
-                         const float *lse, const void *stats, const float *grad_loss, int64_t n, int32_t C, float *dz, void *stream);
-
-/* ------------------------------------------------------------------ batch norm / relu / add
- * MinkowskiBatchNorm == torch.nn.BatchNorm1d on the feature matrix
- * (modules/common.py:22-24; witness resnet.py:101-105), MinkowskiReLU (resnet.py:61),
- * residual `out += residual` (modules/resnet_block.py:66).
+/* ------------------------------------------------------------------ pooling (csrc/pool.hip)
+ * MinkowskiSumPooling(k=2,s=2) (resnet.py:62-64): out[o] = sum_k in[nbr[o][k]] with the
+ * 2^3 children table; backward dIn[i] = dOut[in2out[i]].
  */
-int64_t mink_bn_workspace_bytes(int64_t n, int32_t C);
+int mink_pool_sum_fwd(const float *x, int32_t ldx, int32_t C, const int32_t *nbr, int64_t n_out, int32_t K,
+                      float *y, void *stream);
+int mink_pool_sum_bwd(const float *dy, int32_t C, const int32_t *in2out, int64_t n_in, float *dx,
+                      void *stream);
 
-/* Batch statistics: mean[C], invstd[C] = 1/sqrt(biased var + eps); if running_mean !=
- * NULL also updates running stats with `momentum` (unbiased variance, torch semantics). */
-int mink_bn_stats(const float *x, int64_t n, int32_t C, float eps, float momentum, float *mean,
-                  float *invstd, float *running_mean, float *running_var, void *workspace, int64_t workspace_bytes,
-                  void *stream);
-
-/* y = [relu]( (x-mean)*invstd*gamma + beta [+ residual] ) */
-int mink_bn_apply(const float *x, int64_t n, int32_t C, const float *mean, const float *invstd,
-                  const float *gamma, const float *beta, const float *residual, int32_t relu, float *y,
-                  void *stream);
-/* Training-mode forward in one call: mink_bn_stats followed by mink_bn_apply (mean / invstd are
- * outputs kept for backward).  A single-launch variant for small layers (one workgroup per four
- * channels over all rows) was measured 3-9x slower than the three launches (strided 16-byte
- * column reads) and is not provided. */
-int mink_bn_fwd(const float *x, int64_t n, int32_t C, float eps, float momentum, const float *gamma,
-                const float *beta, const float *residual, int32_t relu, float *y, float *mean, float *invstd,
-                float *running_mean, float *running_var, void *workspace, int64_t workspace_bytes, void *stream);
-/* Statistics from column partials [rows][2][C] (sum, sum of squares; double) that the producer of
- * x already computed -- mink_conv_gather_gemm_stats -- instead of a reduction pass over x. */
-int mink_bn_stats_from_partials(const double *partial, int32_t rows, int64_t n, int32_t C, float eps,
-                                float momentum, float *mean, float *invstd, float *running_mean,
-                                float *running_var, void *stream);
-
-/* Backward of the op above.  y (the forward output) is only read when relu != 0.
- * dgamma[C], dbeta[C]; dx[n][C]; dresidual (may be NULL) receives the masked grad. */
-int mink_bn_bwd(const float *dy, const float *x, const float *y, int64_t n, int32_t C, const float *mean,
-                const float *invstd, const float *gamma, int32_t relu, float *dx, float *dresidual,
-                float *dgamma, float *dbeta, void *workspace, int64_t workspace_bytes, void *stream);
-
-/* ------------------------------------------------------------------ instance norm / layer norm (csrc/norm.hip)
- * MinkowskiInstanceNorm (modules/common.py:25-26): sample b owns rows [batch_offsets[b], batch_offsets[b+1]) of x[n][C]
- * (int32 [B+1] on the device, batch_offsets[B] == n; empty samples are legal) and is normalised per channel by its own
- * mean / biased variance:  y = [relu]( (x - mean_b) * invstd_b * gamma + beta [+ residual] ),  invstd = 1/sqrt(var + eps).
- * Any C in [1, 4096] (16-byte accesses when C % 4 == 0 and every matrix is 16-byte aligned, dword accesses otherwise),
- * 1 <= B <= 65535, n < 2^31.  mean[B][C], invstd[B][C] are outputs kept for backward (0, 0 for an empty sample).
- * Three launches whatever B is, nothing is read back; sum x and sum x^2 are accumulated in double, no floating-point
- * atomics, partials combined in a fixed order: bitwise reproducible.
- *   workspace : >= mink_in_workspace_bytes(n, C, B), 8-byte aligned */
-int64_t mink_in_workspace_bytes(int64_t n, int32_t C, int32_t B);
-int mink_in_fwd(const float *x, int64_t n, int32_t C, const int32_t *batch_offsets, int32_t B, float eps, const float *gamma,
-                const float *beta, const float *residual, int32_t relu, float *y, float *mean, float *invstd, void *workspace,
-                int64_t workspace_bytes, void *stream);
-/* Backward of the op above (four launches).  y (the forward output) is only read when relu != 0.
- * dx[n][C] per sample from that sample's sum g and sum g*xhat (g = dy masked by y > 0); dgamma[C], dbeta[C] summed over all
- * rows of all samples (samples added in index order); dresidual (may be NULL) receives g. */
-int mink_in_bwd(const float *dy, const float *x, const float *y, int64_t n, int32_t C, const int32_t *batch_offsets, int32_t B,
-                const float *mean, const float *invstd, const float *gamma, int32_t relu, float *dx, float *dresidual,
-                float *dgamma, float *dbeta, void *workspace, int64_t workspace_bytes, void *stream);
-
-/* MinkowskiLayerNorm == torch.nn.LayerNorm(C) on the feature matrix (modules/common.py:27-28): every row is normalised over
- * its C channels, 1 <= C <= 512:  y[r] = [relu]( (x[r] - mean_r) * invstd_r * gamma + beta [+ residual[r]] ).
- * One launch; the row stays in registers between the mean pass and the sum (x - mean)^2 pass (two-pass variance).
- * mean[n], invstd[n] are outputs kept for backward. */
-int mink_ln_fwd(const float *x, int64_t n, int32_t C, float eps, const float *gamma, const float *beta, const float *residual,
-                int32_t relu, float *y, float *mean, float *invstd, void *stream);
-/* Backward (two launches): dx[n][C] per row, dresidual (may be NULL) the masked dy, dgamma[C] / dbeta[C] as per-workgroup
- * column partials (double) added in a fixed order.  workspace: >= mink_ln_workspace_bytes(n, C), 8-byte aligned. */
-int64_t mink_ln_workspace_bytes(int64_t n, int32_t C);
-int mink_ln_bwd(const float *dy, const float *x, const float *y, int64_t n, int32_t C, const float *mean, const float *invstd,
-                const float *gamma, int32_t relu, float *dx, float *dresidual, float *dgamma, float *dbeta, void *workspace,
-                int64_t workspace_bytes, void *stream);
-
-/* Split form for MinkowskiSyncBatchNorm (train.py:106-107): per-channel sums stay on the device
- * as doubles so the host can all-reduce them (RCCL) between the passes.
- *   mink_bn_reduce mode 0: sums = [sum x | sum x^2];  mode 1: [sum g | sum g*xhat] (g masked by y>0
- *   when y != NULL).  n_total: device double (rows over all ranks). */
-int mink_bn_reduce(int32_t mode, const float *a, const float *b, const float *y, int64_t n, int32_t C,
-                   const float *mean, const float *invstd, double *sums, void *workspace, int64_t workspace_bytes, void *stream);
-int mink_bn_stats_from_sums(const double *sums, const double *n_total, int32_t C, float eps, float momentum,
-                            float *mean, float *invstd, float *running_mean, float *running_var,
-                            void *stream);
-int mink_bn_bwd_from_sums(const float *dy, const float *x, const float *y, int64_t n, int32_t C,
-                          const double *sums, const double *n_total, const float *mean,
-                          const float *invstd, const float *gamma, int32_t relu, float *dx,
-                          float *dresidual, float *scratch2c, void *stream);
-
-/* Fused tail of the stem: y_pool = SumPool(relu(BN(x))) without materialising the normalised
- * [n,C] tensor (bn1 -> relu -> pool, resnet.py:58-64).  `nbr[n_out][K]` is the 2^3 children
- * table, `in2out[n]` the stride map.  Statistics come from mink_bn_stats; the ReLU mask of the
- * backward pass is recomputed from x. */
-int mink_bn_relu_pool_fwd(const float *x, int32_t C, const float *mean, const float *invstd,
-                          const float *gamma, const float *beta, const int32_t *nbr, int64_t n_out,
-                          int32_t K, float *y, void *stream);
-int mink_bn_relu_pool_bwd(const float *dy_pool, const float *x, int64_t n, int32_t C, const float *mean,
-                          const float *invstd, const float *gamma, const float *beta,
-                          const int32_t *in2out, float *dx, float *dgamma, float *dbeta,
-                          void *workspace, int64_t workspace_bytes, void *stream);
+/* MinkowskiGlobalAvgPooling (resnet.py:15-22,175): y[b] = mean of rows
+ * [batch_offsets[b], batch_offsets[b+1]); backward dx[i] = dy[b]/N_b. */
+int mink_global_avg_fwd(const float *x, int32_t C, const int32_t *batch_offsets, int32_t B, float *y,
+                        void *stream);
+int mink_global_avg_bwd(const float *dy, int32_t C, const int32_t *batch_offsets, int32_t B, int64_t n,
+                        float *dx, void *stream);
 
 /* Max pooling over a neighbour table whose windows may overlap -- the 3x3 stride-2 pooling of the dense 2-D
  * comparison network (torchvision ResNet, reference co3d_2d/src/model/models.py:18-23), which is its only caller: C % 4 == 0,
@@ -498,7 +370,7 @@ int mink_pool_max_fwd(const float *x, int32_t C, const int32_t *nbr, int64_t n_o
 int mink_pool_max_bwd(const float *dy, const int32_t *arg, int32_t C, const int32_t *nbr_t, int64_t n_in, int32_t K,
                       float *dx, void *stream);
 
-/* ------------------------------------------------------------------ sparse pooling family (csrc/pool.hip)
+/* The sparse pooling family.
  * Conventions of mink_pool_sum_* / mink_in_* / mink_ln_*: fp32 features x[n][C] with a row pitch ldx >= C (outputs and
  * gradients are contiguous, pitch C), any 1 <= C <= 4096 -- 16-byte accesses when C % 4 == 0, ldx % 4 == 0 and the pointers are
  * 16-byte aligned, dword accesses otherwise --, no host read-back, no floating-point atomics, sums in a fixed order (two runs
@@ -537,6 +409,182 @@ int mink_global_max_bwd(const float *dy, const int32_t *arg, int64_t n, int32_t 
 int mink_global_sum_fwd(const float *x, int64_t n, int32_t ldx, int32_t C, const int32_t *batch_offsets, int32_t B, float *y,
                         void *workspace, int64_t workspace_bytes, void *stream);
 int mink_global_sum_bwd(const float *dy, int64_t n, int32_t C, const int32_t *batch_offsets, int32_t B, float *dx, void *stream);
+
+/* ------------------------------------------------------------------ segmentation tail (csrc/seghead.hip)
+ * SparseTensor.slice() (reference res16unet.py:435), any C >= 1.  Forward: y[i][:] = x[idx[i]][:], i < n (an index outside
+ * [0, n_src) gives a zero row).  Backward (mink_segment_sum, declared beside
+ * mink_segment_mean in the field section): y[r][:] = sum of x[members[j]][:] over j in [seg[r], seg[r+1]), in member
+ * order (fixed-order fp32 sum: bitwise reproducible), with the (members, seg) pair TensorField.sparse() builds for
+ * mink_segment_mean. */
+int mink_rows_gather(const float *x, int64_t ldx, int64_t n_src, int32_t C, const int32_t *idx, int64_t n, float *y, void *stream);
+
+/* torch.nn.functional.cross_entropy(z, labels, weight=w, ignore_index=ignore_label) (mean reduction) over per-point logits
+ * z[n][C] (fp32, row stride ldz >= C), 2 <= C <= 128, with the prediction, the confusion matrix and the label counts out
+ * of the same pass over the logits (reference modules/segmentation_training.py SegLoss :27-44, utils fast_hist).
+ *   labels        : int64 [n] (labels_int64 != 0) or int32 [n]
+ *   w             : class weights [C], NULL = all ones
+ *   a row is VALID when 0 <= label < C and label != ignore_label, IGNORED when label == ignore_label and BAD otherwise;
+ *   bad rows are counted and otherwise treated like ignored ones (no device-side assert)
+ *   lse[n]        : log sum exp of every row -- all the backward pass needs besides the logits
+ *   pred[n]       : int32 argmax (lowest index on ties); NULL to skip
+ *   hist[C*C]     : int64, hist[label * C + pred] over the valid rows (zeroed here); NULL to skip
+ *   stats         : 40 bytes, 8-byte aligned: double num = sum_valid w[y] * (lse - z[y]); double den = sum_valid w[y];
+ *                   int64 n_valid; int64 n_ignored; int64 n_bad -- in this order
+ *   loss          : fp32 device scalar num / den (NaN when nothing is valid, as torch gives)
+ *   workspace     : >= mink_seg_ce_workspace_bytes(n, C), 8-byte aligned (per-workgroup partial sums)
+ * The assignment of rows to workgroups is fixed, every workgroup writes one (num, den) partial in double and a second
+ * launch adds the partials in index order: the result is bitwise the same from run to run.  n == 0 writes loss = NaN,
+ * a zero histogram and zero stats.
+ * Backward: dz[i][j] = g / den * valid_i * w[y_i] * (exp(z[i][j] - lse[i]) - [j == y_i]); g = *grad_loss and den = stats'
+ * second double are read on the device; every element of the dense dz[n][C] is written (zeros on ignored / bad rows, and
+ * everywhere when den == 0, where torch writes NaN). */
+int64_t mink_seg_ce_workspace_bytes(int64_t n, int32_t C);
+int mink_seg_ce_forward(const float *z, int64_t ldz, const void *labels, int32_t labels_int64, const float *w, int64_t ignore_label,
+                        int64_t n, int32_t C, float *lse, int32_t *pred, int64_t *hist, void *stats, float *loss, void *workspace,
+                        int64_t workspace_bytes, void *stream);
+int mink_seg_ce_backward(const float *z, int64_t ldz, const void *labels, int32_t labels_int64, const float *w, int64_t ignore_label,
+                         const float *lse, const void *stats, const float *grad_loss, int64_t n, int32_t C, float *dz, void *stream);
+
+/* ------------------------------------------------------------------ batch norm (csrc/batchnorm.hip)
+ * MinkowskiBatchNorm == torch.nn.BatchNorm1d on the feature matrix
+ * (modules/common.py:22-24; witness resnet.py:101-105), MinkowskiReLU (resnet.py:61),
+ * residual `out += residual` (modules/resnet_block.py:66).
+ */
+int64_t mink_bn_workspace_bytes(int64_t n, int32_t C);
+
+/* Batch statistics: mean[C], invstd[C] = 1/sqrt(biased var + eps); if running_mean !=
+ * NULL also updates running stats with `momentum` (unbiased variance, torch semantics). */
+int mink_bn_stats(const float *x, int64_t n, int32_t C, float eps, float momentum, float *mean,
+                  float *invstd, float *running_mean, float *running_var, void *workspace, int64_t workspace_bytes,
+                  void *stream);
+
+/* y = [relu]( (x-mean)*invstd*gamma + beta [+ residual] ) */
+int mink_bn_apply(const float *x, int64_t n, int32_t C, const float *mean, const float *invstd,
+                  const float *gamma, const float *beta, const float *residual, int32_t relu, float *y,
+                  void *stream);
+/* Training-mode forward in one call: mink_bn_stats followed by mink_bn_apply (mean / invstd are
+ * outputs kept for backward).  A single-launch variant for small layers (one workgroup per four
+ * channels over all rows) was measured 3-9x slower than the three launches (strided 16-byte
+ * column reads) and is not provided. */
+int mink_bn_fwd(const float *x, int64_t n, int32_t C, float eps, float momentum, const float *gamma,
+                const float *beta, const float *residual, int32_t relu, float *y, float *mean, float *invstd,
+                float *running_mean, float *running_var, void *workspace, int64_t workspace_bytes, void *stream);
+/* Statistics from column partials [rows][2][C] (sum, sum of squares; double) that the producer of
+ * x already computed -- mink_conv_gather_gemm_stats -- instead of a reduction pass over x. */
+int mink_bn_stats_from_partials(const double *partial, int32_t rows, int64_t n, int32_t C, float eps,
+                                float momentum, float *mean, float *invstd, float *running_mean,
+                                float *running_var, void *stream);
+
+/* Backward of the op above.  y (the forward output) is only read when relu != 0.
+ * dgamma[C], dbeta[C]; dx[n][C]; dresidual (may be NULL) receives the masked grad. */
+int mink_bn_bwd(const float *dy, const float *x, const float *y, int64_t n, int32_t C, const float *mean,
+                const float *invstd, const float *gamma, int32_t relu, float *dx, float *dresidual,
+                float *dgamma, float *dbeta, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Split form for MinkowskiSyncBatchNorm (train.py:106-107): per-channel sums stay on the device
+ * as doubles so the host can all-reduce them (RCCL) between the passes.
+ *   mink_bn_reduce mode 0: sums = [sum x | sum x^2];  mode 1: [sum g | sum g*xhat] (g masked by y>0
+ *   when y != NULL).  n_total: device double (rows over all ranks). */
+int mink_bn_reduce(int32_t mode, const float *a, const float *b, const float *y, int64_t n, int32_t C,
+                   const float *mean, const float *invstd, double *sums, void *workspace, int64_t workspace_bytes, void *stream);
+int mink_bn_stats_from_sums(const double *sums, const double *n_total, int32_t C, float eps, float momentum,
+                            float *mean, float *invstd, float *running_mean, float *running_var,
+                            void *stream);
+int mink_bn_bwd_from_sums(const float *dy, const float *x, const float *y, int64_t n, int32_t C,
+                          const double *sums, const double *n_total, const float *mean,
+                          const float *invstd, const float *gamma, int32_t relu, float *dx,
+                          float *dresidual, float *scratch2c, void *stream);
+
+/* Fused tail of the stem: y_pool = SumPool(relu(BN(x))) without materialising the normalised
+ * [n,C] tensor (bn1 -> relu -> pool, resnet.py:58-64).  `nbr[n_out][K]` is the 2^3 children
+ * table, `in2out[n]` the stride map.  Statistics come from mink_bn_stats; the ReLU mask of the
+ * backward pass is recomputed from x. */
+int mink_bn_relu_pool_fwd(const float *x, int32_t C, const float *mean, const float *invstd,
+                          const float *gamma, const float *beta, const int32_t *nbr, int64_t n_out,
+                          int32_t K, float *y, void *stream);
+int mink_bn_relu_pool_bwd(const float *dy_pool, const float *x, int64_t n, int32_t C, const float *mean,
+                          const float *invstd, const float *gamma, const float *beta,
+                          const int32_t *in2out, float *dx, float *dgamma, float *dbeta,
+                          void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Batch-norm finalize inside the apply pass.
+ * mink_bn_apply_from_partials = mink_bn_stats_from_partials + mink_bn_apply (the reference's MinkowskiBatchNorm forward,
+ * co3d_3d/src/models/mink/modules/common.py:22-24) -- as ONE launch when `rows` is at most the fold limit (mink_bn_set_fold; at
+ * most 128; DEFAULT 0 = never: see below), re-reading the partials in every workgroup of the pass costs at most ~8 MB in total,
+ * and C is a multiple of 64: every workgroup of the apply pass sums the partial rows of its 64 channels itself, in the
+ * order of the finalize kernel (results are bit-identical to the two-call sequence; mean / invstd / running statistics are
+ * written by the first row chunk).  mink_bn_bwd folds its finalize into its apply pass under the same conditions.  Every
+ * workgroup re-reads rows x 1 KB of partials and starts its pass behind that: measured SLOWER than the separate finalize launch
+ * in every configuration (B=16: +5 % folding every layer, +-0 with the bytes rule; ResNet34 at B=4: +2.5 % with the bytes rule
+ * -- DESIGN.md Appendix A), so it is off by default and kept as a tested, bit-identical option.  mink_bn_set_fold(max_rows) sets the limit (0: never; 1000 + r: r rows
+ * without the total-bytes rule, for tests) and returns the previous one. */
+int mink_bn_set_fold(int32_t max_rows);
+/* mink_bn_bwd whose incoming gradient is still the `nslab` split-K slabs ([nslab][n][C] at dy_slabs) of the data-gradient
+ * convolution that produced it (mink_conv_gather_gemm_slabs): the column-reduction pass sums them in slab order -- what
+ * splitk_reduce would have written, bit for bit --, adds `addend` behind them (optional [n][C]: the gradient of a residual branch,
+ * what mink_eltwise(.., 2, ..) would have added) and stores the sum to dy_sum on the way.  One or two launches and passes over
+ * the gradient less per convolution backward.  C <= 1024. */
+int mink_bn_bwd_slabs(const float *dy_slabs, int32_t nslab, const float *addend, float *dy_sum, const float *x, const float *y, int64_t n, int32_t C,
+                      const float *mean, const float *invstd, const float *gamma, int32_t relu, float *dx, float *dresidual,
+                      float *dgamma, float *dbeta, void *workspace, int64_t workspace_bytes, void *stream);
+int mink_bn_apply_from_partials(const float *x, int64_t n, int32_t C, const double *partial, int32_t rows, float eps, float momentum,
+                                const float *gamma, const float *beta, const float *residual, int32_t relu, float *y, float *mean,
+                                float *invstd, float *running_mean, float *running_var, void *stream);
+
+/* Few-row layers: batch norm in one launch.
+ * Below mink_bn_small_rows() rows (1024; 0 when switched off with mink_bn_set_small(0)) a batch norm as three dependent launches
+ * (column partials, finalize, apply: the reference's MinkowskiBatchNorm = nn.BatchNorm1d, co3d_3d/src/models/mink/modules/
+ * common.py:22-24, resnet_block.py:53-69) is launch latency, not bytes.  Here a workgroup owns 16 channels and ALL rows:
+ *   mink_conv_gather_gemm_slabs  mink_conv_gather_gemm that LEAVES a split launch's partial slabs in `workspace`
+ *                                ([*slabs_out][n_out][cout]; *slabs_out == 1: y is complete) -- no bias
+ *   mink_bn_small_fwd            y = sum of `nslab` slabs (nslab == 0: y as given) -> batch statistics (mean, invstd, running
+ *                                statistics as mink_bn_stats) -> out = [relu](bn(y) [+ residual])
+ *   mink_bn_small_bwd            mink_bn_bwd in one launch; nslab > 0: the incoming gradient is the sum of `nslab` slabs at
+ *                                `dy` ([nslab][n][C]) plus `addend` ([n][C], optional: a residual branch's gradient),
+ *                                written to dy_sum
+ * C must be a multiple of 16.  Results are deterministic; the summation order differs from the three-launch form (last-bit
+ * differences), which is why the module-by-module path, the yardstick of the bitwise tests, never takes these. */
+int32_t mink_bn_small_rows(void);
+int mink_bn_set_small(int32_t on);
+int mink_bn_small_fwd(const float *slabs, int32_t nslab, int64_t n, int32_t C, float *y, float eps, float momentum,
+                      const float *gamma, const float *beta, const float *residual, int32_t relu, float *out, float *mean,
+                      float *invstd, float *running_mean, float *running_var, void *stream);
+int mink_bn_small_bwd(const float *dy, int32_t nslab, const float *addend, float *dy_sum, const float *x, const float *y, int64_t n, int32_t C,
+                      const float *mean, const float *invstd, const float *gamma, int32_t relu, float *dx, float *dresidual,
+                      float *dgamma, float *dbeta, void *stream);
+
+/* ------------------------------------------------------------------ instance norm / layer norm (csrc/norm.hip)
+ * MinkowskiInstanceNorm (modules/common.py:25-26): sample b owns rows [batch_offsets[b], batch_offsets[b+1]) of x[n][C]
+ * (int32 [B+1] on the device, batch_offsets[B] == n; empty samples are legal) and is normalised per channel by its own
+ * mean / biased variance:  y = [relu]( (x - mean_b) * invstd_b * gamma + beta [+ residual] ),  invstd = 1/sqrt(var + eps).
+ * Any C in [1, 4096] (16-byte accesses when C % 4 == 0 and every matrix is 16-byte aligned, dword accesses otherwise),
+ * 1 <= B <= 65535, n < 2^31.  mean[B][C], invstd[B][C] are outputs kept for backward (0, 0 for an empty sample).
+ * Three launches whatever B is, nothing is read back; sum x and sum x^2 are accumulated in double, no floating-point
+ * atomics, partials combined in a fixed order: bitwise reproducible.
+ *   workspace : >= mink_in_workspace_bytes(n, C, B), 8-byte aligned */
+int64_t mink_in_workspace_bytes(int64_t n, int32_t C, int32_t B);
+int mink_in_fwd(const float *x, int64_t n, int32_t C, const int32_t *batch_offsets, int32_t B, float eps, const float *gamma,
+                const float *beta, const float *residual, int32_t relu, float *y, float *mean, float *invstd, void *workspace,
+                int64_t workspace_bytes, void *stream);
+/* Backward of the op above (four launches).  y (the forward output) is only read when relu != 0.
+ * dx[n][C] per sample from that sample's sum g and sum g*xhat (g = dy masked by y > 0); dgamma[C], dbeta[C] summed over all
+ * rows of all samples (samples added in index order); dresidual (may be NULL) receives g. */
+int mink_in_bwd(const float *dy, const float *x, const float *y, int64_t n, int32_t C, const int32_t *batch_offsets, int32_t B,
+                const float *mean, const float *invstd, const float *gamma, int32_t relu, float *dx, float *dresidual,
+                float *dgamma, float *dbeta, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* MinkowskiLayerNorm == torch.nn.LayerNorm(C) on the feature matrix (modules/common.py:27-28): every row is normalised over
+ * its C channels, 1 <= C <= 512:  y[r] = [relu]( (x[r] - mean_r) * invstd_r * gamma + beta [+ residual[r]] ).
+ * One launch; the row stays in registers between the mean pass and the sum (x - mean)^2 pass (two-pass variance).
+ * mean[n], invstd[n] are outputs kept for backward. */
+int mink_ln_fwd(const float *x, int64_t n, int32_t C, float eps, const float *gamma, const float *beta, const float *residual,
+                int32_t relu, float *y, float *mean, float *invstd, void *stream);
+/* Backward (two launches): dx[n][C] per row, dresidual (may be NULL) the masked dy, dgamma[C] / dbeta[C] as per-workgroup
+ * column partials (double) added in a fixed order.  workspace: >= mink_ln_workspace_bytes(n, C), 8-byte aligned. */
+int64_t mink_ln_workspace_bytes(int64_t n, int32_t C);
+int mink_ln_bwd(const float *dy, const float *x, const float *y, int64_t n, int32_t C, const float *mean, const float *invstd,
+                const float *gamma, int32_t relu, float *dx, float *dresidual, float *dgamma, float *dbeta, void *workspace,
+                int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------ trilinear interpolation and splat (csrc/interp.hip)
  * ME.MinkowskiInterpolation (reference co3d_3d/src/data/transforms.py:472,514-521 PerlinNoise; models/mink/fcnn.py:194-208
@@ -591,12 +639,22 @@ int mink_field_map(const float *tfield, int64_t n, int32_t ts, const uint64_t *t
  * slice dy + off_s (pitch ldy) with a CSR of the field rows grouped by voxel, rows with idx < 0 in no segment. */
 int mink_field_gather_cat(int32_t n_src, const float *const *x, const int32_t *ldx, const int64_t *rows, const int32_t *C,
                           const int32_t *const *idx, int64_t n, float *y, int32_t ldy, void *stream);
+
+/* TensorField.sparse() feature averaging (ME UNWEIGHTED_AVERAGE, resnet.py:164):
+ * y[u] = mean_{j in [seg[u],seg[u+1])} x[members[j]] (members sorted by input row). */
+int mink_segment_mean(const float *x, int32_t ldx, int32_t C, const int32_t *members, const int32_t *seg,
+                      int64_t n_out, float *y, void *stream);
+/* The plain sum over the same (members, seg) pair, in member order: the backward of SparseTensor.slice()
+ * (mink_rows_gather, segmentation tail) and of mink_field_gather_cat. */
+int mink_segment_sum(const float *x, int32_t ldx, int32_t C, const int32_t *members, const int32_t *seg,
+                     int64_t n_out, float *y, void *stream);
 /* Backward of mink_segment_mean (TensorField.sparse() of learned per-point features, reference fcnn.py:143-144,165):
  * dx[members[j]][:] = dy[u][:] / (seg[u+1] - seg[u]) for j in [seg[u], seg[u+1]), u < n_out; members[n_members] are rows of
  * dx (n_in rows of pitch lddx), each written exactly once; a member behind seg[n_out] belongs to no segment. */
 int mink_segment_mean_bwd(const float *dy, int32_t ldy, int32_t C, const int32_t *members, const int32_t *seg, int64_t n_out,
                           int64_t n_members, int64_t n_in, float *dx, int32_t lddx, void *stream);
 
+/* ------------------------------------------------------------------ elementwise (csrc/elementwise.hip) */
 /* Elementwise: mode 0: y = max(x,0); mode 1: dx = (y>0) ? dy : 0 (a=dy,b=y);
  * mode 2: y = a + b. */
 int mink_eltwise(const float *a, const float *b, int64_t count, int32_t mode, float *y, void *stream);
@@ -609,7 +667,15 @@ int mink_eltwise(const float *a, const float *b, int64_t count, int32_t mode, fl
 int mink_activation(const float *x, const float *gy, const float *slope, int32_t C, int64_t count, int32_t kind,
                     float alpha, float *out, void *stream);
 
-/* ------------------------------------------------------------------ dataset front-end
+/* Optimizer step over flat buffers.
+ * torch.optim.SGD's update with momentum and weight decay (the reference's optimizer: co3d_3d/src/modules/optim.py:12-14,
+ * co3d_3d/configs/co3d_cls.gin) for parameters w, gradients g and momentum buffers m that each live in ONE flat fp32 buffer of
+ * the same layout (n floats, a multiple of 4; padding elements are zero and stay zero):
+ *   g' = g + weight_decay w;  m = momentum m + g';  w = w - lr m        (dampening 0, no Nesterov; a zero m = torch's first step)
+ * zero_grad != 0 clears g behind the update (the next step's zero_grad memset).  One pass over 6 n floats. */
+int mink_sgd_step(float *w, float *g, float *m, int64_t n, float lr, float momentum, float weight_decay, int32_t zero_grad, void *stream);
+
+/* ------------------------------------------------------------------ dataset front-end (csrc/coords.hip)
  * PeRFception-CO3D `data.npz` batch on the device (reference co3d.py:160-166 de-quantisation,
  * :196-205 links -> coordinates and feature selection): `links[n]` flat indices x*ry*rz + y*rz + z,
  * `density[n]`, `sh_q[n][27]` uint8, per scene b (rows scene_offsets[b] .. scene_offsets[b+1])
@@ -626,7 +692,7 @@ int mink_decode_plenoxel(const int32_t *links, const float *density, const uint8
                          int32_t col_sh, int32_t col_ones, int32_t col_xyzs, float *scene_scratch, int32_t C,
                          int32_t *coords, float *feats, int32_t ldf, void *stream);
 
-/* ------------------------------------------------------------------ scene augmentation
+/* ------------------------------------------------------------------ scene augmentation (csrc/augment.hip)
  * The reference augments every scene on the CPU in its DataLoader workers (co3d.py:216-219 applies
  * transforms.Compose of the gin-listed classes of transforms.py; configs/co3d_aug3.gin:2-23).  Here
  * the host only DRAWS the per-scene randomness and the whole batch is transformed on the device.
@@ -676,7 +742,7 @@ int mink_augment_scenes(const void *coords, int32_t coords_are_int32, const floa
                         const uint32_t *streams, uint64_t seed, const int32_t *raw_cols, float *out_coords,
                         float *out_feats, int64_t ldo, int32_t *n_kept, void *workspace, int64_t workspace_bytes, void *stream);
 
-/* ------------------------------------------------------------------ segmentation scene augmentation
+/* ------------------------------------------------------------------ segmentation scene augmentation (csrc/seg_augment.hip)
  * The PeRFception-ScanNet recipe of the reference (configs/scannet_plenoxel.gin: RandomRotation, RandomCrop, RandomAffine,
  * CoordinateDropout, RandomFeatureJitter, RandomHorizontalFlip, RandomTranslation, ElasticDistortion) as one device program
  * per scene.  Its own parameter row: MINK_SEGAUG_PARAMS DOUBLES per scene (matrices row-major, applied as row-vector * M):
@@ -744,7 +810,7 @@ int mink_augment_seg_scenes(const void *coords, int32_t coords_are_int32, const 
                             float *out_feats, int64_t ldo, int32_t *out_rows, int32_t *status, void *workspace,
                             int64_t workspace_bytes, void *stream);
 
-/* ------------------------------------------------------------------ point-cloud voxel down-sampling
+/* ------------------------------------------------------------------ point-cloud voxel down-sampling (csrc/points.hip)
  * ME.utils.sparse_quantize(xyz, colours, labels=labels, quantization_size=Q, return_index=True, ignore_label=IGNORE) as the
  * reference's ScannetDataset calls it on every scene (co3d_3d/src/data/scannet.py:233-247), for a whole batch.  One parameter
  * row per scene, MINK_VOXDS_PARAMS doubles: Q (quantisation size; 0 = no down-sampling), VOXEL (voxel size), IGNORE (label).
@@ -775,7 +841,7 @@ int mink_voxel_downsample_scenes(const float *coords, const float *feats, int64_
                                  float *out_feats, int64_t ldo, int32_t *out_labels, int32_t *out_rows, int32_t *out_offsets,
                                  int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
 
-/* ------------------------------------------------------------------ colour program
+/* ------------------------------------------------------------------ colour program (csrc/points.hip)
  * The reference's colour stages (co3d_3d/src/data/transforms.py:44-122: ChromaticTranslation, ChromaticJitter,
  * NormalizeColor) as an ordered list of at most MINK_COLORAUG_MAX_OPS ops per scene, applied to the 3 colour columns
  * cols[0..2] of rows [0, scene_offsets[n_scenes]) (scene_offsets [n_scenes+1] on the device; rows past it are not touched).
@@ -801,7 +867,7 @@ int mink_color_augment_scenes(float *feats, int64_t ldf, const int32_t *cols_hos
                               int32_t n_scenes, const double *params, const uint32_t *streams, uint64_t seed,
                               const int32_t *key_rows, const int32_t *key_offsets, void *stream);
 
-/* ------------------------------------------------------------------ LiDAR scans
+/* ------------------------------------------------------------------ LiDAR scans (csrc/lidar.hip)
  * What the reference's SemanticKITTIDataset (co3d_3d/src/data/semantic_kitti.py:165-222) does to a raw scan around the
  * down-sampling and the recipe, for a whole batch.  Both are row passes: one thread per row, 16-byte row accesses when every
  * pointer and pitch involved is a multiple of 16 bytes and dwords otherwise, every output element written once from its own
@@ -832,15 +898,7 @@ int mink_lidar_decode_scans(const float *scan, const uint32_t *raw_labels, int64
 int mink_lidar_finish_rows(float *coords, int64_t n, const int32_t *n_rows, float voxel_size, float *feats, int64_t ldf, int32_t c0,
                            void *stream);
 
-/* ------------------------------------------------------------------ optimizer step over flat buffers
- * torch.optim.SGD's update with momentum and weight decay (the reference's optimizer: co3d_3d/src/modules/optim.py:12-14,
- * co3d_3d/configs/co3d_cls.gin) for parameters w, gradients g and momentum buffers m that each live in ONE flat fp32 buffer of
- * the same layout (n floats, a multiple of 4; padding elements are zero and stay zero):
- *   g' = g + weight_decay w;  m = momentum m + g';  w = w - lr m        (dampening 0, no Nesterov; a zero m = torch's first step)
- * zero_grad != 0 clears g behind the update (the next step's zero_grad memset).  One pass over 6 n floats. */
-int mink_sgd_step(float *w, float *g, float *m, int64_t n, float lr, float momentum, float weight_decay, int32_t zero_grad, void *stream);
-
-/* ------------------------------------------------------------------ whole residual blocks
+/* ------------------------------------------------------------------ whole residual blocks (csrc/trunk.hip)
  * One call = the complete launch sequence of one stage of the reference network, so the host pays one FFI call per
  * block instead of one per kernel (a Mink-ResNet14 step is ~300 launches; issued one by one from a Python autograd
  * graph the host, not the GPU, was the bottleneck).  Same kernels, same order, same results as the per-operator
@@ -918,57 +976,7 @@ int mink_stem_backward(const MinkStem *s, const MinkExec *ex);
 int mink_block_forward(const MinkBasicBlock *b, const MinkExec *ex);
 int mink_block_backward(const MinkBasicBlock *b, const MinkExec *ex);
 
-/* ------------------------------------------------------------------ batch-norm finalize inside the apply pass
- * mink_bn_apply_from_partials = mink_bn_stats_from_partials + mink_bn_apply (the reference's MinkowskiBatchNorm forward,
- * co3d_3d/src/models/mink/modules/common.py:22-24) -- as ONE launch when `rows` is at most the fold limit (mink_bn_set_fold; at
- * most 128; DEFAULT 0 = never: see below), re-reading the partials in every workgroup of the pass costs at most ~8 MB in total,
- * and C is a multiple of 64: every workgroup of the apply pass sums the partial rows of its 64 channels itself, in the
- * order of the finalize kernel (results are bit-identical to the two-call sequence; mean / invstd / running statistics are
- * written by the first row chunk).  mink_bn_bwd folds its finalize into its apply pass under the same conditions.  Every
- * workgroup re-reads rows x 1 KB of partials and starts its pass behind that: measured SLOWER than the separate finalize launch
- * in every configuration (B=16: +5 % folding every layer, +-0 with the bytes rule; ResNet34 at B=4: +2.5 % with the bytes rule
- * -- DESIGN.md Appendix A), so it is off by default and kept as a tested, bit-identical option.  mink_bn_set_fold(max_rows) sets the limit (0: never; 1000 + r: r rows
- * without the total-bytes rule, for tests) and returns the previous one. */
-int mink_bn_set_fold(int32_t max_rows);
-/* mink_bn_bwd whose incoming gradient is still the `nslab` split-K slabs ([nslab][n][C] at dy_slabs) of the data-gradient
- * convolution that produced it (mink_conv_gather_gemm_slabs): the column-reduction pass sums them in slab order -- what
- * splitk_reduce would have written, bit for bit --, adds `addend` behind them (optional [n][C]: the gradient of a residual branch,
- * what mink_eltwise(.., 2, ..) would have added) and stores the sum to dy_sum on the way.  One or two launches and passes over
- * the gradient less per convolution backward.  C <= 1024. */
-int mink_bn_bwd_slabs(const float *dy_slabs, int32_t nslab, const float *addend, float *dy_sum, const float *x, const float *y, int64_t n, int32_t C,
-                      const float *mean, const float *invstd, const float *gamma, int32_t relu, float *dx, float *dresidual,
-                      float *dgamma, float *dbeta, void *workspace, int64_t workspace_bytes, void *stream);
-int mink_bn_apply_from_partials(const float *x, int64_t n, int32_t C, const double *partial, int32_t rows, float eps, float momentum,
-                                const float *gamma, const float *beta, const float *residual, int32_t relu, float *y, float *mean,
-                                float *invstd, float *running_mean, float *running_var, void *stream);
-
-/* ------------------------------------------------------------------ few-row layers: batch norm in one launch
- * Below mink_bn_small_rows() rows (1024; 0 when switched off with mink_bn_set_small(0)) a batch norm as three dependent launches
- * (column partials, finalize, apply: the reference's MinkowskiBatchNorm = nn.BatchNorm1d, co3d_3d/src/models/mink/modules/
- * common.py:22-24, resnet_block.py:53-69) is launch latency, not bytes.  Here a workgroup owns 16 channels and ALL rows:
- *   mink_conv_gather_gemm_slabs  mink_conv_gather_gemm that LEAVES a split launch's partial slabs in `workspace`
- *                                ([*slabs_out][n_out][cout]; *slabs_out == 1: y is complete) -- no bias
- *   mink_bn_small_fwd            y = sum of `nslab` slabs (nslab == 0: y as given) -> batch statistics (mean, invstd, running
- *                                statistics as mink_bn_stats) -> out = [relu](bn(y) [+ residual])
- *   mink_bn_small_bwd            mink_bn_bwd in one launch; nslab > 0: the incoming gradient is the sum of `nslab` slabs at
- *                                `dy` ([nslab][n][C]) plus `addend` ([n][C], optional: a residual branch's gradient),
- *                                written to dy_sum
- * C must be a multiple of 16.  Results are deterministic; the summation order differs from the three-launch form (last-bit
- * differences), which is why the module-by-module path, the yardstick of the bitwise tests, never takes these. */
-int32_t mink_bn_small_rows(void);
-int mink_bn_set_small(int32_t on);
-int mink_conv_gather_gemm_slabs(const float *x, int64_t n_in, int32_t ldx, int32_t cin, const float *w, int32_t w_transposed,
-                                int32_t flip_k, const int32_t *nbr, int64_t n_out, int32_t K, const int32_t *row_perm,
-                                int64_t n_virtual, float *y, int32_t ldy, int32_t cout, int32_t ksplit, float *workspace,
-                                int64_t workspace_bytes, int32_t *slabs_out, void *stream);
-int mink_bn_small_fwd(const float *slabs, int32_t nslab, int64_t n, int32_t C, float *y, float eps, float momentum,
-                      const float *gamma, const float *beta, const float *residual, int32_t relu, float *out, float *mean,
-                      float *invstd, float *running_mean, float *running_var, void *stream);
-int mink_bn_small_bwd(const float *dy, int32_t nslab, const float *addend, float *dy_sum, const float *x, const float *y, int64_t n, int32_t C,
-                      const float *mean, const float *invstd, const float *gamma, int32_t relu, float *dx, float *dresidual,
-                      float *dgamma, float *dbeta, void *stream);
-
-/* ------------------------------------------------------------------ the whole trunk as one call
+/* ------------------------------------------------------------------ the whole trunk as one call (csrc/trunk.hip)
  * Stem + every BasicBlock of a Mink-ResNet (the reference's ResNetBase.forward up to layer4:
  * co3d_3d/src/models/mink/resnet.py:107-161 `_make_layer`, :163-175 `forward`) in ONE host call per direction.
  * mink_net_forward / mink_net_backward sequence exactly what mink_stem_* and mink_block_* sequence (they call them),
@@ -1038,7 +1046,7 @@ int mink_net_forward(MinkNet *net, const MinkLevelMaps *levels, int32_t n_levels
 int mink_net_backward(MinkNet *net, const MinkLevelMaps *levels, int32_t n_levels, float *arena, int64_t arena_floats,
                       const float *g_out, float *grad_arena, int64_t grad_floats, const MinkExec *ex, void *const *done_events);
 
-/* ------------------------------------------------------------------ bf16 storage of the full-resolution stage
+/* ------------------------------------------------------------------ bf16 storage of the full-resolution stage (csrc/stem16.hip, csrc/batchnorm.hip, csrc/conv_wgrad.hip)
  * BASELINE config "bf16 mixed precision", storage form: the network input and the stem convolution's output -- three
  * quarters of the activation bytes of a Mink-ResNet step -- are kept in HBM as bf16; the pooled level and everything
  * below stay fp32.  Arithmetic is that of mink_conv_set_math(1) (bf16 operands, fp32 accumulation); the batch-norm
@@ -1066,7 +1074,7 @@ int mink_conv_wgrad_bn_relu_pool_b16(const void *xb, int64_t n_in, int32_t cin, 
                                      const int32_t *nbr, int64_t n_out, int32_t K, float *dw, void *workspace,
                                      int64_t workspace_bytes, void *stream);
 
-/* ------------------------------------------------------------------ streams confined to a CU subset
+/* ------------------------------------------------------------------ streams confined to a CU subset (csrc/trunk.hip)
  * A HIP stream whose kernels may only run on compute units [first_cu, first_cu + n_cus) of the device's
  * `total_cus` (hipExtStreamCreateWithCUMask; on a multi-XCD part consecutive mask bits go round the XCDs, so a
  * contiguous range is spread evenly over them).  The training step keeps several streams busy at once -- the
@@ -1077,7 +1085,7 @@ int mink_conv_wgrad_bn_relu_pool_b16(const void *xb, int64_t n_in, int32_t cin, 
 int mink_stream_create_cu_subset(int32_t first_cu, int32_t n_cus, int32_t total_cus, void **stream_out);
 int mink_stream_destroy(void *stream);
 
-/* ------------------------------------------------------------------ kernel timing (measurement only)
+/* ------------------------------------------------------------------ kernel timing (measurement only) (csrc/conv.hip)
  * bench.py reports the roofline of the dominant convolution kernel from HIP events recorded on the stream each
  * kernel is launched on.  mode 0: off; 1: every convolution launch; 2: only launches matching (kind, K, cin, cout).
  * kind: 0 forward, 1 data gradient, 2 weight gradient, -1 (mode 2) any of them -- the passes of one layer.  mink_conv_timing_fetch synchronises the recorded events,

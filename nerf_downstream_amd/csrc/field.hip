@@ -11,12 +11,16 @@
 //                      group of the CONCATENATED row, so ME.cat(y1.slice(x), ..., y4.slice(x)) writes every output row once
 //                      and no [N, C_s] intermediate exists.  idx < 0 (or past the source) -> zeros in that source's columns.
 //                      Its backward is mink_segment_sum per source over a column slice of dy (row pitch).
+//   segment_mean     : mink_segment_mean (TensorField.sparse()) and mink_segment_sum (the backward of SparseTensor.slice()
+//                      and of the gather above): one dword lane per output element, members added in input-row order.
+//                      Outside the anonymous namespace, beside the other kernels of namespace mink proper.
 //   segment_mean_bwd : dx[members[j]][:] = dy[u][:] / (seg[u + 1] - seg[u]) for j in segment u -- the backward of
 //                      mink_segment_mean.  One lane per (member, column group): the segment of member j is found by a binary
 //                      search in seg, so a voxel holding thousands of points costs no more than one holding one, and every
 //                      input row is written exactly once.
 #include <algorithm>
 
+#include "ew_common.h"
 #include "rowpass.h"
 
 namespace mink {
@@ -113,6 +117,23 @@ __global__ __launch_bounds__(FB) void segment_mean_bwd_kernel(const float *__res
 }
 
 }  // namespace
+
+// MEAN: TensorField.sparse(); !MEAN (the plain sum, same member order): the backward of SparseTensor.slice()
+template <bool MEAN>
+__global__ __launch_bounds__(EB) void segment_mean_kernel(const float *__restrict__ x, int ldx, int C,
+                                                          const int *__restrict__ members,
+                                                          const int *__restrict__ seg, int64_t n_out,
+                                                          float *__restrict__ y) {
+  const int64_t idx = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (idx >= n_out * C) return;
+  const int64_t u = idx / C;
+  const int c = (int)(idx - u * C);
+  const int beg = seg[u], end = seg[u + 1];
+  float s = 0.f;
+  for (int j = beg; j < end; ++j) s += x[(int64_t)members[j] * ldx + c];  // input-row order
+  y[idx] = MEAN ? s / (float)(end - beg) : s;
+}
+
 }  // namespace mink
 
 using namespace mink;
@@ -178,6 +199,28 @@ int mink_segment_mean_bwd(const float *dy, int32_t ldy, int32_t C, const int32_t
   const dim3 grid(flat_grid(n_members * (vec ? C / 4 : C), FB, 1 << 16));
   if (vec) segment_mean_bwd_kernel<4><<<grid, FB, 0, st>>>(dy, ldy, C, members, seg, n_out, n_members, n_in, dx, lddx);
   else segment_mean_bwd_kernel<1><<<grid, FB, 0, st>>>(dy, ldy, C, members, seg, n_out, n_members, n_in, dx, lddx);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_segment_mean(const float *x, int32_t ldx, int32_t C, const int32_t *members, const int32_t *seg,
+                      int64_t n_out, float *y, void *stream) {
+  MINK_REQUIRE(C >= 1 && ldx >= C && n_out >= 0, "segment_mean: bad shape");
+  if (n_out == 0) return MINK_OK;
+  MINK_REQUIRE(x && members && seg && y, "segment_mean: NULL pointer");
+  segment_mean_kernel<true><<<dim3((unsigned)cdiv(n_out * C, EB)), EB, 0, (hipStream_t)stream>>>(x, ldx, C, members, seg,
+                                                                                                n_out, y);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_segment_sum(const float *x, int32_t ldx, int32_t C, const int32_t *members, const int32_t *seg,
+                     int64_t n_out, float *y, void *stream) {
+  MINK_REQUIRE(C >= 1 && ldx >= C && n_out >= 0, "segment_sum: bad shape");
+  if (n_out == 0) return MINK_OK;
+  MINK_REQUIRE(x && members && seg && y, "segment_sum: NULL pointer");
+  segment_mean_kernel<false><<<dim3((unsigned)cdiv(n_out * C, EB)), EB, 0, (hipStream_t)stream>>>(x, ldx, C, members, seg,
+                                                                                                 n_out, y);
   MINK_CHECK_LAUNCH();
   return MINK_OK;
 }

@@ -1,6 +1,6 @@
 // Per-sample and per-row normalisation of the feature matrix on gfx950: MinkowskiInstanceNorm (statistics over the rows of
 // one batch sample, per channel) and MinkowskiLayerNorm (statistics over the channels of one row), each with the optional
-// residual add and ReLU of the batch-norm kernels (elementwise.hip) fused into the same pass.
+// residual add and ReLU of the batch-norm kernels (batchnorm.hip) fused into the same pass.
 //
 // Both are bandwidth-bound passes over x[n][C]; the figure of merit is bytes moved per element against the minimum:
 //   instance norm forward : read x (statistics), read x + write y (apply)             12 B / element  (+4 residual)

@@ -1,9 +1,13 @@
 // The sparse pooling family on gfx950: local average / sum / max pooling over a neighbour table whose windows may overlap
 // (ME.MinkowskiAvgPooling, MinkowskiSumPooling beyond kernel_size == stride, MinkowskiMaxPooling) and the segmented global
-// max / sum pooling over the batch offsets (ME.MinkowskiGlobalMaxPooling, MinkowskiGlobalSumPooling).  The non-overlapping
-// sum pooling of the ResNet stem, its fused forms and the global average stay in elementwise.hip, untouched.
+// max / sum pooling over the batch offsets (ME.MinkowskiGlobalMaxPooling, MinkowskiGlobalSumPooling) -- the row-pass
+// family, in the anonymous namespace -- and, behind it in namespace mink proper, the three pools of the classification
+// networks: the non-overlapping sum pooling of the ResNet stem (mink_pool_sum_*), the max pooling of the dense 2-D
+// baseline (mink_pool_max_*) and the global average (mink_global_avg_*).  Those three take C % 4 == 0 and 16-byte aligned
+// pointers only (16-byte lanes, ld4 / st4 of ew_common.h) and have no dword form.  The stem's sum pool fused with its
+// batch norm and ReLU is in batchnorm.hip.
 //
-// All of them are bandwidth-bound row passes over x[n][C] (row pitch ldx >= C): a thread owns one column group of one row,
+// The row-pass family: all of them are bandwidth-bound row passes over x[n][C] (row pitch ldx >= C): a thread owns one column group of one row,
 // 16 bytes wide when C % 4 == 0 and every pointer is 16-byte aligned (and ldx % 4 == 0), one dword otherwise (C = 1, 3, 70).
 //
 // Local pools.  nbr[n_out][K] holds the input row of output o at kernel offset k, or -1.  Forward walks k = 0 .. K-1 in
@@ -29,6 +33,7 @@
 // Determinism: rows -> threads -> partials -> results is a fixed assignment in a fixed order: two runs are bitwise equal.
 #include <algorithm>
 
+#include "ew_common.h"
 #include "rowpass.h"
 
 namespace mink {
@@ -309,6 +314,124 @@ __global__ __launch_bounds__(PB) void gpool_bwd_kernel(const float *__restrict__
 }
 
 }  // namespace
+
+// ------------------------------------------------------------------------- pooling
+__global__ __launch_bounds__(EB) void pool_sum_fwd_kernel(const float *__restrict__ x, int ldx, int C4,
+                                                          const int *__restrict__ nbr, int64_t n_out, int K,
+                                                          float *__restrict__ y) {
+  const int64_t idx = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (idx >= n_out * C4) return;
+  const int64_t o = idx / C4;
+  const int c = (int)(idx - o * C4) * 4;
+  float4 s = make_float4(0, 0, 0, 0);
+  for (int k = 0; k < K; ++k) {
+    const int i = nbr[o * K + k];
+    if (i >= 0) {
+      const float4 v = ld4(x + (int64_t)i * ldx + c);
+      s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
+    }
+  }
+  st4(y + o * (int64_t)(4 * C4) + c, s);
+}
+
+__global__ __launch_bounds__(EB) void pool_sum_bwd_kernel(const float *__restrict__ dy, int C4,
+                                                          const int *__restrict__ in2out, int64_t n_in,
+                                                          float *__restrict__ dx) {
+  const int64_t idx = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (idx >= n_in * C4) return;
+  const int64_t i = idx / C4;
+  const int c = (int)(idx - i * C4) * 4;
+  st4(dx + i * (int64_t)(4 * C4) + c, ld4(dy + (int64_t)in2out[i] * (4 * C4) + c));
+}
+
+// Max pooling over a neighbour table (overlapping windows allowed: the dense 2-D baseline's 3x3 stride-2 pooling).
+// arg[o][c] = input row holding the maximum (the first one in offset order, as torch's window scan picks it).
+__global__ __launch_bounds__(EB) void pool_max_fwd_kernel(const float *__restrict__ x, int C4, const int *__restrict__ nbr,
+                                                          int64_t n_out, int K, float *__restrict__ y, int *__restrict__ arg) {
+  const int64_t idx = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (idx >= n_out * C4) return;
+  const int64_t o = idx / C4;
+  const int c = (int)(idx - o * C4) * 4;
+  float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+  int4 a = make_int4(-1, -1, -1, -1);
+  for (int k = 0; k < K; ++k) {
+    const int i = nbr[o * K + k];
+    if (i >= 0) {
+      const float4 v = ld4(x + (int64_t)i * (4 * C4) + c);
+      if (a.x < 0 || max_replaces(v.x, m.x)) m.x = v.x, a.x = i;  // (torch's rule: the first NaN of the window wins, else
+      if (a.y < 0 || max_replaces(v.y, m.y)) m.y = v.y, a.y = i;  //  the first of the largest numbers)
+      if (a.z < 0 || max_replaces(v.z, m.z)) m.z = v.z, a.z = i;
+      if (a.w < 0 || max_replaces(v.w, m.w)) m.w = v.w, a.w = i;
+    }
+  }
+  st4(y + o * (int64_t)(4 * C4) + c, m);
+  *reinterpret_cast<int4 *>(arg + o * (int64_t)(4 * C4) + c) = a;
+}
+
+// dx[i][c] = sum of dy[o][c] over the windows o that contain i and chose it (gathered through the transposed table:
+// no atomics, one owner per element)
+__global__ __launch_bounds__(EB) void pool_max_bwd_kernel(const float *__restrict__ dy, const int *__restrict__ arg, int C4,
+                                                          const int *__restrict__ nbr_t, int64_t n_in, int K,
+                                                          float *__restrict__ dx) {
+  const int64_t idx = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (idx >= n_in * C4) return;
+  const int64_t i = idx / C4;
+  const int c = (int)(idx - i * C4) * 4;
+  float4 s = make_float4(0, 0, 0, 0);
+  for (int k = 0; k < K; ++k) {
+    const int o = nbr_t[i * K + k];
+    if (o >= 0) {
+      const int4 a = *reinterpret_cast<const int4 *>(arg + (int64_t)o * (4 * C4) + c);
+      const float4 g = ld4(dy + (int64_t)o * (4 * C4) + c);
+      s.x += a.x == (int)i ? g.x : 0.f, s.y += a.y == (int)i ? g.y : 0.f;
+      s.z += a.z == (int)i ? g.z : 0.f, s.w += a.w == (int)i ? g.w : 0.f;
+    }
+  }
+  st4(dx + i * (int64_t)(4 * C4) + c, s);
+}
+
+// one workgroup per (batch, 64-channel slab): 16 float4 columns x 16 row lanes
+__global__ __launch_bounds__(EB) void global_avg_fwd_kernel(const float *__restrict__ x, int C,
+                                                            const int *__restrict__ boff, float *__restrict__ y) {
+  __shared__ float4 s_red[EB];
+  const int b = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 15) * 4, rl = threadIdx.x >> 4;
+  const int beg = boff[b], end = boff[b + 1];
+  float4 s = make_float4(0, 0, 0, 0);
+  if (c < C)
+    for (int r = beg + rl; r < end; r += 16) {
+      const float4 v = ld4(x + (int64_t)r * C + c);
+      s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
+    }
+  s_red[threadIdx.x] = s;
+  __syncthreads();
+  if (rl == 0 && c < C) {
+    for (int r = 1; r < 16; ++r) {
+      const float4 v = s_red[r * 16 + (threadIdx.x & 15)];
+      s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
+    }
+    const float inv = end > beg ? 1.f / (float)(end - beg) : 0.f;
+    st4(y + (int64_t)b * C + c, make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv));
+  }
+}
+
+__global__ __launch_bounds__(EB) void global_avg_bwd_kernel(const float *__restrict__ dy, int C4,
+                                                            const int *__restrict__ boff, int B, int64_t n,
+                                                            float *__restrict__ dx) {
+  const int64_t idx = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (idx >= n * C4) return;
+  const int64_t i = idx / C4;
+  const int c = (int)(idx - i * C4) * 4;
+  int lo = 0, hi = B;  // largest b with boff[b] <= i
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (boff[mid] <= i) lo = mid;
+    else hi = mid;
+  }
+  const float inv = 1.f / (float)(boff[lo + 1] - boff[lo]);
+  const float4 g = ld4(dy + (int64_t)lo * (4 * C4) + c);
+  st4(dx + i * (int64_t)(4 * C4) + c, make_float4(g.x * inv, g.y * inv, g.z * inv, g.w * inv));
+}
+
 }  // namespace mink
 
 using namespace mink;
@@ -454,6 +577,85 @@ int mink_global_sum_bwd(const float *dy, int64_t n, int32_t C, const int32_t *ba
   const bool vec = (C & 3) == 0 && aligned16(dy) && aligned16(dx);
   if (vec) gpool_bwd_kernel<4, false><<<dim3(flat_grid(n * (C / 4), PB, 1 << 16)), PB, 0, st>>>(dy, nullptr, n, C, batch_offsets, B, dx);
   else gpool_bwd_kernel<1, false><<<dim3(flat_grid(n * C, PB, 1 << 16)), PB, 0, st>>>(dy, nullptr, n, C, batch_offsets, B, dx);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_pool_sum_fwd(const float *x, int32_t ldx, int32_t C, const int32_t *nbr, int64_t n_out, int32_t K, float *y,
+                      void *stream) {
+  REQ_C4(C, "pool_sum_fwd");
+  MINK_REQUIRE(n_out >= 0 && K >= 1 && (ldx & 3) == 0 && ldx >= C, "pool_sum_fwd: bad shape");
+  if (n_out == 0) return MINK_OK;
+  MINK_REQUIRE(x && nbr && y, "pool_sum_fwd: NULL pointer");
+  REQ_A16(x, "pool_sum_fwd");
+  REQ_A16(y, "pool_sum_fwd");
+  pool_sum_fwd_kernel<<<dim3((unsigned)cdiv(n_out * (C >> 2), EB)), EB, 0, (hipStream_t)stream>>>(x, ldx, C >> 2, nbr,
+                                                                                                 n_out, K, y);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_pool_sum_bwd(const float *dy, int32_t C, const int32_t *in2out, int64_t n_in, float *dx, void *stream) {
+  REQ_C4(C, "pool_sum_bwd");
+  MINK_REQUIRE(n_in >= 0, "pool_sum_bwd: bad n");
+  if (n_in == 0) return MINK_OK;
+  MINK_REQUIRE(dy && in2out && dx, "pool_sum_bwd: NULL pointer");
+  REQ_A16(dy, "pool_sum_bwd");
+  REQ_A16(dx, "pool_sum_bwd");
+  pool_sum_bwd_kernel<<<dim3((unsigned)cdiv(n_in * (C >> 2), EB)), EB, 0, (hipStream_t)stream>>>(dy, C >> 2, in2out,
+                                                                                                n_in, dx);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_pool_max_fwd(const float *x, int32_t C, const int32_t *nbr, int64_t n_out, int32_t K, float *y, int32_t *arg,
+                      void *stream) {
+  REQ_C4(C, "pool_max_fwd");
+  MINK_REQUIRE(n_out >= 0 && K >= 1, "pool_max_fwd: bad shape");
+  if (n_out == 0) return MINK_OK;
+  MINK_REQUIRE(x && nbr && y && arg, "pool_max_fwd: NULL pointer");
+  REQ_A16(x, "pool_max_fwd");
+  REQ_A16(y, "pool_max_fwd");
+  REQ_A16(arg, "pool_max_fwd");
+  pool_max_fwd_kernel<<<dim3((unsigned)cdiv(n_out * (C >> 2), EB)), EB, 0, (hipStream_t)stream>>>(x, C >> 2, nbr, n_out, K, y, arg);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_pool_max_bwd(const float *dy, const int32_t *arg, int32_t C, const int32_t *nbr_t, int64_t n_in, int32_t K, float *dx,
+                      void *stream) {
+  REQ_C4(C, "pool_max_bwd");
+  MINK_REQUIRE(n_in >= 0 && K >= 1, "pool_max_bwd: bad shape");
+  if (n_in == 0) return MINK_OK;
+  MINK_REQUIRE(dy && arg && nbr_t && dx, "pool_max_bwd: NULL pointer");
+  REQ_A16(dy, "pool_max_bwd");
+  REQ_A16(dx, "pool_max_bwd");
+  REQ_A16(arg, "pool_max_bwd");
+  pool_max_bwd_kernel<<<dim3((unsigned)cdiv(n_in * (C >> 2), EB)), EB, 0, (hipStream_t)stream>>>(dy, arg, C >> 2, nbr_t, n_in, K, dx);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_global_avg_fwd(const float *x, int32_t C, const int32_t *batch_offsets, int32_t B, float *y, void *stream) {
+  REQ_C4(C, "global_avg_fwd");
+  MINK_REQUIRE(B >= 1 && x && batch_offsets && y, "global_avg_fwd: bad arguments");
+  REQ_A16(x, "global_avg_fwd");
+  REQ_A16(y, "global_avg_fwd");
+  global_avg_fwd_kernel<<<dim3((unsigned)B, (unsigned)cdiv(C, 64)), EB, 0, (hipStream_t)stream>>>(x, C, batch_offsets, y);
+  MINK_CHECK_LAUNCH();
+  return MINK_OK;
+}
+
+int mink_global_avg_bwd(const float *dy, int32_t C, const int32_t *batch_offsets, int32_t B, int64_t n, float *dx,
+                        void *stream) {
+  REQ_C4(C, "global_avg_bwd");
+  MINK_REQUIRE(B >= 1 && n >= 0, "global_avg_bwd: bad arguments");
+  if (n == 0) return MINK_OK;
+  MINK_REQUIRE(dy && batch_offsets && dx, "global_avg_bwd: NULL pointer");
+  REQ_A16(dy, "global_avg_bwd");
+  REQ_A16(dx, "global_avg_bwd");
+  global_avg_bwd_kernel<<<dim3((unsigned)cdiv(n * (C >> 2), EB)), EB, 0, (hipStream_t)stream>>>(dy, C >> 2,
+                                                                                               batch_offsets, B, n, dx);
   MINK_CHECK_LAUNCH();
   return MINK_OK;
 }

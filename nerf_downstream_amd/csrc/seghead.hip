@@ -1,6 +1,6 @@
 // Segmentation tail: weighted / ignore-label softmax cross entropy over per-point logits with the prediction, the
 // confusion matrix and the label counts out of the same pass (mink_seg_ce_forward / _backward), and the row gather of
-// SparseTensor.slice() (mink_rows_gather; its backward, mink_segment_sum, sits beside mink_segment_mean in elementwise.hip).
+// SparseTensor.slice() (mink_rows_gather; its backward, mink_segment_sum, sits beside mink_segment_mean in field.hip).
 //
 // Streaming kernels: every logit is read once per direction.  A row of C = 20 / 21 floats (80 / 84 bytes) is not what a
 // lane loads well, so a workgroup loads a contiguous tile of rows cooperatively (16-byte loads when the matrix is dense

@@ -301,7 +301,7 @@ def _side_stream(device):
 
 def set_bn_small(on=True):
     """Few-row layers of the native trunk: the one-launch batch norm + split-K sum (mink_bn_small_fwd / _bwd; csrc/
-    elementwise.hip).  Off: the trunk sequences exactly the kernels of the module-by-module path (the bitwise tests)."""
+    batchnorm.hip).  Off: the trunk sequences exactly the kernels of the module-by-module path (the bitwise tests)."""
     return bool(lib().mink_bn_set_small(1 if on else 0))
 
 

@@ -137,7 +137,7 @@ def _stem_masks_of_hip_run(out, model):
     """The stem ReLU's branch decisions as the HIP backward kernels take them.  The trunk keeps only the POOLED sum of the
     stem's ReLU output, so its backward kernels recompute z = gamma * xhat + beta from the kept convolution output y and
     the batch's (mean, 1 / std) -- and the two kernels that do so round xhat differently (both are valid fp32):
-      * gamma / beta gradients (csrc/elementwise.hip, colreduce / bn_relu_pool_bwd_kernel; also the forward's own
+      * gamma / beta gradients (csrc/batchnorm.hip, colreduce / bn_relu_pool_bwd_kernel; also the forward's own
         decision):                      xhat = fl(fl(y - mean) * invstd),        z = fma(xhat, gamma, beta)
       * the weight gradient (csrc/conv_wgrad.hip, wgrad_stream_kernel<.., FUSE>): xhat = fma(y, invstd, fl(-mean * invstd)), z = fma(xhat, gamma, beta)
     Both are reproduced here in exact fp32 arithmetic on the CPU (an fma through float64: the product of two floats is exact

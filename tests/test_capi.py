@@ -310,6 +310,28 @@ def test_whole_header_is_read():
     assert _lib.constants("MINK_AUG_")["a"] == 9 and _lib.constants("MINK_AUG_")["A"] == 0
 
 
+def test_header_sections_name_the_defining_file():
+    """Text only: every prototype of mink_hip.h sits under a `/* ---- title (csrc/a.hip, csrc/b.hip)` line, and one of the files
+    that title names defines it -- the entry-point name followed by `(` on an unindented line (a call is indented)."""
+    text = open(os.path.join(ROOT, "include", "mink_hip.h")).read()
+    titles = [(m.start(), m.group(1).strip(), re.findall(r"\bcsrc/\w+\.hip\b", m.group(1)))
+              for m in re.finditer(r"^/\* -{4,}([^\n]*)", text, flags=re.M)]
+    code = re.sub(r"/\*.*?\*/", lambda m: " " * len(m.group(0)), text, flags=re.S)  # (offsets kept)
+    protos = [(m.start(), m.group(1)) for m in re.finditer(r"\b(mink_[a-z0-9_]+)\s*\(", code)]
+    assert len(titles) >= 25 and sorted({n for _, n in protos}) == _declared()
+    sources = {}
+    for pos, name in protos:
+        above = [t for t in titles if t[0] < pos]
+        assert above, f"{name} is declared above the first section title"
+        _, title, files = above[-1]
+        assert files, f"{name}: its section {title!r} names no csrc file"
+        for f in files:
+            if f not in sources:
+                sources[f] = open(os.path.join(ROOT, "nerf_downstream_amd", f)).read()
+        defined = [f for f in files if re.search(rf"^[A-Za-z_][\w \*]*?\b{name}\(", sources[f], flags=re.M)]
+        assert defined, f"{name} is declared under {title!r} but none of {files} defines it"
+
+
 def test_library_of_another_abi_is_refused(monkeypatch):
     """lib() on a fresh module state, over a handle whose mink_abi_version answers 3: MinkHipError naming both numbers."""
     from nerf_downstream_amd import _lib

@@ -624,7 +624,7 @@ def _synthetic_table(m, K, n_in, seed, unnamed):
 
 @pytest.mark.parametrize("value", VALUES)
 def test_table_max_and_sum_of_the_stem_and_dense_path(value):
-    """mink_pool_max_fwd / _bwd (the table max of elementwise.hip) and mink_pool_sum_fwd on a synthetic table with
+    """mink_pool_max_fwd / _bwd (the table max of pool.hip) and mink_pool_sum_fwd on a synthetic table with
     overlapping windows, empty entries and one input row that no entry names."""
     from nerf_downstream_amd.minkowski import functional as Fn
 
