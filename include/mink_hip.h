@@ -1304,6 +1304,37 @@ int mink_attn_bwd(const float *qkv, int32_t ldq, const float *out, int32_t ldo, 
                   int64_t B, int32_t N, int32_t H, int32_t D, float scale, float *dqkv, int32_t lddq, void *workspace,
                   int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ grouped convolution (csrc/gconv.hip)
+ * The 3x3 layers of the ResNeXt networks of the 2-D comparison (torchvision's Bottleneck with groups = 32): a convolution over
+ * a neighbour table whose G groups do not mix.  Rows are [n][ld] fp32; group g owns the input columns g cg_in .. (g + 1) cg_in and
+ * the output columns g cg_out .. (g + 1) cg_out.
+ *
+ *     nbr[n_out][K]  entries -1 ("outside") or in [0, n_in), as for mink_conv_gather_gemm; 1 <= K <= MINK_GCONV_MAX_K
+ *     w  [K][G][cg_in][cg_out]                                   (the packed layout; also the layout of dw)
+ *     mink_gconv_fwd    y[r][g cg_out + o] = sum_k sum_c x[nbr[r][k]][g cg_in + c] * w[k][g][c][o]
+ *     mink_gconv_wgrad  dw[k][g][c][o]     = sum_r x[nbr[r][k]][g cg_in + c] * dy[r][g cg_out + o]
+ *
+ * w_transposed reads `w` as [K][G][cg_out][cg_in] and flip_k (bit 0) uses offset K-1-k: with both, and cg_in / cg_out exchanged,
+ * the same entry point is the data gradient through the forward weights, with the meaning the flags have in
+ * mink_conv_gather_gemm -- stride 1 through the forward table with flip_k, stride 2 through the transposed table.
+ *
+ * fp32 in, fp32 accumulate, fp32 out in EVERY mink_conv_set_math mode: the grouped layers do not follow bf16 math.  No atomics,
+ * every sum in a fixed order (the weight gradient is split over row blocks whose partials are added in ascending order): two
+ * calls on the same inputs give the same bits.  A table entry of -1 contributes nothing: the vector-FMA kernels skip it, the
+ * matrix-core kernels (cg_in == cg_out in {16, 32, 64}) feed the row as zeros -- in the weight gradient on both sides, so a NaN of
+ * dy stays out of the offsets its row does not reach; non-finite WEIGHTS reach every row of their group there.  Every logical
+ * output element is written and nothing else: pad columns beyond G cg_out keep their bits, pad columns of the inputs are not read.
+ * Any G, cg_in, cg_out >= 1 with K G cg_in cg_out < 2^31, any pitch >= the logical width, pointers 4-byte aligned (16-byte
+ * accesses when x and y are 16-byte aligned and both pitches are multiples of 4); n_in, n_out < 2^31.  The workspace is 8-byte
+ * aligned and of at least mink_gconv_wgrad_workspace_bytes() bytes.  Anything else is MINK_EINVAL before any launch.  n_out == 0
+ * succeeds without a launch (mink_gconv_wgrad then sets dw to zero). */
+#define MINK_GCONV_MAX_K 27
+int mink_gconv_fwd(const float *x, int64_t n_in, int32_t ldx, const float *w, int32_t w_transposed, int32_t flip_k, const int32_t *nbr,
+                   int64_t n_out, int32_t K, int32_t G, int32_t cg_in, int32_t cg_out, float *y, int32_t ldy, void *stream);
+int64_t mink_gconv_wgrad_workspace_bytes(int64_t n_out, int32_t K, int32_t G, int32_t cg_in, int32_t cg_out);
+int mink_gconv_wgrad(const float *x, int64_t n_in, int32_t ldx, const float *dy, int32_t ldy, const int32_t *nbr, int64_t n_out, int32_t K,
+                     int32_t G, int32_t cg_in, int32_t cg_out, float *dw, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

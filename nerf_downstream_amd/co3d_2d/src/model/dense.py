@@ -8,7 +8,8 @@ outside the image, built once per (shape, kernel, stride, padding) and cached, s
 So the 3x3 / 1x1 convolutions, batch norm (+ fused ReLU / residual add) and the global average pooling run in the
 hand-written gfx950 kernels of libmink_hip.so (`mink_conv_gather_gemm` / `mink_conv_wgrad`: LDS-staged tiles, fp32 or
 bf16 MFMA); the one new kernel is the overlapping max pooling (`mink_pool_max_*`).  A kernel volume above 27 (the 7x7
-stem) is applied as two offset groups whose outputs are added.
+stem) is applied as two offset groups whose outputs are added.  `Conv2d(groups > 1)` (the 3x3 layers of ResNeXt) runs in
+csrc/gconv.hip (`mink_gconv_fwd` / `mink_gconv_wgrad`), fp32 in every math mode.
 
 Parameter names and layouts are torch's (`weight` [Cout, Cin, kh, kw], `running_mean`, ...), so torchvision ResNet
 checkpoints load unchanged (reference co3d_2d/src/model/models.py:18-23 builds torchvision's resnet18)."""
@@ -77,16 +78,29 @@ def _conv_tables(grid, k, stride, pad, device):
 class Conv2d(nn.Module):
     """torch.nn.Conv2d(bias=False) semantics on the row layout.  `forward(x, grid)` -> (y, out_grid)."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=False):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=False, groups=1):
         super().__init__()
         assert not bias, "the ResNet convolutions carry no bias"
+        if groups < 1 or in_channels % groups or out_channels % groups:
+            raise ValueError(f"Conv2d: in_channels={in_channels} and out_channels={out_channels} must be multiples of groups={groups}")
+        if groups > 1 and kernel_size * kernel_size > 27:
+            raise ValueError(f"Conv2d: a grouped {kernel_size} x {kernel_size} kernel has more than the 27 offsets of one launch")
         self.in_channels, self.out_channels, self.k, self.stride, self.padding = in_channels, out_channels, kernel_size, stride, padding
-        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size))
+        self.groups = groups
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels // groups, kernel_size, kernel_size))
         nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")  # torchvision's ResNet init
 
     def forward(self, x, grid, bn_stats=False):
         out_grid, nbr, nbr_t, perm = _conv_tables(grid, self.k, self.stride, self.padding, x.device)
         K = self.k * self.k
+        if self.groups > 1:
+            # torch's [G * co, ci, ky, kx] -> the packed [ky * k + kx][G][ci][co] of csrc/gconv.hip (autograd repacks the gradient);
+            # no statistics epilogue: the batch norm that follows computes its own
+            G, ci, co = self.groups, self.in_channels // self.groups, self.out_channels // self.groups
+            w = self.weight.view(G, co, ci, self.k, self.k).permute(3, 4, 0, 2, 1).reshape(K, G, ci, co)
+            same_map = self.stride == 1 and self.k % 2 == 1 and 2 * self.padding == self.k - 1
+            tf = lambda transposed, t=(nbr, nbr_t): t  # noqa: E731
+            return Fn.GroupedConvolutionFunction.apply(x, w.contiguous(), tf, same_map), out_grid, None
         w = self.weight.permute(2, 3, 1, 0).reshape(K, self.in_channels, self.out_channels)  # [ky*k+kx][cin][cout]
         same_map = self.stride == 1 and self.k % 2 == 1 and 2 * self.padding == self.k - 1
         holder = [] if bn_stats else None

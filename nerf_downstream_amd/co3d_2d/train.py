@@ -4,9 +4,12 @@ gin names (`run.*`, `LitModel.*`, `DataModule.*`, `ResNetBased.*`, `ViTBased.*`)
 as a plain loop instead of a Lightning Trainer.  `run.precision = 16` runs the convolutions on the bf16 matrix cores
 (fp32 accumulate and storage); every convolution, batch norm and pooling is a hand-written gfx950 kernel
 (src/model/dense.py).  The Vision Transformers (configs/vit*.gin, src/model/vit.py) run in fp32 only: `run.precision = 16` with
-one of them is refused.
+one of them is refused.  The grouped 3x3 layers of the ResNeXt networks (configs/resnext*.gin, csrc/gconv.hip) are fp32 in, fp32
+accumulate and fp32 out whatever `run.precision` says: with 16 the 1x1 layers around them run on the bf16 matrix cores and the
+grouped layers do not follow.
 
-    python -m nerf_downstream_amd.co3d_2d.train --ginc nerf_downstream_amd/co3d_2d/configs/resnet18.gin"""
+    python -m nerf_downstream_amd.co3d_2d.train --ginc nerf_downstream_amd/co3d_2d/configs/resnet18.gin
+    python -m nerf_downstream_amd.co3d_2d.train --ginc nerf_downstream_amd/co3d_2d/configs/resnext50.gin"""
 import argparse
 import logging
 import os
