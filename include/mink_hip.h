@@ -898,6 +898,93 @@ int mink_lidar_decode_scans(const float *scan, const uint32_t *raw_labels, int64
 int mink_lidar_finish_rows(float *coords, int64_t n, const int32_t *n_rows, float voxel_size, float *feats, int64_t ldf, int32_t c0,
                            void *stream);
 
+/* ------------------------------------------------------------------ images: AugMix chains and the 2-D recipe (csrc/image.hip)
+ * What the reference's 2-D loader does to a decoded frame (co3d_2d/src/data/loader.py:100-107, augmix.py:184-215,
+ * transforms.py), for a whole batch, with Pillow's arithmetic: every 8-bit result below is the integer Pillow computes, the
+ * float result follows torch's float32 operations one by one.  The host decodes and draws; the device applies.
+ *
+ * A batch: `packed`, the uint8 HWC RGB images of the B samples one after the other (any sizes, any byte alignment);
+ * `offsets` [B+1] int64, the BYTE offset of every image in `packed` (offsets[0] = 0, offsets[b+1] - offsets[b] = 3 * w * h,
+ * offsets[B] = 3 * total_pixels); `sizes` [B][2] int32 = (w, h), w * h < 2^31; `programs` [B][MINK_IMG_PARAMS] double, all on the device.
+ * A sample whose offsets, sizes or boxes do not fit is not read: its chain buffers stay as they are and its output is NaN.
+ *
+ * The program row of a sample:
+ *     [WIDTH]              chains of this sample, 0 .. MINK_IMG_MAX_WIDTH and <= the call's `width` (0: evaluation, out = pre_0)
+ *     [M]                  m (a float32), out = (1 - m) * pre_0(x) + m * mix
+ *     [WS + i - 1]         ws_i (float32) of chain i = 1 .. WIDTH: mix = ((0 + ws_1 * pre_1) + ws_2 * pre_2) + ..., in that order
+ *     [BRANCH + k * BRANCH_STRIDE + ...]  branch k = 0 .. WIDTH; branch 0 is the untouched image, branch i >= 1 chain i:
+ *       B_DEPTH            ops of the chain, 0 .. MINK_IMG_MAX_DEPTH (ignored for branch 0)
+ *       B_OPS + r * OP_STRIDE = (kind, p0 .. p5) of round r: AUTOCONTRAST, EQUALIZE (no arguments; per-channel tables from the
+ *                          histogram), POSTERIZE (p0 = bits kept: v & ~(2^(8-bits) - 1)), SOLARIZE (p0 = t: v < t ? v : 255 - v),
+ *                          ROTATE, SHEAR_X/Y, TRANSLATE_X/Y (p0 .. p5 = the affine matrix a0 .. a5 the host built: output pixel
+ *                          (x, y) reads xin = a0 (x + .5) + a1 (y + .5) + a2, yin = a3 (x + .5) + a4 (y + .5) + a5, BILINEAR,
+ *                          zero outside [0, w) x [0, h), in double, truncated to 8 bits)
+ *       B_BOX              x0, y0, w, h of the crop, inside the image
+ *       B_TARGET           OW, OH: the crop is resized to OW x OH (BILINEAR, horizontal pass first, 8 bits after each pass, the
+ *                          taps clipped to the crop, coefficients of 22 fractional bits) ...
+ *       B_WINDOW           wx, wy: ... of which the S x S window at (wx, wy) is kept (RandomResizedCrop: OW = OH = S, window 0, 0;
+ *                          CenterCrop: shorter side S, the centred window)
+ *       B_ORDER            three slots, each a MINK_IMG_JIT_* or 0: the ColorJitter steps in the drawn order, uint8 to uint8
+ *       B_FACTORS          brightness, saturation, hue factor (read by the slots that name them)
+ *       B_FLIP             != 0: mirror the columns
+ *       B_RGB              r, g, b of the PCA lighting (float32), added after / 255; then (x - mean) / std of the CO3D statistics
+ *
+ * mink_img_workspace_bytes: the scratch of both calls for a batch of total_pixels pixels, B samples and at most `width` chains
+ * per sample (independent of S): histograms [B][width][3][256] int32, tables [B][width][3][256] uint8 and, per chain, two
+ * images of the whole batch, A and B.  Round 0 reads `packed` and writes A, round 1 reads A and writes B, round 2 reads B and
+ * writes A: mink_img_chain_buffer_offset(total_pixels, B, width, chain i >= 1, depth d >= 1) is the byte offset in the workspace
+ * of the batch of chain i after d ops (laid out like `packed`), -1 for arguments outside those ranges.
+ *
+ * mink_img_chain_round: round r = 0, 1, 2 of every chain of the batch, three launches (histograms of the chains whose op of this
+ * round needs one: LDS sub-histograms with equal bins of a wave merged before the atomic, integer sums only; the tables; one
+ * apply pass of 16-byte stores with scalar head and tail).  Chains with depth <= r are skipped.  Rounds run in order on one stream.
+ *
+ * mink_img_finish: out [B][3][S][S] float32, every element written once; one workgroup owns a tile of the output of one sample
+ * and walks branch 0 .. WIDTH in order, accumulating in registers (no atomics: two calls agree bit for bit).  `stages`, when
+ * not NULL, is uint8 [B][width + 1][S][S][3] and receives the 8-bit image of branch k <= WIDTH after the flip (further
+ * branches are not written).  No product of the float and double expressions above is fused with an addition. */
+enum {
+  MINK_IMG_MAX_WIDTH = 3,
+  MINK_IMG_MAX_DEPTH = 3,
+  MINK_IMG_OP_AUTOCONTRAST = 1,
+  MINK_IMG_OP_EQUALIZE = 2,
+  MINK_IMG_OP_POSTERIZE = 3,
+  MINK_IMG_OP_ROTATE = 4,
+  MINK_IMG_OP_SOLARIZE = 5,
+  MINK_IMG_OP_SHEAR_X = 6,
+  MINK_IMG_OP_SHEAR_Y = 7,
+  MINK_IMG_OP_TRANSLATE_X = 8,
+  MINK_IMG_OP_TRANSLATE_Y = 9,
+  MINK_IMG_JIT_BRIGHTNESS = 1,
+  MINK_IMG_JIT_SATURATION = 2,
+  MINK_IMG_JIT_HUE = 3,
+  MINK_IMG_WIDTH = 0,
+  MINK_IMG_M = 1,
+  MINK_IMG_WS = 2,
+  MINK_IMG_BRANCH = 5,
+  MINK_IMG_BRANCH_STRIDE = 40,
+  MINK_IMG_B_DEPTH = 0,
+  MINK_IMG_B_OPS = 1,
+  MINK_IMG_OP_STRIDE = 7,
+  MINK_IMG_B_BOX = 22,
+  MINK_IMG_B_TARGET = 26,
+  MINK_IMG_B_WINDOW = 28,
+  MINK_IMG_B_ORDER = 30,
+  MINK_IMG_B_FACTORS = 33,
+  MINK_IMG_B_FLIP = 36,
+  MINK_IMG_B_RGB = 37,
+  MINK_IMG_PARAMS = 165
+};
+
+int64_t mink_img_workspace_bytes(int64_t total_pixels, int32_t B, int32_t width, int32_t S);
+int64_t mink_img_chain_buffer_offset(int64_t total_pixels, int32_t B, int32_t width, int32_t chain, int32_t depth);
+int mink_img_chain_round(const uint8_t *packed, const int64_t *offsets, const int32_t *sizes, const double *programs,
+                         int64_t total_pixels, int32_t B, int32_t width, int32_t round, void *workspace, int64_t workspace_bytes,
+                         void *stream);
+int mink_img_finish(const uint8_t *packed, const int64_t *offsets, const int32_t *sizes, const double *programs,
+                    int64_t total_pixels, int32_t B, int32_t width, int32_t S, const void *workspace, int64_t workspace_bytes,
+                    float *out, uint8_t *stages, void *stream);
+
 /* ------------------------------------------------------------------ whole residual blocks (csrc/trunk.hip)
  * One call = the complete launch sequence of one stage of the reference network, so the host pays one FFI call per
  * block instead of one per kernel (a Mink-ResNet14 step is ~300 launches; issued one by one from a Python autograd

@@ -52,6 +52,10 @@ class LitModel(nn.Module):
         self.eval()
         preds, labels = [], []
         for batch in loader:
+            if "programs" in batch:  # frames from disk: the CenterCrop recipe runs on the GPU
+                from ..data.loader import images_to_device
+
+                batch = images_to_device(batch, device)
             preds.append(self.model(batch["images"].to(device)).float())
             labels.append(batch["labels"].to(device))
         self.train(was)

@@ -19,7 +19,7 @@ import torch
 
 from nerf_downstream_amd import gin_lite as gin
 from nerf_downstream_amd.safe_load import load_checkpoint_file
-from nerf_downstream_amd.co3d_2d.src.data.loader import DataModule
+from nerf_downstream_amd.co3d_2d.src.data.loader import DataModule, images_to_device
 from nerf_downstream_amd.co3d_2d.src.model.models import ViTBased
 from nerf_downstream_amd.co3d_2d.src.modules.classification import LitModel, lr_at
 
@@ -65,7 +65,7 @@ def run(ckpt_path, resume_training, seed, run_name="resnet18", num_gpus=1, log_e
             if done:
                 break
             for batch in train_loader:
-                batch = {k: v.to(dev, non_blocking=True) for k, v in batch.items()}
+                batch = images_to_device(batch, dev)  # (frames from disk: AugMix and the recipe run here, on the GPU)
                 for pg in opt.param_groups:
                     pg["lr"] = lr_at(step, model.lr, total)
                 opt.zero_grad(set_to_none=True)

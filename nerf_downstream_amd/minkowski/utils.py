@@ -496,6 +496,71 @@ def prepare_lidar_batch(batch, count_async=False):
     return c[:k], f[:k], labels[:k], src[:k]
 
 
+def image_batch_check(offsets, sizes, programs, n_bytes):
+    """Host check of an image batch before it goes to the device (`collate_images` hands these over as host arrays): offsets
+    int64 [B+1] in bytes, sizes int32 [B,2] = (w, h), programs float64 [B, MINK_IMG_PARAMS].  Returns (B, width of the widest
+    sample).  The kernels skip a sample that does not fit (its output is NaN); here the same thing raises."""
+    from .._lib import constants
+
+    I = constants("MINK_IMG_")
+    offsets, sizes, programs = np.asarray(offsets), np.asarray(sizes), np.asarray(programs)
+    B = sizes.shape[0]
+    if offsets.shape != (B + 1,) or sizes.shape != (B, 2) or programs.shape != (B, I["PARAMS"]):
+        raise ValueError(f"image batch: offsets {offsets.shape}, sizes {sizes.shape}, programs {programs.shape} for {B} images "
+                         f"([B+1], [B,2], [B,{I['PARAMS']}])")
+    if B == 0:
+        return 0, 0
+    nbytes = 3 * sizes[:, 0].astype(np.int64) * sizes[:, 1].astype(np.int64)
+    if (sizes < 1).any() or (nbytes > 3 * 0x7FFFFFFF).any() or offsets[0] != 0 or (np.diff(offsets) != nbytes).any() or offsets[-1] != n_bytes:
+        raise ValueError("image batch: offsets are not the running sum of 3 * w * h over the images of the packed buffer")
+    widths = programs[:, I["WIDTH"]]
+    if not ((widths >= 0) & (widths <= I["MAX_WIDTH"]) & (widths == np.floor(widths))).all():
+        raise ValueError(f"image batch: chain widths {widths} (whole numbers 0 .. {I['MAX_WIDTH']})")
+    return B, int(widths.max())
+
+
+def prepare_image_batch(packed, offsets, sizes, programs, size=224, stages=False):
+    """The input of a batch of decoded frames (co3d_2d/src/data/loader.py: `collate_images`), on the current stream: the three
+    rounds of the AugMix chains (`mink_img_chain_round`) and the fused crop / resize / ColorJitter / flip / PCA / Normalize / mix
+    tail (`mink_img_finish`).  packed: uint8 [n_bytes] on the device, the HWC RGB images one after the other; offsets int64 [B+1]
+    (bytes), sizes int32 [B,2] = (w, h) and programs float64 [B, MINK_IMG_PARAMS] (co3d_2d/src/data/transforms.py:
+    `compile_program`) as HOST arrays or CPU tensors: they are checked here and copied.  Nothing is read back.
+    Returns float32 [B,3,size,size]; with `stages=True` also uint8 [B, width+1, size, size, 3], every branch after its flip."""
+    from .._lib import check, lib
+
+    if not (torch.is_tensor(packed) and packed.is_cuda and packed.dtype == torch.uint8 and packed.dim() == 1):
+        raise TypeError("prepare_image_batch: the packed frames are one uint8 vector on the GPU (move the batch to cuda first)")
+    host = [v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v) for v in (offsets, sizes, programs)]
+    offs, szs, progs = host[0].astype(np.int64), host[1].astype(np.int32), np.ascontiguousarray(host[2], np.float64)
+    B, width = image_batch_check(offs, szs, progs, packed.numel())
+    dev, S = packed.device, int(size)
+    out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+    st = torch.empty(B, width + 1, S, S, 3, dtype=torch.uint8, device=dev) if stages else None
+    if B == 0:
+        return (out, st) if stages else out
+    if not packed.is_contiguous():
+        packed = packed.contiguous()
+    up = lambda a: torch.from_numpy(a).pin_memory().to(dev, non_blocking=True)  # noqa: E731
+    d_offs, d_szs, d_progs = up(offs), up(np.ascontiguousarray(szs)), up(progs)
+    n_pix = packed.numel() // 3
+    L = lib()
+    ws = torch.empty(max(1, L.mink_img_workspace_bytes(n_pix, B, width, S)), dtype=torch.uint8, device=dev)
+    stream = torch._C._cuda_getCurrentRawStream(dev.index)
+    from .._lib import constants
+
+    I = constants("MINK_IMG_")
+    depth = 0
+    for k in range(1, width + 1):
+        col = progs[:, I["BRANCH"] + k * I["BRANCH_STRIDE"] + I["B_DEPTH"]]
+        depth = max(depth, int(col[progs[:, I["WIDTH"]] >= k].max(initial=0)))
+    for r in range(min(depth, I["MAX_DEPTH"])):  # (a round no chain reaches is not launched)
+        check(L.mink_img_chain_round(packed.data_ptr(), d_offs.data_ptr(), d_szs.data_ptr(), d_progs.data_ptr(), n_pix, B, width, r,
+                                     ws.data_ptr(), ws.numel(), stream))
+    check(L.mink_img_finish(packed.data_ptr(), d_offs.data_ptr(), d_szs.data_ptr(), d_progs.data_ptr(), n_pix, B, width, S,
+                            ws.data_ptr(), ws.numel(), out.data_ptr(), None if st is None else st.data_ptr(), stream))
+    return (out, st) if stages else out
+
+
 class SampleSceneError(RuntimeError):
     """`mink_fps_scenes` left a scene unsampled: it is empty (or its offsets leave the matrix), its first pick lies outside
     it, or it holds more rows than the caller's bound."""
