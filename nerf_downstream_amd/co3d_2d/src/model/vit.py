@@ -7,7 +7,7 @@ dependency.
     depth x block     x = x + proj(attention(qkv(LN(x))));  x = x + fc2(GELU(fc1(LN(x))))      (pre-norm, LayerNorm eps 1e-6)
     tail              LN, `head` on the class token
 
-The attention between `qkv` and `proj` is minkowski.functional.AttentionFunction (csrc/attn.hip): it reads the packed rows
+The attention between `qkv` and `proj` is minkowski.attn.AttentionFunction (csrc/attn.hip): it reads the packed rows
 the qkv linear writes and writes the rows the proj linear reads, fp32 on the fp32 matrix cores, head size 64.  The exact-erf
 GELU is ActivationFunction (mink_activation), the linears are dense GEMMs through torch as in MinkowskiLinear.  Layer norm is
 LayerNormFunction (mink_ln_*) where the width fits that kernel's 512-channel limit -- vit_small, 384 -- and
@@ -24,7 +24,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from nerf_downstream_amd.minkowski import functional as Fn
+from nerf_downstream_amd.minkowski.attn import AttentionFunction
+from nerf_downstream_amd.minkowski.eltwise import ActivationFunction
+from nerf_downstream_amd.minkowski.norm import LayerNormFunction
 
 PATCH = 16
 HEAD_DIM = 64  # of all three networks, and the one size csrc/attn.hip is built for
@@ -36,7 +38,7 @@ SIZES = {"vit_small_patch16_224": (384, 12, 6), "vit_base_patch16_224": (768, 12
 
 def layer_norm(x, ln):
     if x.shape[1] <= LN_KERNEL_MAX:
-        return Fn.LayerNormFunction.apply(x, ln.weight, ln.bias, ln.eps, None, False)
+        return LayerNormFunction.apply(x, ln.weight, ln.bias, ln.eps, None, False)
     return F.layer_norm(x, ln.normalized_shape, ln.weight, ln.bias, ln.eps)
 
 
@@ -61,7 +63,7 @@ class Attention(nn.Module):
         self.proj = nn.Linear(dim, dim)
 
     def forward(self, x, batch, tokens):
-        return self.proj(Fn.AttentionFunction.apply(self.qkv(x), batch, tokens, self.num_heads, self.scale))
+        return self.proj(AttentionFunction.apply(self.qkv(x), batch, tokens, self.num_heads, self.scale))
 
 
 class Mlp(nn.Module):
@@ -71,7 +73,7 @@ class Mlp(nn.Module):
         self.fc2 = nn.Linear(hidden, dim)
 
     def forward(self, x):
-        return self.fc2(Fn.ActivationFunction.apply(self.fc1(x), "gelu", 0.0, None))
+        return self.fc2(ActivationFunction.apply(self.fc1(x), "gelu", 0.0, None))
 
 
 class Block(nn.Module):

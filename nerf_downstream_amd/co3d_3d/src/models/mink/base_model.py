@@ -78,7 +78,7 @@ class MinkowskiBaseModel(_HIP_ME.MinkowskiNetwork, InputInterface):
                 plan = ME.CoordinateManager.compile_plan(trace)
                 if self._coord_plan is None or len(plan) > len(self._coord_plan):
                     self._coord_plan = plan
-        skew = getattr(getattr(ME, "functional", None), "skew", None)
+        skew = getattr(getattr(ME, "streams", None), "skew", None)
         # a batch that was just copied to the device carries the event recorded after its H2D copies
         # (train.py `_to_device`): the prepare stream waits for exactly that, not for the compute stream
         with self._prepare_stream_ctx(coords, fence=batch.get("h2d_event", False) if _fence else False):
@@ -158,13 +158,13 @@ class MinkowskiBaseModel(_HIP_ME.MinkowskiNetwork, InputInterface):
             self._side.wait_stream(torch.cuda.current_stream(t.device))
         elif fence:
             self._side.wait_event(fence)
-        wait_gate = getattr(getattr(self._ME, "functional", None), "wait_prepare_gate", None)
+        wait_gate = getattr(getattr(self._ME, "streams", None), "wait_prepare_gate", None)
         if wait_gate is not None:  # (MINK_PREPARE_GATE: one map build per step, beside its middle)
             wait_gate(self._side)
         return torch.cuda.stream(self._side)
 
     def _new_prepare_stream(self, device):
-        new_stream = getattr(getattr(self._ME, "functional", None), "new_stream", None)
+        new_stream = getattr(getattr(self._ME, "streams", None), "new_stream", None)
         import torch
 
         st = new_stream(device, "prepare") if new_stream is not None else torch.cuda.Stream(device=device)

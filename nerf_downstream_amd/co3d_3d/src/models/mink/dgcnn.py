@@ -44,16 +44,16 @@ class DGCNN_cls(MinkowskiBaseModel):
         self.knn_indices = []  # the neighbour tables of the last forward: four int32 [n, k] tensors of global rows
 
     def _bn_lrelu(self, F, bn):
-        Fn = self._ME.functional
+        ME = self._ME
         training = bn.training or not bn.track_running_stats
         if training and bn.track_running_stats:
             bn.num_batches_tracked += 1
         momentum = bn.momentum if bn.momentum is not None else 1.0 / max(float(bn.num_batches_tracked), 1.0)
-        F = Fn.BatchNormFunction.apply(F, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps, None, False)
-        return Fn.ActivationFunction.apply(F, "leaky_relu", 0.2, None)
+        F = ME.norm.BatchNormFunction.apply(F, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps, None, False)
+        return ME.eltwise.ActivationFunction.apply(F, "leaky_relu", 0.2, None)
 
     def forward(self, x):
-        Fn, G = self._ME.functional, self._ME.graph
+        pool, G = self._ME.pool, self._ME.graph
         x._settle()
         m = x.coordinate_manager
         boff = m.field_batch_offsets(x.C)
@@ -67,7 +67,7 @@ class DGCNN_cls(MinkowskiBaseModel):
             outs.append(F)
         F = torch.cat(outs, 1).mm(self.conv5[0].weight.view(self.emb_dims, -1).t())
         F = self._bn_lrelu(F, self.conv5[1])
-        h = torch.cat([Fn.GlobalMaxPoolFunction.apply(F, boff)[0], Fn.GlobalAvgPoolFunction.apply(F, boff)], 1)
+        h = torch.cat([pool.GlobalMaxPoolFunction.apply(F, boff)[0], pool.GlobalAvgPoolFunction.apply(F, boff)], 1)
         h = self.dp1(self._bn_lrelu(self.linear1(h), self.bn6))
         h = self.dp2(self._bn_lrelu(self.linear2(h), self.bn7))
         return self.linear3(h)

@@ -40,18 +40,18 @@ class BasicBlock(nn.Module):
         Returns (shortcut, join) where join() makes the current stream wait for the branch."""
         import torch
 
-        from nerf_downstream_amd.minkowski import functional as Fn
+        from nerf_downstream_amd.minkowski import streams
 
         cur = torch.cuda.current_stream(x.F.device)
-        br = Fn.branch_stream(x.F.device, home=cur)
-        Fn.stream_wait(br, cur)
-        Fn.skew(br)
+        br = streams.branch_stream(x.F.device, home=cur)
+        streams.stream_wait(br, cur)
+        streams.skew(br)
         with torch.cuda.stream(br):
             shortcut = self._shortcut(x)
         x.F.record_stream(br)
 
         def join():
-            Fn.stream_wait(cur, br)
+            streams.stream_wait(cur, br)
             shortcut.F.record_stream(cur)
 
         return shortcut, join
@@ -67,9 +67,9 @@ class BasicBlock(nn.Module):
     def _may_fork(self, x):
         if not (self._fused and self._fork and self.downsample is not None and x.F.is_cuda):
             return False
-        from nerf_downstream_amd.minkowski import functional as Fn
+        from nerf_downstream_amd.minkowski import streams
 
-        return Fn.branch_fork_enabled() and (getattr(x.coordinate_manager, "prepared", False) or self._fork_unprepared)
+        return streams.branch_fork_enabled() and (getattr(x.coordinate_manager, "prepared", False) or self._fork_unprepared)
 
     def forward(self, x):
         if self._may_fork(x):

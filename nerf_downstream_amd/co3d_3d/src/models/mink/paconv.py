@@ -40,7 +40,7 @@ class _PAConvBase(MinkowskiBaseModel):
         F = x.F.float()
         idx = ME.graph.knn(F, boff, self.k)  # unlike DGCNN, the search is in xyz only
         self.knn_indices = [idx]
-        return F, boff, idx, ME.paconv.scorenet_input(F, idx), ME.functional.lazy_index_csr(idx, F.shape[0])
+        return F, boff, idx, ME.paconv.scorenet_input(F, idx), ME.field.lazy_index_csr(idx, F.shape[0])
 
     def _layer(self, i, h, rows, idx, csr, mode, bias):
         P = self._ME.paconv
@@ -73,13 +73,13 @@ class PAConvPointNet(_PAConvBase):
         self.linear2 = nn.Linear(head, out_channel)
 
     def forward(self, x):
-        Fn, P = self._ME.functional, self._ME.paconv
+        pool, P = self._ME.pool, self._ME.paconv
         F, boff, idx, rows, csr = self._graph(x)
         h = P.batch_norm_rows(F.mm(self.conv1.weight.view(self.conv1.out_channels, -1).t()), self.bn1, True)
         for i in (2, 3, 4):
             h = self._layer(i, h, rows, idx, csr, "pointnet", 0)
         h = P.batch_norm_rows(h.mm(self.conv5.weight.view(self.conv5.out_channels, -1).t()), self.bn5, True)
-        h = Fn.GlobalMaxPoolFunction.apply(h, boff)[0]
+        h = pool.GlobalMaxPoolFunction.apply(h, boff)[0]
         h = self.dp1(P.batch_norm_rows(self.linear1(h), self.bn6, True))
         return self.linear2(h)
 
@@ -114,7 +114,7 @@ class PAConvDGCNN(_PAConvBase):
         self.linear3 = nn.Linear(head[1], out_channel)
 
     def forward(self, x):
-        Fn, P = self._ME.functional, self._ME.paconv
+        pool, P = self._ME.pool, self._ME.paconv
         h, boff, idx, rows, csr = self._graph(x)
         outs = []
         for i in (1, 2, 3, 4):
@@ -122,7 +122,7 @@ class PAConvDGCNN(_PAConvBase):
             outs.append(h)
         conv = self.conv5[0]
         h = P.batch_norm_rows(torch.cat(outs, 1).mm(conv.weight.view(conv.out_channels, -1).t()), self.bn5, True)
-        h = torch.cat([Fn.GlobalMaxPoolFunction.apply(h, boff)[0], Fn.GlobalAvgPoolFunction.apply(h, boff)], 1)
+        h = torch.cat([pool.GlobalMaxPoolFunction.apply(h, boff)[0], pool.GlobalAvgPoolFunction.apply(h, boff)], 1)
         h = self.dp1(P.batch_norm_rows(self.linear1(h), self.bn11, True))
         h = self.dp2(P.batch_norm_rows(self.linear2(h), self.bn22, True))
         return self.linear3(h)

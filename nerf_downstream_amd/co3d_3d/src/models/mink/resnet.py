@@ -105,7 +105,7 @@ class ResNetBase(MinkowskiBaseModel):
                 self._trunk_plan = trunk.plan_for(self) or False
             xs = x.sparse()
             if self._trunk_plan and trunk.usable(self, self._trunk_plan, xs):
-                fork = getattr(self.layer1[0], "_fork", False) and trunk.Fn.trunk_branch_mode() is not None
+                fork = getattr(self.layer1[0], "_fork", False) and trunk.streams.trunk_branch_mode() is not None
                 feats = trunk.TrunkFunction.apply(xs.F, self._trunk_plan, xs.coordinate_manager, fork, *self._trunk_plan.params)
                 out = self._ME.SparseTensor(feats, trunk.out_key_of(self._trunk_plan), xs.coordinate_manager)
                 return self._head(out)
@@ -127,7 +127,7 @@ class ResNetBase(MinkowskiBaseModel):
         fin = self.final
         if self._fused and out.F.is_cuda and getattr(fin, "use_mm", False) and out.F.dtype == torch.float32:
             m = out.coordinate_manager
-            return self._ME.functional.global_avg_linear(out.F, m.batch_offsets(out.coordinate_map_key), fin.kernel, fin.bias)
+            return self._ME.head.global_avg_linear(out.F, m.batch_offsets(out.coordinate_map_key), fin.kernel, fin.bias)
         return self.final(self.glob_avg(out)).F
 
 

@@ -10,7 +10,7 @@ import torch.nn.functional as F
 def cross_entropy(logits, labels):
     """F.cross_entropy(logits, labels) (reference :33); device logits take the backend's one-launch kernels."""
     if logits.is_cuda:
-        from nerf_downstream_amd.minkowski.functional import cross_entropy as hip_ce
+        from nerf_downstream_amd.minkowski.head import cross_entropy as hip_ce
 
         return hip_ce(logits, labels)
     return F.cross_entropy(logits, labels)

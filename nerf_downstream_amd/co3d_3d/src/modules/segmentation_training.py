@@ -4,14 +4,14 @@ with an ignore label and an optional weight on the last ("void") class (SegLoss 
 confusion-matrix metrics of src/utils `fast_hist` / `per_class_iu` (:115-126) accumulated on the device.
 
 Loss, prediction, confusion matrix and the label counts of a step come out of ONE pass over the logits
-(minkowski/functional.py: seg_cross_entropy); the metrics below only do arithmetic on that pass's C x C histogram."""
+(minkowski/head.py: seg_cross_entropy); the metrics below only do arithmetic on that pass's C x C histogram."""
 import math
 
 import numpy as np
 import torch
 
 from nerf_downstream_amd import gin_lite as gin
-from nerf_downstream_amd.minkowski.functional import seg_cross_entropy, seg_stats
+from nerf_downstream_amd.minkowski.head import seg_cross_entropy, seg_stats
 
 EPS = 1e-10
 

@@ -3,7 +3,7 @@
 data/utils.py:1), backed by hand-written HIP kernels for gfx950 (libmink_hip.so)."""
 import enum
 
-from . import MinkowskiFunctional, MinkowskiOps, graph, paconv, utils # noqa: F401
+from . import MinkowskiFunctional, MinkowskiOps, eltwise, field, graph, head, norm, paconv, pool, streams, utils  # noqa: F401
 from .coords import CoordinateManager, CoordinateMapKey  # noqa: F401
 from .modules import (  # noqa: F401
     MinkowskiAvgPooling,

@@ -515,7 +515,7 @@ class CoordinateManager:
         """(idx int32 [N], csr_fn) of the float rows coords[N, 4] = (b, x, y, z) of a TensorField of this manager against
         the map `key`: idx[i] = the row of the voxel of that tensor stride containing row i, -1 where there is none
         (mink_field_map) [ME-recall of SparseTensor.slice; parity unpinned, ME is absent]; csr_fn() -> the rows grouped by
-        voxel (functional.index_csr), built on first use -- the backward of the slice.  Kept on the manager per tensor stride
+        voxel (field.index_csr), built on first use -- the backward of the slice.  Kept on the manager per tensor stride
         for the coordinate tensor it was computed from (a field and everything derived from it share that tensor), so the
         four slices of fcnn.py:158-161 and the next batch's backward find it.  Out-of-range, NaN and infinite rows raise
         ValueError (one host read of the status word)."""

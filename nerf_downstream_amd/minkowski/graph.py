@@ -9,6 +9,9 @@ import torch
 
 from .._lib import check, lib
 from . import functional as Fn
+from ._rt import _check_offsets, _f32c, _row_stride, _scratch, _stream
+from .field import lazy_index_csr
+from .norm import _bn_statistics
 
 MAX_K, MAX_C = 64, 256  # MINK_KNN_MAX_K / MINK_KNN_MAX_C
 
@@ -17,14 +20,14 @@ def knn(x, batch_offsets, k):
     """idx int32 [n, k]: the global rows of the k rows of the same sample (batch_offsets int32 [B + 1] on the device) nearest
     to every row of x [n, C] in squared Euclidean distance, the row itself included; ascending distance, ties to the lower
     row.  Not differentiable.  Slots of a sample with fewer than k rows are -1 (see check_sample_sizes)."""
-    B = Fn._check_offsets(batch_offsets)
+    B = _check_offsets(batch_offsets)
     x = x.detach()
     assert x.is_cuda and x.dim() == 2, "knn: x [n, C] on the device"
     if x.dtype != torch.float32 or x.stride(1) != 1:
         x = x.float().contiguous()
     n, C = x.shape
     idx = torch.empty(n, int(k), dtype=torch.int32, device=x.device)
-    check(lib().mink_knn(x.data_ptr(), n, x.stride(0) if n > 1 else C, C, batch_offsets.data_ptr(), B, int(k), idx.data_ptr(), Fn._stream()))
+    check(lib().mink_knn(x.data_ptr(), n, _row_stride(x), C, batch_offsets.data_ptr(), B, int(k), idx.data_ptr(), _stream()))
     return idx
 
 
@@ -56,13 +59,13 @@ def knn_cross(q, c, k=1, q_offsets=None, c_offsets=None, return_distance=False):
         both = torch.zeros(4, dtype=torch.int32, device=q.device)
         both[1], both[3] = nq, nc  # (host scalars written by fills: no read-back)
         q_offsets, c_offsets = both[:2], both[2:]
-    B = Fn._check_offsets(q_offsets)
-    assert Fn._check_offsets(c_offsets) == B, "knn_cross: q_offsets and c_offsets describe the same B samples"
+    B = _check_offsets(q_offsets)
+    assert _check_offsets(c_offsets) == B, "knn_cross: q_offsets and c_offsets describe the same B samples"
     idx = torch.empty(nq, int(k), dtype=torch.int32, device=q.device)
     dist = torch.empty(nq, int(k), dtype=torch.float32, device=q.device) if return_distance else None
-    check(lib().mink_knn_cross(q.data_ptr(), nq, q.stride(0) if nq > 1 else C, c.data_ptr(), nc, c.stride(0) if nc > 1 else C, C,
+    check(lib().mink_knn_cross(q.data_ptr(), nq, _row_stride(q), c.data_ptr(), nc, _row_stride(c), C,
                                q_offsets.data_ptr(), c_offsets.data_ptr(), B, int(k), idx.data_ptr(),
-                               dist.data_ptr() if return_distance else None, Fn._stream()))
+                               dist.data_ptr() if return_distance else None, _stream()))
     return (idx, dist) if return_distance else idx
 
 
@@ -90,7 +93,7 @@ class EdgeConvFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, gamma, beta, running_mean, running_var, idx, training, momentum, eps):
         L = lib()
-        x = Fn._f32c(x)
+        x = _f32c(x)
         n, cin = x.shape
         cout = W.shape[0]
         assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.dim() == 2 and idx.shape[0] == n, \
@@ -101,22 +104,22 @@ class EdgeConvFunction(torch.autograd.Function):
         W1 = Wm[:, :cin].contiguous()
         Wd = (Wm[:, cin:] - Wm[:, :cin]).contiguous()
         P, Q = _xwt(x, W1), _xwt(x, Wd)
-        gamma, beta = Fn._f32c(gamma.detach()), Fn._f32c(beta.detach())
+        gamma, beta = _f32c(gamma.detach()), _f32c(beta.detach())
         if training:
             partial = torch.empty(L.mink_edge_stats_rows(n), 2, cout, dtype=torch.float64, device=x.device)
             check(L.mink_edge_stats(P.data_ptr(), Q.data_ptr(), idx.data_ptr(), n, k, cout, partial.data_ptr(), partial.numel() * 8,
-                                    Fn._stream()))
-            mean, invstd = Fn._bn_statistics(L, P, n * k, cout, eps, momentum, running_mean, running_var, partial)
+                                    _stream()))
+            mean, invstd = _bn_statistics(L, P, n * k, cout, eps, momentum, running_mean, running_var, partial)
         else:
             mean = running_mean.float().contiguous()
             invstd = torch.rsqrt(running_var.float() + eps)
         y = torch.empty(n, cout, dtype=torch.float32, device=x.device)
         arg = torch.empty(n, cout, dtype=torch.uint8, device=x.device)
         check(L.mink_edge_fwd(P.data_ptr(), Q.data_ptr(), idx.data_ptr(), n, k, cout, mean.data_ptr(), invstd.data_ptr(),
-                              gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), arg.data_ptr(), Fn._stream()))
+                              gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), arg.data_ptr(), _stream()))
         ctx.save_for_backward(x, W1, Wd, P, Q, arg, mean, invstd, gamma, beta, idx)
         ctx.training, ctx.w_shape = bool(training), W.shape
-        ctx.csr_fn = Fn.lazy_index_csr(idx, n)
+        ctx.csr_fn = lazy_index_csr(idx, n)
         ctx.mark_non_differentiable(arg)
         return y, arg
 
@@ -124,17 +127,17 @@ class EdgeConvFunction(torch.autograd.Function):
     def backward(ctx, gy, _garg=None):
         L = lib()
         x, W1, Wd, P, Q, arg, mean, invstd, gamma, beta, idx = ctx.saved_tensors
-        gy = Fn._f32c(gy)
+        gy = _f32c(gy)
         n, cout = gy.shape
         k = idx.shape[1]
         members, seg = ctx.csr_fn()
         dP, dQ = torch.empty_like(P), torch.empty_like(Q)
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        ws = Fn._scratch(L.mink_edge_bwd_workspace_bytes(n, cout), gy.device, "edge")
+        ws = _scratch(L.mink_edge_bwd_workspace_bytes(n, cout), gy.device, "edge")
         check(L.mink_edge_bwd(gy.data_ptr(), P.data_ptr(), Q.data_ptr(), idx.data_ptr(), arg.data_ptr(), n, k, cout, mean.data_ptr(),
                               invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), int(ctx.training), members.data_ptr(),
                               seg.data_ptr(), dP.data_ptr(), dQ.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(),
-                              ws.numel(), Fn._stream()))
+                              ws.numel(), _stream()))
         gx = gw = None
         if ctx.needs_input_grad[0]:
             gx = torch.addmm(dP.mm(W1), dQ, Wd)

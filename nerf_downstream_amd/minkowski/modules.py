@@ -9,6 +9,20 @@ import torch.nn as nn
 from .. import gin_lite as gin
 from . import functional as Fn
 from .coords import ORIGIN_TS, CoordinateMapKey, _as_int
+from .eltwise import ActivationFunction, ReLUFunction
+from .field import FieldGatherCatFunction, lazy_index_csr
+from .interp import InterpolationFunction
+from .norm import BatchNormFunction, BNReLUSumPoolFunction, InstanceNormFunction, LayerNormFunction, SyncBatchNormFunction
+from .pool import (
+    AvgPoolFunction,
+    GlobalAvgPoolFunction,
+    GlobalMaxPoolFunction,
+    GlobalSumPoolFunction,
+    OverlapSumPoolFunction,
+    SparseMaxPoolFunction,
+    SumPoolFunction,
+)
+from .posenc import PositionalEncodingFunction
 from .tensor import SparseTensor, TensorField
 
 
@@ -187,7 +201,7 @@ def cat(*tensors):
             if t.coordinate_manager is not first.coordinate_manager or t.C.shape[0] != first.C.shape[0]:
                 raise ValueError("TensorFields must share the coordinate manager and the rows")
         if len(tensors) <= 8 and all(t._F is None and t._pending is not None for t in tensors):
-            out = Fn.FieldGatherCatFunction.apply(tuple(t._pending[1] for t in tensors), *[t._pending[0] for t in tensors])
+            out = FieldGatherCatFunction.apply(tuple(t._pending[1] for t in tensors), *[t._pending[0] for t in tensors])
         else:
             out = torch.cat([t.F for t in tensors], dim=1)
         return first._like(out)
@@ -230,7 +244,7 @@ class MinkowskiBatchNorm(nn.Module):
             _check_same(input, residual)
         gamma = bn.weight if bn.affine else torch.ones(bn.num_features, device=F.device)
         beta = bn.bias if bn.affine else torch.zeros(bn.num_features, device=F.device)
-        out = Fn.BatchNormFunction.apply(
+        out = BatchNormFunction.apply(
             F, gamma, beta, bn.running_mean, bn.running_var, training,
             _bn_momentum(bn), bn.eps,
             residual.F if residual is not None else None, bool(relu),
@@ -258,7 +272,7 @@ class MinkowskiSyncBatchNorm(MinkowskiBatchNorm):
             bn.num_batches_tracked += 1
         if residual is not None:
             _check_same(input, residual)
-        out = Fn.SyncBatchNormFunction.apply(
+        out = SyncBatchNormFunction.apply(
             _features(input), bn.weight, bn.bias, bn.running_mean, bn.running_var, _bn_momentum(bn),
             bn.eps, residual.F if residual is not None else None, bool(relu), self.process_group)
         return _same_kind(input, out)
@@ -287,7 +301,7 @@ class MinkowskiReLU(nn.Module):
         self.inplace = inplace
 
     def forward(self, input):
-        return _same_kind(input, Fn.ReLUFunction.apply(_features(input)))
+        return _same_kind(input, ReLUFunction.apply(_features(input)))
 
 
 class _Activation(nn.Module):
@@ -303,7 +317,7 @@ class _Activation(nn.Module):
             self.alpha = float(args[0] if args else kwargs.get(self.ARG, self.ALPHA))
 
     def forward(self, input):
-        return _same_kind(input, Fn.ActivationFunction.apply(_features(input), self.KIND, self.alpha, None))
+        return _same_kind(input, ActivationFunction.apply(_features(input), self.KIND, self.alpha, None))
 
 
 class MinkowskiLeakyReLU(_Activation):
@@ -334,7 +348,7 @@ class MinkowskiPReLU(nn.Module):
         self.weight = nn.Parameter(torch.full((num_parameters,), float(init)))
 
     def forward(self, input):
-        return _same_kind(input, Fn.ActivationFunction.apply(_features(input), "prelu", 0.0, self.weight))
+        return _same_kind(input, ActivationFunction.apply(_features(input), "prelu", 0.0, self.weight))
 
 
 class MinkowskiInstanceNorm(nn.Module):
@@ -358,7 +372,7 @@ class MinkowskiInstanceNorm(nn.Module):
     def forward(self, input, relu=False, residual=None):
         if residual is not None:
             _check_same(input, residual)
-        out = Fn.InstanceNormFunction.apply(_features(input), self.weight.reshape(-1), self.bias.reshape(-1),
+        out = InstanceNormFunction.apply(_features(input), self.weight.reshape(-1), self.bias.reshape(-1),
                                             _sample_offsets(input), self.eps,
                                             residual.F if residual is not None else None, bool(relu))
         return _same_kind(input, out)
@@ -389,7 +403,7 @@ class MinkowskiLayerNorm(nn.Module):
         C = ln.normalized_shape[0]
         gamma = ln.weight if ln.weight is not None else torch.ones(C, device=F.device)
         beta = ln.bias if ln.bias is not None else torch.zeros(C, device=F.device)
-        out = Fn.LayerNormFunction.apply(F, gamma, beta, ln.eps, residual.F if residual is not None else None, bool(relu))
+        out = LayerNormFunction.apply(F, gamma, beta, ln.eps, residual.F if residual is not None else None, bool(relu))
         return _same_kind(input, out)
 
 
@@ -463,7 +477,7 @@ class MinkowskiPositionalEncoding(nn.Module):
         if F.dim() != 2 or F.shape[1] != self.shape[0]:
             raise ValueError(f"MinkowskiPositionalEncoding: {tuple(F.shape)} features, in_channel = {self.shape[0]}")
         lo, hi = self.include_original_channel_range or (0, 0)
-        out = Fn.PositionalEncodingFunction.apply(F, self.frequencies, self.offset.view(-1), self.num_encoding_functions, lo, hi)
+        out = PositionalEncodingFunction.apply(F, self.frequencies, self.offset.view(-1), self.num_encoding_functions, lo, hi)
         return _same_kind(input, out)
 
 
@@ -526,7 +540,7 @@ class MinkowskiAvgPooling(_LocalPooling):
 
     def forward(self, input):
         m, out_key, nbr, nbr_t = self._tables(input)
-        out, _ = Fn.AvgPoolFunction.apply(input.F, nbr, nbr_t)
+        out, _ = AvgPoolFunction.apply(input.F, nbr, nbr_t)
         return SparseTensor(out, out_key, m)
 
 
@@ -537,7 +551,7 @@ class MinkowskiMaxPooling(_LocalPooling):
 
     def forward(self, input):
         m, out_key, nbr, nbr_t = self._tables(input)
-        out, _ = Fn.SparseMaxPoolFunction.apply(input.F, nbr, nbr_t)
+        out, _ = SparseMaxPoolFunction.apply(input.F, nbr, nbr_t)
         return SparseTensor(out, out_key, m)
 
 
@@ -570,7 +584,7 @@ class MinkowskiSumPooling(nn.Module):
                 input = norm(input, relu=True)
             out_key = m.stride(in_key, self.stride)
             nbr, nbr_t = m.kernel_table(in_key, out_key, self.kernel_size, 1, transposed=True)
-            out, _ = Fn.OverlapSumPoolFunction.apply(input.F, nbr, nbr_t)
+            out, _ = OverlapSumPoolFunction.apply(input.F, nbr, nbr_t)
             return SparseTensor(out, out_key, m)
         out_key = m.stride(in_key, self.stride)
         nbr, _ = m.kernel_table(in_key, out_key, self.kernel_size, 1)
@@ -581,13 +595,13 @@ class MinkowskiSumPooling(nn.Module):
             training = bn.training or not bn.track_running_stats
             if training and bn.track_running_stats and not norm.counted_by_parent:
                 bn.num_batches_tracked += 1
-            out = Fn.BNReLUSumPoolFunction.apply(input.F, bn.weight, bn.bias, bn.running_mean, bn.running_var, training,
+            out = BNReLUSumPoolFunction.apply(input.F, bn.weight, bn.bias, bn.running_mean, bn.running_var, training,
                                                  _bn_momentum(bn), bn.eps, nbr, i2o,
                                                  getattr(input, "_bn_partial", None) if training else None)
         else:
             if norm is not None:
                 input = norm(input, relu=True)
-            out = Fn.SumPoolFunction.apply(input.F, nbr, i2o)
+            out = SumPoolFunction.apply(input.F, nbr, i2o)
         return SparseTensor(out, out_key, m)
 
 
@@ -619,7 +633,7 @@ class MinkowskiGlobalAvgPooling(nn.Module):
     """ME.MinkowskiGlobalAvgPooling() (resnet.py:15-22): row b of the output is batch index b."""
 
     def forward(self, input):
-        out = Fn.GlobalAvgPoolFunction.apply(_features(input), _sample_offsets(input))
+        out = GlobalAvgPoolFunction.apply(_features(input), _sample_offsets(input))
         return SparseTensor(out, CoordinateMapKey(ORIGIN_TS), input.coordinate_manager)
 
 
@@ -633,7 +647,7 @@ class MinkowskiGlobalMaxPooling(nn.Module):
         super().__init__()
 
     def forward(self, input):
-        out, _ = Fn.GlobalMaxPoolFunction.apply(_features(input), _sample_offsets(input))
+        out, _ = GlobalMaxPoolFunction.apply(_features(input), _sample_offsets(input))
         return SparseTensor(out, CoordinateMapKey(ORIGIN_TS), input.coordinate_manager)
 
 
@@ -644,7 +658,7 @@ class MinkowskiGlobalSumPooling(nn.Module):
         super().__init__()
 
     def forward(self, input):
-        out = Fn.GlobalSumPoolFunction.apply(_features(input), _sample_offsets(input))
+        out = GlobalSumPoolFunction.apply(_features(input), _sample_offsets(input))
         return SparseTensor(out, CoordinateMapKey(ORIGIN_TS), input.coordinate_manager)
 
 
@@ -662,7 +676,7 @@ class MinkowskiInterpolation(nn.Module):
 
     def forward(self, input, tfield):
         imap, w = input.coordinate_manager.interpolation_map_weight(input.coordinate_map_key, tfield)
-        out = Fn.InterpolationFunction.apply(input.F, imap, w, Fn.lazy_csr(imap, input.F.shape[0]))
+        out = InterpolationFunction.apply(input.F, imap, w, lazy_index_csr(imap, input.F.shape[0]))
         if not (self.return_kernel_map or self.return_weights):
             return out
         flat = imap.reshape(-1)

@@ -14,8 +14,10 @@ import torch
 import torch.nn as nn
 
 from .._lib import check, lib
-from . import functional as Fn
+from ._rt import _f32c, _stream
+from .field import lazy_index_csr
 from .graph import MAX_K, _xwt
+from .norm import BatchNormFunction
 
 MAX_M = 16  # MINK_PACONV_MAX_M
 MODES = ("dgcnn", "pointnet")
@@ -35,12 +37,12 @@ def _bank(matrice, M, cin, mode):
 class PAConvFunction(torch.autograd.Function):
     """y [n, O] = apply(x [n, Cin], matrice [Cin', M O], scores [n, k, M], idx int32 [n, k], mode, csr_fn); differentiable in x,
     matrice and scores.  Kept for the backward: x, the scores, [A | S x] and S.  `csr_fn` returns the incoming-edge lists of
-    idx (Fn.lazy_index_csr(idx, n): built on the first backward; layers that share idx may share it)."""
+    idx (lazy_index_csr(idx, n): built on the first backward; layers that share idx may share it)."""
 
     @staticmethod
     def forward(ctx, x, matrice, scores, idx, mode, csr_fn):
         L = lib()
-        x, s = Fn._f32c(x), Fn._f32c(scores)
+        x, s = _f32c(x), _f32c(scores)
         n, cin = x.shape
         assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.dim() == 2 and idx.shape[0] == n, \
             "paconv: idx int32 [n, k] on the device"
@@ -53,18 +55,18 @@ class PAConvFunction(torch.autograd.Function):
         Z = torch.empty(n, 2, M, cin, dtype=torch.float32, device=x.device)  # [A | S x]
         S = torch.empty(n, M, dtype=torch.float32, device=x.device)
         check(L.mink_paconv_gather(x.data_ptr(), s.data_ptr(), idx.data_ptr(), n, k, M, cin, Z.data_ptr(), Z.data_ptr() + 4 * M * cin,
-                                   2 * M * cin, S.data_ptr(), Fn._stream()))
+                                   2 * M * cin, S.data_ptr(), _stream()))
         y = _xwt(Z.view(n, -1), W.t().contiguous()) if n else x.new_zeros(0, W.shape[1])
         ctx.save_for_backward(x, s, idx, Z, S, W)
         ctx.mode, ctx.bank_shape = mode, matrice.shape
-        ctx.csr_fn = csr_fn if csr_fn is not None else Fn.lazy_index_csr(idx, n)
+        ctx.csr_fn = csr_fn if csr_fn is not None else lazy_index_csr(idx, n)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         L = lib()
         x, s, idx, Z, S, W = ctx.saved_tensors
-        g = Fn._f32c(gy)
+        g = _f32c(gy)
         n, cin = x.shape
         k, M, O = idx.shape[1], s.shape[2], W.shape[1]
         ldz = 2 * M * cin
@@ -74,12 +76,12 @@ class PAConvFunction(torch.autograd.Function):
             dA, dCX = dZ.data_ptr(), dZ.data_ptr() + 4 * M * cin
             if ctx.needs_input_grad[2]:
                 gs = torch.empty_like(s)
-                check(L.mink_paconv_score_bwd(dA, dCX, ldz, x.data_ptr(), idx.data_ptr(), n, k, M, cin, gs.data_ptr(), Fn._stream()))
+                check(L.mink_paconv_score_bwd(dA, dCX, ldz, x.data_ptr(), idx.data_ptr(), n, k, M, cin, gs.data_ptr(), _stream()))
             if ctx.needs_input_grad[0]:
                 members, seg = ctx.csr_fn()
                 gx = torch.empty_like(x)
                 check(L.mink_paconv_scatter_bwd(dA, dCX, ldz, s.data_ptr(), S.data_ptr(), members.data_ptr(), seg.data_ptr(), n, k, M, cin,
-                                                gx.data_ptr(), Fn._stream()))
+                                                gx.data_ptr(), _stream()))
         if ctx.needs_input_grad[1]:
             dW = Z.view(n, -1).t().mm(g).view(2, M, cin, O)  # (dWn, -dWc)
             dWn, dWc = dW[0], -dW[1]
@@ -108,7 +110,7 @@ def batch_norm_rows(x, bn, relu):
     if training and bn.track_running_stats:
         bn.num_batches_tracked += 1
     momentum = bn.momentum if bn.momentum is not None else 1.0 / max(float(bn.num_batches_tracked), 1.0)
-    return Fn.BatchNormFunction.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps, None, bool(relu))
+    return BatchNormFunction.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps, None, bool(relu))
 
 
 def scorenet_input(xyz, idx):

@@ -2,7 +2,14 @@
 reference: base_model.py:10-13, resnet.py:164,177, resnet_block.py:66, sparse_conv.py:387-425)."""
 import torch
 
+from .._lib import check, lib
 from . import functional as Fn
+from . import streams
+from ._rt import _stream
+from .eltwise import AddFunction
+from .field import FieldGatherCatFunction, SegmentMeanFunction, index_csr, lazy_index_csr, segment_mean
+from .head import slice_rows
+from .interp import InterpolationFunction, SplatFunction
 from .coords import CoordinateManager, CoordinateMapKey
 
 
@@ -74,7 +81,7 @@ class SparseTensor:
         if m.levels[1].n == field.F.shape[0]:
             F = self._F  # no duplicates: the rows are the field's rows, in order (no copy)
         else:
-            F = Fn.slice_rows(self._F, m.field_inverse, *_field_members(m))  # (gather; backward: fixed-order segment sum)
+            F = slice_rows(self._F, m.field_inverse, *_field_members(m))  # (gather; backward: fixed-order segment sum)
         return TensorField(features=F, coordinates=field.C, _manager=m, _origin=field)
 
     def features_at_coordinates(self, query):
@@ -82,7 +89,7 @@ class SparseTensor:
         stride -> a tensor [N, C] [ME-recall of SparseTensor.features_at_coordinates; parity unpinned, ME is absent].  An
         absent corner contributes nothing (no renormalisation); the gradient goes to the features only."""
         imap, w = self._manager.interpolation_map_weight(self.coordinate_map_key, query)
-        return Fn.InterpolationFunction.apply(self._F, imap, w, Fn.lazy_csr(imap, self._F.shape[0]))
+        return InterpolationFunction.apply(self._F, imap, w, lazy_index_csr(imap, self._F.shape[0]))
 
     def interpolate(self, field):
         """`y.interpolate(x)` (reference models/mink/fcnn.py:194-208): this tensor's features, at any tensor stride, read at
@@ -93,12 +100,12 @@ class SparseTensor:
 
     def __iadd__(self, other):  # `out += residual`, reference resnet_block.py:66
         self._check(other)
-        self._F = Fn.AddFunction.apply(self._F, other._F)
+        self._F = AddFunction.apply(self._F, other._F)
         return self
 
     def __add__(self, other):
         self._check(other)
-        return SparseTensor(Fn.AddFunction.apply(self._F, other._F), self.coordinate_map_key, self._manager)
+        return SparseTensor(AddFunction.apply(self._F, other._F), self.coordinate_map_key, self._manager)
 
     def __repr__(self):
         return f"SparseTensor(F={tuple(self._F.shape)}, tensor_stride={self.tensor_stride})"
@@ -158,7 +165,7 @@ class TensorField:
         self._F, self._C = features, coordinates
         m = self._manager = CoordinateManager(D=coordinates.shape[1] - 1, device=coordinates.device)
         self._plan, self._ready = plan, None
-        self._build_stream = Fn.current_stream(coordinates.device)
+        self._build_stream = streams.current_stream(coordinates.device)
         defer = bool(defer) and plan is not None
         self.coordinate_field_map_key = m.insert_field(coordinates, CoordinateManager.plan_stride_chain(plan), defer=defer)
         if not defer:
@@ -171,8 +178,8 @@ class TensorField:
             m.finish_field()
             return
         plan, self._plan = self._plan, None
-        Fn.skew(self._build_stream)
-        Fn.wait_prepare_gate(self._build_stream)
+        streams.skew(self._build_stream)
+        streams.wait_prepare_gate(self._build_stream)
         with torch.cuda.stream(self._build_stream):
             m.finish_field()
             m.replay(plan)
@@ -188,7 +195,7 @@ class TensorField:
     def F(self):
         if self._F is None:  # a strided slice read on its own: the one-source form of the fused gather
             x, fmap = self._pending
-            self._F = Fn.FieldGatherCatFunction.apply((fmap,), x)
+            self._F = FieldGatherCatFunction.apply((fmap,), x)
         return self._F
 
     @property
@@ -211,7 +218,7 @@ class TensorField:
         m = root._manager
         root.finish()
         if root._ready is not None:  # maps were built ahead of time on another stream
-            cur = Fn.current_stream()
+            cur = streams.current_stream()
             cur.wait_event(root._ready)
             m.hand_over(cur)
             for t in (root._F, root._C):  # may have been produced on the build stream (GPU-side decode)
@@ -237,9 +244,9 @@ class TensorField:
         else:
             order, seg = _field_members(m)
             if F.requires_grad and torch.is_grad_enabled():  # learned per-point features (reference fcnn.py:143-144,165)
-                Fs = Fn.SegmentMeanFunction.apply(F, order, seg, n_unique)
+                Fs = SegmentMeanFunction.apply(F, order, seg, n_unique)
             else:
-                Fs = Fn.segment_mean(F, order, seg, n_unique)
+                Fs = segment_mean(F, order, seg, n_unique)
         return SparseTensor(Fs, CoordinateMapKey(1), m)
 
     def splat(self):
@@ -259,7 +266,7 @@ class TensorField:
         corners = torch.empty(8 * n, 4, dtype=torch.int32, device=C.device)
         w = torch.empty(n, 8, dtype=torch.float32, device=C.device)
         status = torch.zeros(1, dtype=torch.int32, device=C.device)
-        Fn.check(Fn.lib().mink_splat_coords(C.data_ptr(), n, corners.data_ptr(), w.data_ptr(), status.data_ptr(), Fn._stream()))
+        check(lib().mink_splat_coords(C.data_ptr(), n, corners.data_ptr(), w.data_ptr(), status.data_ptr(), _stream()))
         if int(status.item()) & 1:  # MINK_STATUS_RANGE
             raise ValueError(
                 "coordinate outside the supported range (0 <= batch <= 65534, -32768 <= x, y, z <= 32767 for every corner of "
@@ -269,5 +276,5 @@ class TensorField:
         key = m.insert_field(corners)
         n_rows = m.levels[1].n
         imap = m.field_inverse.reshape(n, 8)
-        Fs = Fn.SplatFunction.apply(self.F, imap, w, Fn.pair_csr(imap, n_rows), n_rows)
+        Fs = SplatFunction.apply(self.F, imap, w, index_csr(imap, n_rows), n_rows)
         return SparseTensor(Fs, key, m)

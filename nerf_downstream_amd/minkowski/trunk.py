@@ -22,6 +22,8 @@ from .._lib import BLOCK_DONE_HOOK, STAGE_HOOK, Exec, LevelMaps, Net
 from .._lib import BasicBlock as _BlockDesc
 from .._lib import check, lib
 from . import functional as Fn
+from . import streams
+from ._rt import _f32c, _scratch
 from .coords import CoordinateMapKey
 
 # Data parallelism: a block's collective is issued from inside mink_net_backward, on the weight-gradient stream, at the point behind
@@ -29,7 +31,7 @@ from .coords import CoordinateMapKey
 # a stream of its own for the launches, a FIFTH busy hardware queue (the cliff of DESIGN section 6 at GPU_MAX_HW_QUEUES >= 8).
 _DP_LAUNCH_IN_CALL = os.environ.get("MINK_DP_LAUNCH", "call") != "stream"
 _KEEPALIVE = []  # gradient scratch of the running backward pass: the weight-gradient stream reads it until the final join
-Fn._AFTER_JOIN.append(_KEEPALIVE.clear)
+streams.after_join(_KEEPALIVE.clear)
 _ALIGN = 64  # floats: kNetAlign of csrc/trunk.hip (every block's region starts on a 256-byte boundary)
 # Test seam (tests/test_gpu_layerwise.py): keep the backward pass's gradient arena, the trunk's incoming gradient and the gradient
 # that reaches the stem on the node's `saved` (_Saved.grad_stage).  Off: nothing is kept, allocated or synchronised.
@@ -209,13 +211,13 @@ def _table(m, ts_in, ts_out, ks, transposed=False):
 
 def _branch(dev, cur):
     """The stream of the shortcut branch: its own, or (data parallelism) the weight-gradient stream."""
-    return Fn._side_stream(dev) if Fn.trunk_branch_mode() == "side" else Fn.branch_stream(dev, home=cur)
+    return streams.side_stream(dev) if streams.trunk_branch_mode() == "side" else streams.branch_stream(dev, home=cur)
 
 
 def _exec(plan, cur, br, side, nbytes, device):
-    ws_c = Fn._scratch(nbytes, device, "trunk")
-    ws_b = Fn._scratch(nbytes, device, "trunk", br) if br != cur else ws_c
-    ws_s = Fn._scratch(nbytes, device, "trunk", side) if side != cur else ws_c
+    ws_c = _scratch(nbytes, device, "trunk")
+    ws_b = _scratch(nbytes, device, "trunk", br) if br != cur else ws_c
+    ws_s = _scratch(nbytes, device, "trunk", side) if side != cur else ws_c
     ex = plan.ex
     ex.compute, ex.branch, ex.wgrad = cur.cuda_stream, br.cuda_stream, side.cuda_stream
     ex.ws_compute, ex.ws_branch, ex.ws_wgrad = ws_c.data_ptr(), ws_b.data_ptr(), ws_s.data_ptr()
@@ -254,36 +256,40 @@ _HOOK_STATE = {"installed": False, "cur": None, "fwd_skew": (), "bwd_skew": ()}
 
 def _stage_hook(stage, backward):
     st = _HOOK_STATE
-    if Fn._PREPARE_GATE and Fn._PREPARE_GATE == (int(bool(backward)), stage):
-        # (the next batches' map builds start beside THIS point of a step and not before: functional._PREPARE_GATE)
-        Fn.note_prepare_gate(st["cur"])
+    if streams._PREPARE_GATE and streams._PREPARE_GATE == (int(bool(backward)), stage):
+        # (the next batches' map builds start beside THIS point of a step and not before: streams._PREPARE_GATE)
+        streams.note_prepare_gate(st["cur"])
     if backward:
         if stage < 0:
             Fn.log_phase("stem_backward_begin", st["cur"])
         else:
             for s_ in st["bwd_skew"]:
-                Fn.skew(s_)
+                streams.skew(s_)
     elif stage < 0:
         Fn.log_phase("stem_forward_begin", st["cur"])
     else:
         if stage == 0:
             Fn.log_phase("stem_forward", st["cur"])
         for s_ in st["fwd_skew"]:
-            Fn.skew(s_)
+            streams.skew(s_)
 
 
 _HOOK_C = STAGE_HOOK(_stage_hook)
 
 
+def _hook_wanted():
+    return bool(streams._SKEW) or Fn._PHASE_LOG is not None or bool(streams._PREPARE_GATE)
+
+
 def _arm_hook(L, cur, fwd_skew=(), bwd_skew=(), n_stages=None):
-    if Fn._PREPARE_GATE and n_stages is not None and not _HOOK_STATE.get("gate_checked"):
+    if streams._PREPARE_GATE and n_stages is not None and not _HOOK_STATE.get("gate_checked"):
         _HOOK_STATE["gate_checked"] = True
-        if not -1 <= Fn._PREPARE_GATE[1] < n_stages:  # (a gate point no pass ever reaches: the map builds would simply never be held back)
+        if not -1 <= streams._PREPARE_GATE[1] < n_stages:  # (a gate point no pass ever reaches: the map builds would simply never be held back)
             import warnings
 
-            warnings.warn(f"MINK_PREPARE_GATE names block {Fn._PREPARE_GATE[1]} of a trunk with {n_stages} blocks: the gate never fires "
+            warnings.warn(f"MINK_PREPARE_GATE names block {streams._PREPARE_GATE[1]} of a trunk with {n_stages} blocks: the gate never fires "
                           "and the map builds follow the host as without it")
-    want = bool(Fn._SKEW) or Fn._PHASE_LOG is not None or bool(Fn._PREPARE_GATE)
+    want = _hook_wanted()
     st = _HOOK_STATE
     if want:
         st["cur"], st["fwd_skew"], st["bwd_skew"] = cur, fwd_skew, bwd_skew
@@ -392,7 +398,7 @@ class TrunkFunction(torch.autograd.Function):
         nbr_pool = _table(m, 1, 2, 2)[0]
         i2o = m.in2out[(1, 2)] if m.prepared else m.stride_map(CoordinateMapKey(1), CoordinateMapKey(2))
         n0, n1 = x.shape[0], nbr_pool.shape[0]
-        cur = Fn.current_stream(dev)
+        cur = streams.current_stream(dev)
         br = _branch(dev, cur) if (fork and m.prepared) else cur
         # ---- the level records of this batch (level l = tensor stride 2 << l)
         lv, tables, rows = plan.levels, [], []
@@ -435,7 +441,7 @@ class TrunkFunction(torch.autograd.Function):
         else:
             xb_pre = None
         arena = torch.empty(act_floats, dtype=torch.float32, device=dev)
-        _arm_hook(L, cur, fwd_skew=(br,) if (Fn._SKEW and br != cur) else (), n_stages=len(plan.stages))
+        _arm_hook(L, cur, fwd_skew=(br,) if (streams._SKEW and br != cur) else (), n_stages=len(plan.stages))
         net = plan.net
         check(L.mink_net_forward(ctypes.byref(net), lv, plan.n_levels, arena.data_ptr(), act_floats, exp))
         if Fn._TIMING_MODE == 1:
@@ -454,24 +460,24 @@ class TrunkFunction(torch.autograd.Function):
         L = lib()
         plan, m, saved, params = ctx.plan, ctx.manager, ctx.saved, ctx.params
         dev = g_out.device
-        g_out = Fn._f32c(g_out)
-        sink = Fn._GRAD_SINK
+        g_out = _f32c(g_out)
+        sink = streams.grad_sink()
         x, w0p, arena0, nbr0, nbr_pool, i2o, pad, b16, xb_pre = saved.stem
         arena, rows, tables = saved.arena, saved.rows, saved.tables
-        views = Fn._sink_views(*params) if (sink is not None and pad == 0) else None
+        views = streams.sink_views(*params) if (sink is not None and pad == 0) else None
         # the weight gradients may run on the side stream (joined once, at the end of backward) when nothing consumes a
         # gradient earlier: the gradient buffer's owner (the sink) has them written in place, or autograd merely
         # installs them as .grad
-        overlap = Fn._OVERLAP_WGRAD
+        overlap = streams.wgrad_overlap()
         if overlap and views is None:
             for p in params:
                 if p.grad is not None or p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None):
                     overlap = False
                     break
             overlap = overlap and not torch.is_grad_enabled()
-        cur = Fn.current_stream(dev)
+        cur = streams.current_stream(dev)
         br = _branch(dev, cur) if (ctx.fork and m.prepared) else cur
-        side = Fn._side_stream(dev) if overlap else cur
+        side = streams.side_stream(dev) if overlap else cur
         C0 = w0p.shape[-1]
         n0 = x.shape[0]
         # ---- the level records again (another forward pass of this model may have run in between), with the transposed
@@ -498,7 +504,7 @@ class TrunkFunction(torch.autograd.Function):
         act_floats, grad_floats, ws_net = _sizes(L, plan, rows)
         exp = _exec(plan, cur, br, side, max(ws_net, _stem_ws(L, n0, x.shape[1], C0)), dev)
         if overlap:
-            Fn._defer_join()
+            streams.defer_join()
         # ---- where the parameter gradients go
         grads = [None] * len(params)
         flat = None
@@ -565,7 +571,7 @@ class TrunkFunction(torch.autograd.Function):
             if plan.events is None:
                 plan.events = _Events(L, len(plan.stages))
             evp = plan.events.arr
-        _arm_hook(L, cur, bwd_skew=tuple({br, side} - {cur}) if Fn._SKEW else ())
+        _arm_hook(L, cur, bwd_skew=tuple({br, side} - {cur}) if streams._SKEW else ())
         try:
             check(L.mink_net_backward(ctypes.byref(plan.net), lv, plan.n_levels, arena.data_ptr(), act_floats, g_out.data_ptr(),
                                       g_buf.data_ptr(), grad_floats, exp, evp))

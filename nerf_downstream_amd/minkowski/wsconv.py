@@ -12,7 +12,7 @@ from collections import namedtuple
 import torch
 
 from .._lib import WSCONV_CHUNK, check, lib
-from . import functional as Fn
+from ._rt import _f32c, _ptr, _stream
 
 # The largest tested density at which mink_wsconv_fwd beat mink_conv_gather_gemm on EVERY timed shape (profiles/wsconv_kernels.txt).
 MAX_DENSITY = 0.0
@@ -80,18 +80,18 @@ def wsconv_forward(x, packed, nbr, n_out, bias=None):
     """y [n_out, cout] = the weight-sparse convolution of x [n_in, cin] through the neighbour table nbr [n_out, K] (int32, -1 =
     no neighbour; a transposed convolution passes its transposed table).  Runs under no_grad; the result never requires grad."""
     with torch.no_grad():
-        x = Fn._f32c(x.detach())
+        x = _f32c(x.detach())
         assert x.dim() == 2 and x.shape[1] == packed.cin, (tuple(x.shape), packed.cin)
         assert nbr.dtype == torch.int32 and nbr.dim() == 2 and nbr.shape[0] == n_out and nbr.shape[1] == packed.K, \
             (tuple(nbr.shape), n_out, packed.K)
         nbr = nbr.contiguous()
         if bias is not None:
-            bias = Fn._f32c(bias.detach()).reshape(-1)
+            bias = _f32c(bias.detach()).reshape(-1)
             assert bias.numel() == packed.cout
         y = torch.empty(n_out, packed.cout, dtype=torch.float32, device=x.device)
         check(lib().mink_wsconv_fwd(
             x.data_ptr(), x.shape[0], x.stride(0) if x.shape[0] else packed.cin, packed.cin, nbr.data_ptr(), n_out, packed.K,
             packed.koffs.data_ptr(), len(packed.valid_kernel), packed.rowptr.data_ptr(), packed.cptr.data_ptr(),
-            packed.colidx.data_ptr(), packed.vals.data_ptr(), packed.nnz, y.data_ptr(), packed.cout, packed.cout, Fn._ptr(bias),
-            Fn._stream()))
+            packed.colidx.data_ptr(), packed.vals.data_ptr(), packed.nnz, y.data_ptr(), packed.cout, packed.cout, _ptr(bias),
+            _stream()))
         return y

@@ -130,32 +130,32 @@ class BucketedGradAllReduce:
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._on_grad))
         if self._collect or dev.type == "cuda":
             if dev.type == "cuda":
-                from .minkowski import functional as Fn
+                from .minkowski import streams
 
                 if not self._collect:
-                    Fn.set_grad_sink(self)
+                    streams.set_grad_sink(self)
                 elif os.environ.get("MINK_DP_MULTISTREAM", _multistream_default()) == "0":  # conservative schedule: compute + prepare streams only
-                    Fn.set_wgrad_overlap(False)
-                    Fn.set_branch_fork(False)
+                    streams.set_wgrad_overlap(False)
+                    streams.set_branch_fork(False)
                 else:
                     # a shortcut-branch stream of its own stays off under data parallelism: with the process group's
                     # streams in the picture it gains nothing at six or seven hardware queues and costs a factor at
                     # eight (5.8 ms/step; DESIGN Appendix A).  The native trunk runs the branch on the weight-gradient
                     # stream instead, which is idle in forward and has room in backward: 4.00 -> 3.88 ms with a one-rank
-                    # RCCL group (3.82 without the data-parallel machinery); fp32 math only (Fn.trunk_branch_mode)
-                    Fn.set_branch_fork(False)
-                    Fn.set_trunk_branch_on_side(True)
+                    # RCCL group (3.82 without the data-parallel machinery); fp32 math only (streams.trunk_branch_mode)
+                    streams.set_branch_fork(False)
+                    streams.set_trunk_branch_on_side(True)
                     # convolution weight gradients are written straight into the flat buffer by the
                     # weight-gradient stream (no per-layer accumulate + join on the compute stream), batch-norm
                     # scale / shift gradients by their backward kernel (no accumulate launch per parameter)
-                    Fn.set_grad_sink(self)
+                    streams.set_grad_sink(self)
                     self.defer = os.environ.get("MINK_DP_DEFER_LAUNCH", "1") != "0"
         # RCCL averages inside the collective; gloo (CPU tests, rehearsals) sums and finish() scales
         self._avg = dist.is_initialized() and dist.get_backend(process_group) == "nccl"
         self._op = dist.ReduceOp.AVG if self._avg else dist.ReduceOp.SUM
         self._active = self._collect or dev.type == "cuda"
 
-    # ---- gradient sink protocol (minkowski.functional.set_grad_sink)
+    # ---- gradient sink protocol (minkowski.streams.set_grad_sink)
     def view_for(self, p):
         """The slice of the flat buffer to write the gradient of `p` into -- once per step (a second
         gradient of the same parameter in one step must ADD, which autograd's accumulate does)."""
@@ -222,7 +222,7 @@ class BucketedGradAllReduce:
             # own stream, the shortcut-branch stream, the weight-gradient stream); the collective
             # orders itself after the CURRENT stream only.  Launch it from the weight-gradient
             # stream (after making that one wait for the others): the compute stream is not held up.
-            from .minkowski import functional as Fn
+            from .minkowski import streams
 
             dev = self.flat.device
             if self.stage_stream is not None:
@@ -243,13 +243,13 @@ class BucketedGradAllReduce:
                     self._work.append(dist.all_reduce(self.flat[s:e], op=self._op, group=self.group, async_op=True))
                 return
             cur = torch.cuda.current_stream(dev)
-            side = Fn.side_stream_if_any(dev)
+            side = streams.side_stream_if_any(dev)
             launch_from = side if side is not None else cur
             seen = {launch_from}
-            for st in [self._home, cur] + Fn.compute_streams(dev):
+            for st in [self._home, cur] + streams.compute_streams(dev):
                 if st is not None and st not in seen:
                     seen.add(st)
-                    Fn.stream_wait(launch_from, st)
+                    streams.stream_wait(launch_from, st)
             with torch.cuda.stream(launch_from):
                 self._work.append(dist.all_reduce(self.flat[s:e], op=self._op, group=self.group, async_op=True))
             return
@@ -261,9 +261,9 @@ class BucketedGradAllReduce:
         the weight-gradient stream instead of a stream of its own -- one busy hardware queue fewer (measurement hook for the
         hardware-queue cliff)."""
         if os.environ.get("MINK_DP_LAUNCH_STREAM") == "side":
-            from .minkowski import functional as Fn
+            from .minkowski import streams
 
-            return Fn._side_stream(dev)
+            return streams.side_stream(dev)
         return torch.cuda.Stream(device=dev)
 
     def _on_grad(self, p):
@@ -342,15 +342,15 @@ class BucketedGradAllReduce:
     def zero_grad(self):
         """Gradients accumulate into the flat buffer; clear it with one memset per step."""
         if self.flat.is_cuda:
-            from .minkowski import functional as Fn
+            from .minkowski import streams
 
-            self._home = Fn.current_stream(self.flat.device)
+            self._home = streams.current_stream(self.flat.device)
 
             if self._collect:  # last step's collectives were launched from the side streams (one rank: every gradient
                 # write of the last backward pass was joined by its end-of-backward callback -- no barrier packets here)
-                for st in Fn.compute_streams(self.flat.device):
+                for st in streams.compute_streams(self.flat.device):
                     if st != self._home:
-                        Fn.stream_wait(self._home, st)
+                        streams.stream_wait(self._home, st)
         if self.cleared:  # (FlatSGD.step cleared it behind its update: one pass less over the gradients)
             self.cleared = False
         else:

@@ -67,7 +67,7 @@ def _flat_poison(t, v):
 @pytest.mark.parametrize("value", VALUES)
 def test_relu_masked_gradient_and_add(value):
     """mink_eltwise modes 0 (ReLU), 1 (its gradient: gy where y > 0) and 2 (add) at counts 1, 5, 1027."""
-    from nerf_downstream_amd.minkowski.functional import _eltwise
+    from nerf_downstream_amd.minkowski.eltwise import _eltwise
 
     v = FP.POISONS[value]
     reached = FP.Reached([f"mode {m} count {c}" for m in (0, 1, 2) for c in COUNTS])

@@ -43,7 +43,8 @@ def _dev(z, ldz):
 def _native(zt, labels_t, wt, ignore=IGNORE, g=1.0, backward=True):
     """The C entry points called directly -> dict(loss, lse, pred, hist, stats, dz); dz is NaN-filled before the call."""
     from nerf_downstream_amd._lib import check, lib
-    from nerf_downstream_amd.minkowski.functional import _ptr, _stream, seg_stats
+    from nerf_downstream_amd.minkowski._rt import _ptr, _stream
+    from nerf_downstream_amd.minkowski.head import seg_stats
 
     L = lib()
     n, C = zt.shape

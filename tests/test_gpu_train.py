@@ -57,11 +57,12 @@ def test_training_matches_oracle(tmp_path, oracle_maps):
 def _schedule(model, multi, lazy_fork=False):
     """multi=True: every overlap the training loops use (prepare-ahead on its stream, weight
     gradients on the side stream, shortcut branch on its own stream) with each auxiliary stream
-    DELAYED by ~1 ms per use (Fn._SKEW), so a missing cross-stream dependency changes the result
+    DELAYED by ~1 ms per use (streams._SKEW), so a missing cross-stream dependency changes the result
     instead of passing by luck.  multi=False: everything on one stream."""
     from nerf_downstream_amd.minkowski import functional as Fn
+    from nerf_downstream_amd.minkowski import streams
 
-    Fn._SKEW = 2_000_000 if multi else 0
+    streams._SKEW = 2_000_000 if multi else 0
     Fn.set_wgrad_overlap(multi)
     Fn.set_branch_fork(True)  # (a data-parallel reducer switches both off by default; the tests force them)
     model.prepare_ahead = multi and not lazy_fork
@@ -106,6 +107,7 @@ def test_multi_stream_schedule_is_bitwise_single_stream(grid, sink, math):
 
     from nerf_downstream_amd.co3d_3d.src.models import get_model
     from nerf_downstream_amd.minkowski import functional as Fn
+    from nerf_downstream_amd.minkowski import streams
     from nerf_downstream_amd.parallel import BucketedGradAllReduce
 
     dev = torch.device("cuda", 0)
@@ -128,8 +130,8 @@ def test_multi_stream_schedule_is_bitwise_single_stream(grid, sink, math):
             reducer = BucketedGradAllReduce(m) if sink else None
             _schedule(m, multi, lazy_fork)
             Fn.set_trunk_branch_on_side(mode == "multi-side")
-            Fn._PREPARE_GATE = (0, 0) if mode == "multi-gated" else None
-            Fn._PREPARE_GATE_EVENT.clear()
+            streams._PREPARE_GATE = (0, 0) if mode == "multi-gated" else None
+            streams._PREPARE_GATE_EVENT.clear()
             if mode == "multi-side":
                 Fn.set_branch_fork(False)  # (as a data-parallel reducer leaves it)
                 assert Fn.trunk_branch_mode() == ("side" if math == "fp32" else None)  # (bf16 math: no branch at all under data parallelism)
@@ -140,12 +142,12 @@ def test_multi_stream_schedule_is_bitwise_single_stream(grid, sink, math):
                 assert node.saved[0][7] is True  # bf16 storage taken
             out[mode] = _train_steps(m, batches, labels, 5, reducer)
             if mode == "multi-gated":
-                assert bool(Fn._PREPARE_GATE_EVENT) == native  # (the gate point is a stage of the native trunk)
+                assert bool(streams._PREPARE_GATE_EVENT) == native  # (the gate point is a stage of the native trunk)
             Fn.set_grad_sink(None)
     finally:
-        Fn._SKEW = 0
-        Fn._PREPARE_GATE = None
-        Fn._PREPARE_GATE_EVENT.clear()
+        streams._SKEW = 0
+        streams._PREPARE_GATE = None
+        streams._PREPARE_GATE_EVENT.clear()
         Fn.set_wgrad_overlap(True)
         Fn.set_grad_sink(None)
         Fn.set_trunk_branch_on_side(False)

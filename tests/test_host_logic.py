@@ -51,9 +51,9 @@ def test_descriptor_offsets_are_the_kernel_offsets():
 
 def test_prepare_gate_parsing_and_no_ops():
     from nerf_downstream_amd import memory
-    from nerf_downstream_amd.minkowski import functional as Fn
+    from nerf_downstream_amd.minkowski import streams
 
-    assert Fn._parse_gate("0") is None and Fn._parse_gate("") is None and Fn._parse_gate(None) is None
-    assert Fn._parse_gate("f0") == (0, 0) and Fn._parse_gate("f3") == (0, 3) and Fn._parse_gate("b1") == (1, 1) and Fn._parse_gate("b-1") == (1, -1)
-    Fn.wait_prepare_gate(None)  # nothing recorded, no stream: nothing to wait for
+    assert streams.parse_gate("0") is None and streams.parse_gate("") is None and streams.parse_gate(None) is None
+    assert streams.parse_gate("f0") == (0, 0) and streams.parse_gate("f3") == (0, 3) and streams.parse_gate("b1") == (1, 1) and streams.parse_gate("b-1") == (1, -1)
+    streams.wait_prepare_gate(None)  # nothing recorded, no stream: nothing to wait for
     assert memory.reserve_on(None) == 0 and memory.reserve(torch.device("cpu")) == 0
