@@ -268,8 +268,52 @@ int mink_conv_get_math(void); /* the current mode, unchanged */
 int mink_conv_plan_ksplit(int64_t n_out, int32_t K, int32_t cout, int32_t row_classes);
 /* The same with the reduction width known (what the block sequencer and the Python layer ask): for a class-permuted fp32 mid
  * layer (row_classes != 0) the channel-chunk split of the row-compacted kernel, for an fp32 mid layer its offset split (<= 14
- * slabs), otherwise mink_conv_plan_ksplit's answer.  The workspace is 4 * ksplit * n_out * cout bytes in every case. */
+ * slabs), otherwise mink_conv_plan_ksplit's answer.  The workspace is 4 * ksplit * n_out * cout bytes in every case.
+ * Which kernel a call with that split then reaches: mink_conv_gather_gemm_launch_info below. */
 int mink_conv_plan(int64_t n_rows, int32_t K, int32_t cin, int32_t cout, int32_t row_classes);
+
+/* Which launch a convolution call will make, answered by the planner the launch itself runs (host arithmetic, no GPU).
+ * kernel = MINK_KERNEL_*, targ = the template arguments of the instantiation in the order given with each family, grid /
+ * block / lds_bytes the launch configuration, slabs the slices it writes (row splits for a weight gradient), epilogue =
+ * MINK_EPILOGUE_*.  A call with n_out == 0 launches nothing: all zeros. */
+enum {
+  MINK_KERNEL_GATHER_SCALAR = 1,     /* gather_gemm_kernel {W_T} */
+  MINK_KERNEL_GATHER2 = 2,           /* gather_gemm2_kernel {W_T, STAGE, FLAT, MATH} */
+  MINK_KERNEL_COMPACT = 3,           /* compact_gemm_kernel {W_T, PERM, ABL, MATH, P3, SK} */
+  MINK_KERNEL_WGRAD = 4,             /* wgrad_kernel {G, NARROW, VEC, BUF} */
+  MINK_KERNEL_WGRAD16 = 5,           /* wgrad16_kernel {G} */
+  MINK_KERNEL_WGRAD_STREAM = 6,      /* wgrad_stream_kernel {D, FUSE, FLAT} */
+  MINK_KERNEL_WGRAD_STREAM_BF16 = 7, /* wgrad_stream_bf16_kernel {FUSE, B16} */
+  MINK_KERNEL_WGRAD_STREAM_B16T = 8  /* wgrad_stream_b16t_kernel */
+};
+enum {
+  MINK_EPILOGUE_NONE = 0,
+  MINK_EPILOGUE_COLSUM = 1,              /* un-split launch with statistics: colsum_f32_kernel over the per-tile partials */
+  MINK_EPILOGUE_SPLITK_REDUCE = 2,       /* splitk_reduce_kernel */
+  MINK_EPILOGUE_SPLITK_REDUCE_STATS = 3, /* splitk_reduce_stats_kernel */
+  MINK_EPILOGUE_SLABS = 4,               /* the slabs are left to the caller (mink_conv_gather_gemm_slabs) */
+  MINK_EPILOGUE_SLAB_REDUCE = 5          /* weight gradient: slab_reduce_kernel over the row splits */
+};
+typedef struct {
+  int32_t kernel;
+  int32_t targ[6];
+  int32_t grid[3];
+  int32_t block;
+  int32_t lds_bytes;
+  int32_t slabs;
+  int32_t epilogue;
+} MinkConvLaunchInfo;
+/* mink_conv_gather_gemm / _slabs / _stats described by scalars: row_perm / bias / stats / slabs != 0 where the call passes
+ * that pointer (stats: the three statistics buffers), xw_aligned = x and w on 16 bytes, y_aligned = y, workspace and bias on
+ * 16 bytes.  Refuses what the call would refuse for these scalars, with the same message. */
+int mink_conv_gather_gemm_launch_info(int64_t n_in, int32_t ldx, int32_t cin, int32_t w_transposed, int32_t flip_k, int64_t n_out,
+                                      int32_t K, int32_t row_perm, int64_t n_virtual, int32_t ldy, int32_t cout, int32_t bias,
+                                      int32_t ksplit, int32_t stats, int32_t slabs, int32_t xw_aligned, int32_t y_aligned,
+                                      MinkConvLaunchInfo *info);
+/* mink_conv_wgrad (fuse = 0), mink_conv_wgrad_bn_relu_pool (1; ldy = cout) or mink_conv_wgrad_bn_relu_pool_b16 (2; ldx = 32,
+ * ldy = cout) described the same way; aligned = x and dy on 16 bytes, n_pool the pooled rows of a fused call (else 0). */
+int mink_conv_wgrad_launch_info(int64_t n_in, int32_t ldx, int32_t cin, int32_t ldy, int32_t cout, int64_t n_out, int32_t K,
+                                int32_t fuse, int64_t n_pool, int32_t aligned, MinkConvLaunchInfo *info);
 /* flip_k: bit 0 = read the weights of offset K-1-k for offset k (data gradient of a stride-1 convolution through the
  * forward table); bit 1 = ACCUMULATE, y[row] += result instead of y[row] = result -- for an un-split launch whose
  * row_perm visits every output row at most once (rows it does not visit are left untouched): the data gradient of

@@ -133,7 +133,7 @@ def constants(prefix):
 
 with open(HEADER) as _f:
     SIGNATURES, STRUCTS, _HOOKS, CONSTANTS = parse_header(_f.read())  # name -> (restype, argtypes) | class | hook type | int
-globals().update(STRUCTS)  # KernelMapDesc, ConvLayer, NormLayer, Exec, Stem, BasicBlock, LevelMaps, Net, ClassPartitionDesc, TimingEntry
+globals().update(STRUCTS)  # KernelMapDesc, ConvLayer, NormLayer, Exec, Stem, BasicBlock, LevelMaps, Net, ClassPartitionDesc, TimingEntry, ConvLaunchInfo
 STAGE_HOOK, BLOCK_DONE_HOOK = _HOOKS["MinkStageHook"], _HOOKS["MinkBlockDoneHook"]
 # the input channels mink_wsconv_fwd stages at a time, its output-channel tile, the row count from which a workgroup owns 256 rows
 _WS, _FPS = constants("MINK_WSCONV_"), constants("MINK_FPS_")

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 #include <type_traits>
 #include <vector>
@@ -1588,23 +1589,22 @@ static SkPlan sk_plan(int64_t n_rows, int K, int cout) {
   return {0, 0};
 }
 
-template <bool W_T>
-static int launch_compact_sk(const GemmParams &p, int G, hipStream_t st) {
-  constexpr int smem = compact_smem(64, false, true);
-  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(&compact_gemm_kernel<W_T, 64, false, false, 4, 0, false, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess;
-  MINK_REQUIRE(ok, "gather_gemm: %d bytes of LDS per workgroup refused", smem);
-  compact_gemm_kernel<W_T, 64, false, false, 4, 0, false, true><<<dim3((unsigned)G), 256, smem, st>>>(p);
-  return MINK_OK;
-}
-
-template <bool W_T, bool PERM, int MATH>
-static int launch_compact_p3(const GemmParams &p, dim3 grid, hipStream_t st) {
-  constexpr int smem = compact_smem(64, true);
-  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(&compact_gemm_kernel<W_T, 64, PERM, false, 4, MATH, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess;
-  MINK_REQUIRE(ok, "gather_gemm: %d bytes of LDS per workgroup refused", smem);
-  compact_gemm_kernel<W_T, 64, PERM, false, 4, MATH, true><<<grid, 256, smem, st>>>(p);
+// The one launch of this file's convolution kernels.  A kernel that wants dynamic LDS beyond the default limit is granted it
+// once per (instantiation, size): `granted` only grows, so the measurement launch that gives the two-stage kernel the
+// three-stage footprint does not take it away from a launch that follows.
+template <void (*KERNEL)(GemmParams)>
+static int launch_gemm(const GemmParams &p, dim3 grid, int smem, hipStream_t st) {
+  static std::atomic<int> granted{0};
+  if (smem > granted.load(std::memory_order_acquire)) {
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    if (smem > granted.load(std::memory_order_relaxed)) {
+      MINK_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess,
+                   "gather_gemm: %d bytes of LDS per workgroup refused", smem);
+      granted.store(smem, std::memory_order_release);
+    }
+  }
+  KERNEL<<<grid, 256, smem, st>>>(p);
   return MINK_OK;
 }
 
@@ -1706,32 +1706,92 @@ int mink_conv_plan_ksplit(int64_t n_out, int32_t K, int32_t cout, int32_t row_cl
   return best;
 }
 
+// ---- decide, then do: what a gather-GEMM call looks like (GatherCall), what will be launched for it (GatherPlan), and the one
+// function between them (plan_gather).  The rules below are each written once and shared by plan_gather, mink_conv_plan and
+// mink_conv_gather_gemm_launch_info.
+struct GatherCall {
+  int64_t n_in, n_out, n_virtual;  // n_virtual == n_out without a row permutation
+  int ldx, cin, ldy, cout, K, ksplit;
+  bool w_transposed, flip, accumulate;  // flip_k bit 0, bit 1
+  bool perm;                            // a row permutation is given
+  bool stats, slabs, bias;              // statistics wanted; slabs_out given; a bias is given
+  bool xw_aligned, y_aligned;           // x | w, y | workspace | bias on 16 bytes
+};
+static GatherCall gather_call(int64_t n_in, int ldx, int cin, int w_transposed, int flip_k, int64_t n_out, int K, bool perm, int64_t n_virtual,
+                              int ldy, int cout, int ksplit, bool bias, bool stats, bool slabs, bool xw_aligned, bool y_aligned) {
+  return {n_in, n_out, perm ? n_virtual : n_out, ldx, cin, ldy, cout, K, ksplit, w_transposed != 0, (flip_k & 1) != 0, (flip_k & 2) != 0,
+          perm, stats, slabs, bias, xw_aligned, y_aligned};
+}
+
+// One instantiation as an integer: the switch label of the launch.  t0, t1, t4, t5 are flags, t2 < 32, t3 < 4.
+constexpr int gather_inst(int family, int t0, int t1 = 0, int t2 = 0, int t3 = 0, int t4 = 0, int t5 = 0) {
+  return (((((family * 2 + t0) * 2 + t1) * 32 + t2) * 4 + t3) * 2 + t4) * 2 + t5;
+}
+
+struct GatherPlan {
+  int family;   // MINK_KERNEL_GATHER_SCALAR {W_T} / _GATHER2 {W_T, STAGE, FLAT, MATH} / _COMPACT {W_T, PERM, ABL, MATH, P3, SK}
+  int targ[6];  // ... the template arguments of the instantiation
+  dim3 grid;
+  int lds;         // dynamic LDS bytes (every kernel here runs 256 threads)
+  int kper;        // offsets per slice (class-permuted form: 32-channel chunks per slice)
+  int slabs;       // slices of the launch: zs, or zc for the channel-chunk split
+  int swz_x, swz_y, swz_z;
+  unsigned sk_q, sk_r;
+  int sk_X, sk_S;
+  bool trace;  // the trace buffer is attached
+  bool vec;    // 16-byte rows: what an accumulating launch needs
+  int epilogue;       // MINK_EPILOGUE_*
+  unsigned epi_grid;  // ... its workgroups (the statistics rows of the two statistics epilogues)
+  int epi_lds;
+  unsigned tiles_x;   // row tiles that wrote statistics partials
+  int inst() const { return gather_inst(family, targ[0], targ[1], targ[2], targ[3], targ[4], targ[5]); }
+};
+
 // XCD-aware launch of compact_gemm_kernel for the layers whose weights do not stay in one L2 (4 MB): few row tiles, many
 // (column tile, slice) pairs.  Turns the three-dimensional grid into the padded one-dimensional one the kernel decodes.
-static void compact_swizzle(GemmParams &p, dim3 &grid, int cin, int cout, int K) {
-  p.swz_x = p.swz_y = p.swz_z = 0;
-  p.trace = nullptr;
+static void compact_swizzle(GatherPlan &pl, int cin, int cout, int K) {
+  pl.swz_x = pl.swz_y = pl.swz_z = 0;
   const int64_t wbytes = 4ll * K * cin * cout;
-  const unsigned slices = grid.y * grid.z;
-  if (wbytes <= (2ll << 20) || grid.x > 64 || slices < 16) return;
-  p.swz_x = (int)grid.x, p.swz_y = (int)grid.y, p.swz_z = (int)grid.z;
-  grid = dim3((unsigned)(cdiv(slices, 8) * 8 * grid.x), 1, 1);
+  const unsigned slices = pl.grid.y * pl.grid.z;
+  if (wbytes <= (2ll << 20) || pl.grid.x > 64 || slices < 16) return;
+  pl.swz_x = (int)pl.grid.x, pl.swz_y = (int)pl.grid.y, pl.swz_z = (int)pl.grid.z;
+  pl.grid = dim3((unsigned)(cdiv(slices, 8) * 8 * pl.grid.x), 1, 1);
+}
+
+// A mid layer as both row-compacted forms want it (cin_min: 64, or 32 under set_stagger bit 8 for the class-permuted form).
+static bool mid_shape(int64_t n_rows, int K, int cin, int cin_min, int cout) {
+  return K >= 8 && cin >= cin_min && cin % BK == 0 && cout % BN == 0 && n_rows >= 1;
+}
+// What the launch asks of a mid layer's operands on top of its shape (both row-compacted forms): 16-byte rows, a plain store
+// epilogue, 32-bit gather offsets.
+static bool compact_operands(const GatherCall &c, bool vec) {
+  return vec && !c.accumulate && (c.ldy & 3) == 0 && 4ll * c.K * c.cin * c.cout < (1ll << 31) && 4ll * c.n_in * c.ldx < (1ll << 32) && c.y_aligned;
 }
 
 // compact_gemm_kernel (fp32, no row permutation): 64-row tiles, four workgroups per CU, at most CKP offsets per workgroup.
 // kbench ksweep on the ResNet layers: the best split is the largest one that keeps the launch within two resident rounds
 // (2 x 1024 workgroups), capped at 14 slabs -- l2.conv2 83 us at 7 slabs against 94 at the 3 the older rule picks.
-static bool compact_shape(int64_t n_rows, int K, int cin, int cout, int row_classes) {
-  if (!(g_conv.compact && g_conv.math == 0 && !row_classes && K >= 8 && cin >= 64 && cin % BK == 0 && cout % BN == 0 && n_rows >= 1))
-    return false;
+// (--math bf16 keeps the stride-1 mid layers on the dense bf16 kernel: the row-compacted form with one bf16 MFMA per block and item,
+//  measured round 5, is no faster there -- l1.conv2 57 / 60 us against 56 / 56 forward / data gradient, l3 48 / 58 against 44 / 46)
+static bool compact_mid(const ConvKnobs &kn, int64_t n_rows, int K, int cin, int cout, int row_classes) {
+  return kn.compact && kn.math == 0 && !row_classes && mid_shape(n_rows, K, cin, 64, cout);
+}
+static bool compact_budget(int64_t n_rows, int K, int cout) {
   const int64_t zmin = cdiv(K, CKP);  // the fewest slabs the rulebook allows; beyond the slab budget: the dense kernel, un-split
   return zmin == 1 || zmin * 4 * n_rows * cout <= (128ll << 20);
 }
-static int compact_plan(int64_t n_rows, int K, int cout) {
-  if ((g_conv.compact_p3 & 8) && !(g_conv.stagger & 0xFC) && !g_conv.trace_buf) {  // stream-K (the gate of gather_gemm_impl): the slab count of its plan
-    const SkPlan sk = sk_plan(n_rows, K, cout);
-    if (sk.G) return sk.S;
-  }
+static bool compact_shape(const ConvKnobs &kn, int64_t n_rows, int K, int cin, int cout, int row_classes) {
+  return compact_mid(kn, n_rows, K, cin, cout, row_classes) && compact_budget(n_rows, K, cout);
+}
+// Stream-K (compact_gemm_kernel<.., SK>) for a stride-1 mid layer: its plan where the switches allow the form (the timing-only
+// instantiation and the phase trace have no stream-K twin) and the shape takes it, else G = 0.
+static SkPlan compact_stream_k(const ConvKnobs &kn, int64_t n_rows, int K, int cout) {
+  if (!((kn.compact_p3 & 8) && !(kn.stagger & 0xFC) && !kn.trace_buf)) return {0, 0};
+  return sk_plan(n_rows, K, cout);
+}
+static int compact_plan(const ConvKnobs &kn, int64_t n_rows, int K, int cout) {
+  const SkPlan sk = compact_stream_k(kn, n_rows, K, cout);
+  if (sk.G) return sk.S;  // the slab count of its plan
   constexpr int wg_cap = 2048;
   const int64_t tiles = cdiv(n_rows, 64) * cdiv(cout, BN);
   const int64_t slab_cap = std::max<int64_t>(1, (128ll << 20) / (4 * n_rows * cout));
@@ -1750,14 +1810,15 @@ static int compact_plan(int64_t n_rows, int K, int cout) {
 // compact_gemm_kernel<.., PERM> (fp32, rows grouped by parity class: the data gradient of a strided convolution): the split
 // is over 32-channel chunks; kbench ksweep: the largest that keeps the launch within ~800 workgroups (l2.conv1 three slices 51 us
 // against 57 at two or four, l3.conv1 five 53 against 57 at seven).
-static bool compact_perm_shape(int64_t n_rows, int K, int cin, int cout, int row_classes) {
-  return g_conv.compact && g_conv.compact_perm && (g_conv.math == 0 || (g_conv.math == 1 && g_conv.compact_perm16)) && row_classes && K >= 8 &&
-         cin >= (g_conv.compact_cin32 ? 32 : 64) && cin % BK == 0 && cout % BN == 0 && n_rows >= 1;
+static bool compact_perm_shape(const ConvKnobs &kn, int64_t n_rows, int K, int cin, int cout, int row_classes) {
+  return kn.compact && kn.compact_perm && (kn.math == 0 || (kn.math == 1 && kn.compact_perm16)) && row_classes &&
+         mid_shape(n_rows, K, cin, kn.compact_cin32 ? 32 : 64, cout);
 }
 static int compact_perm_plan(int64_t n_rows, int cin, int cout) {
   constexpr int cap = 850;
   const int ncc = cin / BK;
-  // (n_rows is the padded length of the class permutation: up to 127 padding rows per class, whose tiles exit at once)
+  // (n_rows is the padded length of the class permutation: up to 127 padding rows per class, whose tiles exit at once -- hence
+  //  the tile count taken from n_rows - 512)
   const int64_t tiles = cdiv(std::max<int64_t>(n_rows - 512, 64), 64) * cdiv(cout, BN);
   int best = 1;
   // (up to nine slices where the launch stays under the cap: layer 4 at four scenes per GPU, 5 slices 33 us, 9 slices 27 -- ksplit_sweep, round 5)
@@ -1769,14 +1830,133 @@ static int compact_perm_plan(int64_t n_rows, int cin, int cout) {
 }
 
 int mink_conv_plan(int64_t n_rows, int32_t K, int32_t cin, int32_t cout, int32_t row_classes) {
-  if (compact_perm_shape(n_rows, K, cin, cout, row_classes)) return compact_perm_plan(n_rows, cin, cout);
-  if (compact_shape(n_rows, K, cin, cout, row_classes)) return compact_plan(n_rows, K, cout);
+  if (compact_perm_shape(g_conv, n_rows, K, cin, cout, row_classes)) return compact_perm_plan(n_rows, cin, cout);
+  if (compact_shape(g_conv, n_rows, K, cin, cout, row_classes)) return compact_plan(g_conv, n_rows, K, cout);
   return mink_conv_plan_ksplit(n_rows, K, cout, row_classes);
+}
+
+// The launch one gather-GEMM call makes: kernel instantiation, grid, LDS, split and epilogue, from the call's scalars and the
+// switches alone.  No HIP call, no global: gather_gemm_impl launches what this returns and mink_conv_gather_gemm_launch_info
+// reports it.
+static GatherPlan plan_gather(const GatherCall &c, const ConvKnobs &kn) {
+  GatherPlan pl = {};
+  const bool al = c.xw_aligned && (c.ldx & 3) == 0 && (c.cin & 3) == 0;
+  const bool vec = al && (c.w_transposed ? true : (c.cout & 3) == 0);
+  pl.vec = vec;
+  const bool ablate = (kn.stagger & 0xFC) != 0;  // the timing-only switches of scripts/kbench.py cab / cabp
+  const bool operands = compact_operands(c, vec);
+  // every condition of the row-compacted form (compact_gemm_kernel) except its slice length, which depends on the split below
+  const bool compact_ok = compact_mid(kn, c.n_out, c.K, c.cin, c.cout, c.perm) && operands;
+  pl.kper = (int)cdiv(c.K, c.ksplit);
+  // stream-K: a split stride-1 launch whose caller planned at least the slabs the plan needs.  Only where the launch takes the
+  // row-compacted kernel: any other kernel splits by kper = cdiv(K, ksplit), and the `ksplit` slabs of the stream-K plan would
+  // give it trailing slices that start at or past K.
+  SkPlan sk = {0, 0};
+  if (c.ksplit > 1 && compact_ok && compact_budget(c.n_out, c.K, c.cout)) {
+    sk = compact_stream_k(kn, c.n_out, c.K, c.cout);
+    if (sk.S > c.ksplit) sk = {0, 0};
+  }
+  const int zs = sk.G ? c.ksplit : (int)cdiv(c.K, pl.kper);  // (stream-K: exactly the slabs the caller planned; the spare ones are zeroed)
+  pl.slabs = zs;
+  pl.grid = dim3((unsigned)cdiv(c.n_virtual, BM), (unsigned)cdiv(c.cout, BN), (unsigned)zs);
+  const unsigned col_tiles = pl.grid.y;
+  if (c.perm && compact_perm_shape(kn, c.n_virtual, c.K, c.cin, c.cout, 1) && operands && !c.stats &&
+      (kn.math == 0 || c.w_transposed)) {  // (bf16 math: the data-gradient form only)
+    // class-permuted rows, every live offset of a tile, split over channel chunks (compact_gemm_kernel<.., PERM>)
+    const int ncc = c.cin / BK;
+    pl.kper = (int)cdiv(ncc, c.ksplit);  // channel chunks per slice
+    const int zc = (int)cdiv(ncc, pl.kper);
+    pl.slabs = zc;
+    pl.grid = dim3((unsigned)cdiv(c.n_virtual, 64), col_tiles, (unsigned)zc);
+    compact_swizzle(pl, c.cin, c.cout, c.K);
+    const bool p3 = c.w_transposed && (kn.compact_p3 & 2) && !ablate;
+    const bool abl = c.w_transposed && !p3 && ablate;  // (the instantiation that carries the switches is fp32 under either math)
+    const int math = c.w_transposed && !abl && kn.math == 1;
+    pl.family = MINK_KERNEL_COMPACT;
+    pl.targ[0] = c.w_transposed, pl.targ[1] = 1, pl.targ[2] = abl, pl.targ[3] = math, pl.targ[4] = p3;
+    pl.lds = compact_smem(64, p3);
+    pl.epilogue = zc == 1 ? MINK_EPILOGUE_NONE : c.slabs ? MINK_EPILOGUE_SLABS : MINK_EPILOGUE_SPLITK_REDUCE;
+    pl.epi_grid = (unsigned)cdiv(c.n_out * c.cout, 256);
+    return pl;
+  }
+  pl.tiles_x = pl.grid.x;  // row tiles that write statistics partials
+  if (compact_ok && (pl.kper <= CKP || sk.G)) {  // row-compacted offsets, C tile in LDS (compact_gemm_kernel)
+    pl.grid = dim3((unsigned)cdiv(c.n_out, 64), col_tiles, (unsigned)zs);
+    pl.tiles_x = pl.grid.x;
+    compact_swizzle(pl, c.cin, c.cout, c.K);
+    pl.family = MINK_KERNEL_COMPACT;
+    pl.targ[0] = c.w_transposed;
+    pl.lds = compact_smem(64);
+    // precedence: stream-K, then pipeline bit 2, then bit 0 (so bit 2 outranks bit 0), then the transposed kernel, then the
+    // ablation / trace instantiation
+    if (sk.G) {
+      pl.swz_x = 0;  // (swz_y / swz_z keep what the swizzle planned: the kernel reads only swz_x > 0)
+      const int64_t F = cdiv(c.n_out, 64) * col_tiles * c.K;
+      pl.sk_q = (unsigned)(F / sk.G), pl.sk_r = (unsigned)(F % sk.G), pl.sk_X = (int)cdiv(c.n_out, 64), pl.sk_S = zs;
+      pl.targ[5] = 1;
+      pl.grid = dim3((unsigned)sk.G);
+      pl.lds = compact_smem(64, false, true);
+    } else if (kn.compact_p3 & 4) {  // (measurement only: two stages at three workgroups per CU)
+      pl.lds = compact_smem(64, true);
+    } else if ((kn.compact_p3 & 1) && !ablate) {
+      pl.targ[4] = 1;
+      pl.lds = compact_smem(64, true);
+    } else if (!c.w_transposed && (ablate || kn.trace_buf)) {  // (a transposed launch with ablation bits set takes the plain kernel)
+      // timing-only switches (kbench cab) / phase trace (kbench ctrace): the instantiation that carries them
+      pl.targ[2] = 1;
+      pl.trace = kn.trace_buf && (int64_t)pl.grid.x * pl.grid.y * pl.grid.z <= kn.trace_cap;
+    }
+  } else if (vec) {
+    // the flat path addresses x rows with a 24-bit multiply: the table must not name a row >= 2^24 - 1 (n_in bounds it)
+    const bool flat = c.cin == 28 && zs == 1 && !c.flip && !c.w_transposed && !c.perm && kn.flat && c.ldx <= 32 &&
+                      4ll * c.K * c.cin * c.cout < (1ll << 31) && c.n_in < (1 << 24) - 1;
+    pl.family = MINK_KERNEL_GATHER2;
+    pl.targ[0] = c.w_transposed, pl.targ[1] = c.perm, pl.targ[2] = flat ? 28 : 0, pl.targ[3] = kn.math == 1 ? 1 : kn.math == 3 ? 3 : 0;
+  } else {  // operands that are not 16-byte rows (e.g. 27 channels)
+    pl.family = MINK_KERNEL_GATHER_SCALAR;
+    pl.targ[0] = c.w_transposed;
+  }
+  const bool want_stats = c.stats && !c.perm && !c.w_transposed;
+  if (want_stats && zs == 1 && vec) {  // conv epilogue -> per-tile partials -> stage 2
+    pl.epilogue = MINK_EPILOGUE_COLSUM;
+    pl.epi_grid = (unsigned)std::min<int64_t>(512, cdiv((int64_t)pl.tiles_x, 8));  // >= 8 tiles per partial row: a latency-bound pass
+  } else if (zs > 1 && c.slabs) {
+    pl.epilogue = MINK_EPILOGUE_SLABS;
+  } else if (zs > 1 && want_stats && (c.cout & 3) == 0 && c.cout <= 1024 && (c.ldy & 3) == 0 && c.y_aligned) {
+    const int rlanes = 256 / (c.cout >> 2);
+    pl.epilogue = MINK_EPILOGUE_SPLITK_REDUCE_STATS;
+    pl.epi_grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(512, cdiv(c.n_out, (int64_t)rlanes * 4)));  // one four-row trip per thread
+    pl.epi_lds = rlanes * 2 * c.cout * (int)sizeof(double);
+  } else if (zs > 1) {
+    pl.epilogue = MINK_EPILOGUE_SPLITK_REDUCE;
+    pl.epi_grid = (unsigned)cdiv(c.n_out * c.cout, 256);
+  }
+  return pl;
+}
+
+// What mink_conv_gather_gemm* and the launch query share: the refusals a call's scalars decide, the plan, and the two refusals
+// that need the plan -- all before any launch.  pl.family == 0: no rows, nothing to launch.
+static int gather_decide(const GatherCall &c, const ConvKnobs &kn, GatherPlan &pl) {
+  pl = GatherPlan{};
+  MINK_REQUIRE(c.K >= 1 && c.K <= KMAX, "gather_gemm: kernel volume %d unsupported", c.K);
+  MINK_REQUIRE(c.cin >= 1 && c.cout >= 1 && c.ldx >= c.cin && c.ldy >= c.cout && c.n_out >= 0 && c.n_in >= 0, "gather_gemm: bad shape");
+  MINK_REQUIRE(c.ksplit >= 1 && c.ksplit <= std::max(c.K, c.cin / BK), "gather_gemm: bad ksplit %d", c.ksplit);  // (offsets, or channel chunks: compact_perm_plan)
+  MINK_REQUIRE(c.n_out * (int64_t)c.K < (1ll << 31), "gather_gemm: table too large");
+  if (c.n_out == 0) return MINK_OK;
+  MINK_REQUIRE(c.n_virtual >= c.n_out || c.accumulate, "gather_gemm: the row permutation must cover every output row");
+  pl = plan_gather(c, kn);
+  MINK_REQUIRE(!c.accumulate || (pl.slabs == 1 && pl.vec && !c.stats),
+               "gather_gemm: accumulation needs an un-split launch of the pipelined kernel (16-byte aligned operands)");
+  const bool perm_form = pl.family == MINK_KERNEL_COMPACT && pl.targ[1];  // (never refused a bias here: kept)
+  MINK_REQUIRE(pl.epilogue != MINK_EPILOGUE_SLABS || perm_form || (!c.bias && !c.stats),
+               "gather_gemm: slabs are left to the caller only without bias and statistics");
+  return MINK_OK;
 }
 
 // stats_out (optional): double [<= 512][2][cout] column (sum, sum of squares) partials of y for the
 // batch norm that follows; *stats_rows receives how many partial rows were written (0: this
 // launch configuration cannot produce them and the caller reduces y itself).
+// Validate, plan (plan_gather), launch, epilogue.
 static int gather_gemm_impl(const float *x, int64_t n_in, int32_t ldx, int32_t cin, const float *w, int32_t w_transposed,
                             int32_t flip_k, const int32_t *nbr, int64_t n_out, int32_t K, const int32_t *row_perm,
                             int64_t n_virtual, float *y, int32_t ldy, int32_t cout, const float *bias, int32_t ksplit,
@@ -1786,10 +1966,12 @@ static int gather_gemm_impl(const float *x, int64_t n_in, int32_t ldx, int32_t c
   // caller's next kernel -- mink_bn_small_fwd); *slabs_out = 1 means y holds the result as usual
   if (slabs_out) *slabs_out = 1;
   if (stats_rows) *stats_rows = 0;
-  MINK_REQUIRE(K >= 1 && K <= KMAX, "gather_gemm: kernel volume %d unsupported", K);
-  MINK_REQUIRE(cin >= 1 && cout >= 1 && ldx >= cin && ldy >= cout && n_out >= 0 && n_in >= 0, "gather_gemm: bad shape");
-  MINK_REQUIRE(ksplit >= 1 && ksplit <= std::max(K, cin / BK), "gather_gemm: bad ksplit %d", ksplit);  // (offsets, or channel chunks: compact_perm_plan)
-  MINK_REQUIRE(n_out * (int64_t)K < (1ll << 31), "gather_gemm: table too large");
+  const GatherCall c = gather_call(n_in, ldx, cin, w_transposed, flip_k, n_out, K, row_perm != nullptr, n_virtual, ldy, cout, ksplit,
+                                   bias != nullptr, stats_out && stats_rows && stats_ws, slabs_out != nullptr,
+                                   (((uintptr_t)x | (uintptr_t)w) & 15) == 0,
+                                   (((uintptr_t)y | (uintptr_t)workspace | (uintptr_t)bias) & 15) == 0);
+  GatherPlan pl;
+  if (const int rc = gather_decide(c, g_conv, pl)) return rc;
   if (n_out == 0) return MINK_OK;
   MINK_REQUIRE(x && w && nbr && y, "gather_gemm: NULL pointer");
   MINK_REQUIRE(ksplit == 1 || workspace, "gather_gemm: split-K needs a workspace");
@@ -1799,175 +1981,87 @@ static int gather_gemm_impl(const float *x, int64_t n_in, int32_t ldx, int32_t c
   MINK_REQUIRE(!stats_ws || stats_ws_bytes >= mink_conv_stats_workspace_bytes(n_out, cout),
                "gather_gemm: statistics workspace of %lld bytes, %lld needed", (long long)stats_ws_bytes,
                (long long)mink_conv_stats_workspace_bytes(n_out, cout));
-  if (!row_perm) n_virtual = n_out;
-  MINK_REQUIRE(n_virtual >= n_out || (flip_k & 2), "gather_gemm: the row permutation must cover every output row");
-  ScopedTimer timer(w_transposed ? 1 : 0, n_in, n_out, K, cin, cout, nbr, (hipStream_t)stream);
-  GemmParams p;
-  p.row_perm = row_perm, p.n_virtual = n_virtual;
-  p.stagger = g_conv.stagger;
-  p.x = x, p.w = w, p.nbr = nbr, p.bias = bias, p.y = y, p.ws = workspace;
-  p.n_out = n_out, p.ldx = ldx, p.cin = cin, p.ldy = ldy, p.cout = cout, p.K = K, p.flip_k = flip_k & 1;
-  p.accumulate = (flip_k >> 1) & 1;
-  p.kper = (int)cdiv(K, ksplit);
-  p.stats = nullptr;
-  p.swz_x = p.swz_y = p.swz_z = 0;
-  p.trace = nullptr;
-  p.sk_q = p.sk_r = 0, p.sk_X = 0, p.sk_S = 0;
-  const bool al = (((uintptr_t)x | (uintptr_t)w) & 15) == 0 && (ldx & 3) == 0 && (cin & 3) == 0;
-  const bool vec = al && (w_transposed ? true : (cout & 3) == 0);
-  // every condition of the row-compacted form (compact_gemm_kernel) except its slice length, which depends on the split below
-  const bool compact_ok = g_conv.compact && g_conv.math == 0 && vec && !row_perm && !p.accumulate && K >= 8 && cin >= 64 && cin % BK == 0 &&
-                          cout % BN == 0 && (ldy & 3) == 0 && 4ll * K * cin * cout < (1ll << 31) && 4ll * n_in * ldx < (1ll << 32) &&
-                          (((uintptr_t)y | (uintptr_t)workspace | (uintptr_t)bias) & 15) == 0;
-  // stream-K (compact_gemm_kernel<.., SK>): a split stride-1 launch whose caller planned at least the slabs the plan needs.  Only
-  // where the launch takes the row-compacted kernel: any other kernel splits by kper = cdiv(K, ksplit), and the `ksplit` slabs of
-  // the stream-K plan would give it trailing slices that start at or past K.
-  SkPlan sk = {0, 0};
-  if ((g_conv.compact_p3 & 8) && ksplit > 1 && compact_ok && !(g_conv.stagger & 0xFC) && !g_conv.trace_buf && compact_shape(n_out, K, cin, cout, 0)) {
-    sk = sk_plan(n_out, K, cout);
-    if (sk.G == 0 || sk.S > ksplit) sk = {0, 0};
-  }
-  const int zs = sk.G ? ksplit : (int)cdiv(K, p.kper);  // (stream-K: exactly the slabs the caller planned; the spare ones are zeroed)
-  const dim3 grid((unsigned)cdiv(n_virtual, BM), (unsigned)cdiv(cout, BN), (unsigned)zs);
+
   hipStream_t st = (hipStream_t)stream;
-  MINK_REQUIRE(!p.accumulate || (zs == 1 && vec && !stats_out),
-               "gather_gemm: accumulation needs an un-split launch of the pipelined kernel (16-byte aligned operands)");
-  flip_k &= 1;
-  const bool want_stats = stats_out && stats_rows && stats_ws && !row_perm && !w_transposed;
-  const bool stats_direct = want_stats && zs == 1 && vec;  // conv epilogue -> per-tile partials -> stage 2
-  const bool stats_split = want_stats && zs > 1 && (cout & 3) == 0 && cout <= 1024 && (ldy & 3) == 0 &&
-                           (((uintptr_t)y | (uintptr_t)workspace | (uintptr_t)bias) & 15) == 0;
-  if (compact_perm_shape(n_virtual, K, cin, cout, row_perm != nullptr) && row_perm && vec && !p.accumulate && !stats_out &&
-      (g_conv.math == 0 || w_transposed) &&  // (bf16 math: the data-gradient form only)
-      (ldy & 3) == 0 && 4ll * K * cin * cout < (1ll << 31) && 4ll * n_in * ldx < (1ll << 32) &&  // (32-bit gather offsets)
-      (((uintptr_t)y | (uintptr_t)workspace | (uintptr_t)bias) & 15) == 0) {
-    // class-permuted rows, every live offset of a tile, split over channel chunks (compact_gemm_kernel<.., PERM>)
-    constexpr int CMT = 64;
-    constexpr int smem = compact_smem(CMT);
-    static const bool attr_ok = [] {
-      return hipFuncSetAttribute(reinterpret_cast<const void *>(&compact_gemm_kernel<false, CMT, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess &&
-             hipFuncSetAttribute(reinterpret_cast<const void *>(&compact_gemm_kernel<true, CMT, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess;
-    }();
-    MINK_REQUIRE(attr_ok, "gather_gemm: %d bytes of LDS per workgroup refused", smem);
-    const int ncc = cin / BK;
-    p.kper = (int)cdiv(ncc, ksplit);  // channel chunks per slice
-    const int zc = (int)cdiv(ncc, p.kper);
-    dim3 cgrid((unsigned)cdiv(n_virtual, CMT), grid.y, (unsigned)zc);
-    compact_swizzle(p, cgrid, cin, cout, K);
-    if (w_transposed && (g_conv.compact_p3 & 2) && !(g_conv.stagger & 0xFC)) {
-      const int rc = g_conv.math == 1 ? launch_compact_p3<true, true, 1>(p, cgrid, st) : launch_compact_p3<true, true, 0>(p, cgrid, st);
-      if (rc) return rc;
-    } else if (w_transposed && (g_conv.stagger & 0xFC)) {  // timing-only switches (kbench cabp): the instantiation that carries them
-      static const bool abl_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(&compact_gemm_kernel<true, CMT, true, true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess;
-      MINK_REQUIRE(abl_ok, "gather_gemm: %d bytes of LDS per workgroup refused", smem);
-      compact_gemm_kernel<true, CMT, true, true><<<cgrid, 256, smem, st>>>(p);
-    } else if (w_transposed && g_conv.math == 1) {
-      static const bool a16_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(&compact_gemm_kernel<true, CMT, true, false, 4, 1>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess;
-      MINK_REQUIRE(a16_ok, "gather_gemm: %d bytes of LDS per workgroup refused", smem);
-      compact_gemm_kernel<true, CMT, true, false, 4, 1><<<cgrid, 256, smem, st>>>(p);
-    } else if (w_transposed) compact_gemm_kernel<true, CMT, true><<<cgrid, 256, smem, st>>>(p);
-    else compact_gemm_kernel<false, CMT, true><<<cgrid, 256, smem, st>>>(p);
-    MINK_CHECK_LAUNCH();
-    if (zc > 1 && slabs_out) {
-      *slabs_out = zc;
-    } else if (zc > 1) {
-      splitk_reduce_kernel<<<dim3((unsigned)cdiv(n_out * cout, 256)), 256, 0, st>>>(workspace, n_out, cout, zc, bias, y, ldy);
-      MINK_CHECK_LAUNCH();
-    }
-    return MINK_OK;
+  ScopedTimer timer(w_transposed ? 1 : 0, n_in, n_out, K, cin, cout, nbr, st);
+  GemmParams p;
+  p.x = x, p.w = w, p.nbr = nbr, p.bias = bias, p.y = y, p.ws = workspace;
+  p.row_perm = row_perm, p.n_out = n_out, p.n_virtual = c.n_virtual;
+  p.ldx = ldx, p.cin = cin, p.ldy = ldy, p.cout = cout, p.K = K, p.flip_k = c.flip, p.kper = pl.kper, p.stagger = g_conv.stagger;
+  p.accumulate = c.accumulate;
+  p.stats = pl.epilogue == MINK_EPILOGUE_COLSUM ? (float *)stats_ws : nullptr;
+  p.swz_x = pl.swz_x, p.swz_y = pl.swz_y, p.swz_z = pl.swz_z;
+  p.trace = pl.trace ? g_conv.trace_buf : nullptr;
+  p.sk_q = pl.sk_q, p.sk_r = pl.sk_r, p.sk_X = pl.sk_X, p.sk_S = pl.sk_S;
+  int rc;
+  switch (pl.inst()) {
+    // gather_gemm_kernel<W_T, VEC = false>
+    case gather_inst(MINK_KERNEL_GATHER_SCALAR, 0): rc = launch_gemm<gather_gemm_kernel<false, false>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER_SCALAR, 1): rc = launch_gemm<gather_gemm_kernel<true, false>>(p, pl.grid, pl.lds, st); break;
+    // gather_gemm2_kernel<W_T, STAGE, FLAT, MATH>
+    case gather_inst(MINK_KERNEL_GATHER2, 0, 0, 0, 0): rc = launch_gemm<gather_gemm2_kernel<false, false, 0, 0>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 0, 0, 0, 1): rc = launch_gemm<gather_gemm2_kernel<false, false, 0, 1>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 0, 0, 0, 3): rc = launch_gemm<gather_gemm2_kernel<false, false, 0, 3>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 0, 0, 28, 0): rc = launch_gemm<gather_gemm2_kernel<false, false, 28, 0>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 0, 0, 28, 1): rc = launch_gemm<gather_gemm2_kernel<false, false, 28, 1>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 0, 0, 28, 3): rc = launch_gemm<gather_gemm2_kernel<false, false, 28, 3>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 0, 1, 0, 0): rc = launch_gemm<gather_gemm2_kernel<false, true, 0, 0>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 0, 1, 0, 1): rc = launch_gemm<gather_gemm2_kernel<false, true, 0, 1>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 0, 1, 0, 3): rc = launch_gemm<gather_gemm2_kernel<false, true, 0, 3>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 1, 0, 0, 0): rc = launch_gemm<gather_gemm2_kernel<true, false, 0, 0>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 1, 0, 0, 1): rc = launch_gemm<gather_gemm2_kernel<true, false, 0, 1>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 1, 0, 0, 3): rc = launch_gemm<gather_gemm2_kernel<true, false, 0, 3>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 1, 1, 0, 0): rc = launch_gemm<gather_gemm2_kernel<true, true, 0, 0>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 1, 1, 0, 1): rc = launch_gemm<gather_gemm2_kernel<true, true, 0, 1>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_GATHER2, 1, 1, 0, 3): rc = launch_gemm<gather_gemm2_kernel<true, true, 0, 3>>(p, pl.grid, pl.lds, st); break;
+    // compact_gemm_kernel<W_T, 64, PERM, ABL, 4, MATH, P3, SK>
+    case gather_inst(MINK_KERNEL_COMPACT, 0, 0, 0, 0, 0, 0): rc = launch_gemm<compact_gemm_kernel<false, 64>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_COMPACT, 1, 0, 0, 0, 0, 0): rc = launch_gemm<compact_gemm_kernel<true, 64>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_COMPACT, 0, 0, 1, 0, 0, 0): rc = launch_gemm<compact_gemm_kernel<false, 64, false, true>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_COMPACT, 0, 0, 0, 0, 1, 0): rc = launch_gemm<compact_gemm_kernel<false, 64, false, false, 4, 0, true>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_COMPACT, 1, 0, 0, 0, 1, 0): rc = launch_gemm<compact_gemm_kernel<true, 64, false, false, 4, 0, true>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_COMPACT, 0, 0, 0, 0, 0, 1): rc = launch_gemm<compact_gemm_kernel<false, 64, false, false, 4, 0, false, true>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_COMPACT, 1, 0, 0, 0, 0, 1): rc = launch_gemm<compact_gemm_kernel<true, 64, false, false, 4, 0, false, true>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_COMPACT, 0, 1, 0, 0, 0, 0): rc = launch_gemm<compact_gemm_kernel<false, 64, true>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_COMPACT, 1, 1, 0, 0, 0, 0): rc = launch_gemm<compact_gemm_kernel<true, 64, true>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_COMPACT, 1, 1, 1, 0, 0, 0): rc = launch_gemm<compact_gemm_kernel<true, 64, true, true>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_COMPACT, 1, 1, 0, 1, 0, 0): rc = launch_gemm<compact_gemm_kernel<true, 64, true, false, 4, 1>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_COMPACT, 1, 1, 0, 0, 1, 0): rc = launch_gemm<compact_gemm_kernel<true, 64, true, false, 4, 0, true>>(p, pl.grid, pl.lds, st); break;
+    case gather_inst(MINK_KERNEL_COMPACT, 1, 1, 0, 1, 1, 0): rc = launch_gemm<compact_gemm_kernel<true, 64, true, false, 4, 1, true>>(p, pl.grid, pl.lds, st); break;
+    default: MINK_REQUIRE(false, "gather_gemm: no kernel for the planned instantiation (family %d)", pl.family);
   }
-  if (stats_direct) p.stats = (float *)stats_ws;
-  unsigned tiles_x = grid.x;  // row tiles that wrote statistics partials
-  // (--math bf16 keeps the stride-1 mid layers on the dense bf16 kernel: the row-compacted form with one bf16 MFMA per block and item,
-  //  measured round 5, is no faster there -- l1.conv2 57 / 60 us against 56 / 56 forward / data gradient, l3 48 / 58 against 44 / 46)
-  const bool compact = compact_ok && (p.kper <= CKP || sk.G);
-  if (compact) {  // row-compacted offsets, C tile in LDS (compact_gemm_kernel)
-    constexpr int CMT = 64;
-    constexpr int smem = compact_smem(CMT);
-    static const bool attr_ok = [] {
-      return hipFuncSetAttribute(reinterpret_cast<const void *>(&compact_gemm_kernel<false, CMT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 smem) == hipSuccess &&
-             hipFuncSetAttribute(reinterpret_cast<const void *>(&compact_gemm_kernel<true, CMT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 smem) == hipSuccess;
-    }();
-    MINK_REQUIRE(attr_ok, "gather_gemm: %d bytes of LDS per workgroup refused", smem);
-    dim3 cgrid((unsigned)cdiv(n_out, CMT), grid.y, grid.z);
-    tiles_x = cgrid.x;
-    compact_swizzle(p, cgrid, cin, cout, K);
-    if (sk.G) {
-      p.swz_x = 0;
-      const int64_t F = (int64_t)cdiv(n_out, CMT) * grid.y * K;
-      p.sk_q = (unsigned)(F / sk.G), p.sk_r = (unsigned)(F % sk.G), p.sk_X = (int)cdiv(n_out, CMT), p.sk_S = zs;
-      const int rc = w_transposed ? launch_compact_sk<true>(p, sk.G, st) : launch_compact_sk<false>(p, sk.G, st);
-      if (rc) return rc;
-    } else if (g_conv.compact_p3 & 4) {  // (measurement only: two stages at three workgroups per CU)
-      constexpr int smem3 = compact_smem(CMT, true);
-      static const bool ok3 = hipFuncSetAttribute(reinterpret_cast<const void *>(&compact_gemm_kernel<false, CMT>), hipFuncAttributeMaxDynamicSharedMemorySize, smem3) == hipSuccess &&
-                              hipFuncSetAttribute(reinterpret_cast<const void *>(&compact_gemm_kernel<true, CMT>), hipFuncAttributeMaxDynamicSharedMemorySize, smem3) == hipSuccess;
-      MINK_REQUIRE(ok3, "gather_gemm: %d bytes of LDS per workgroup refused", smem3);
-      if (w_transposed) compact_gemm_kernel<true, CMT><<<cgrid, 256, smem3, st>>>(p);
-      else compact_gemm_kernel<false, CMT><<<cgrid, 256, smem3, st>>>(p);
-    } else
-    if ((g_conv.compact_p3 & 1) && !(g_conv.stagger & 0xFC)) {
-      const int rc = w_transposed ? launch_compact_p3<true, false, 0>(p, cgrid, st) : launch_compact_p3<false, false, 0>(p, cgrid, st);
-      if (rc) return rc;
-    } else if (w_transposed) compact_gemm_kernel<true, CMT><<<cgrid, 256, smem, st>>>(p);
-    else if ((g_conv.stagger & 0xFC) || g_conv.trace_buf) {  // timing-only switches (kbench cab) / phase trace (kbench ctrace): the instantiation that carries them
-      p.trace = (int64_t)cgrid.x * cgrid.y * cgrid.z <= g_conv.trace_cap ? g_conv.trace_buf : nullptr;
-      static const bool abl_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(&compact_gemm_kernel<false, CMT, false, true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess;
-      MINK_REQUIRE(abl_ok, "gather_gemm: %d bytes of LDS per workgroup refused", smem);
-      compact_gemm_kernel<false, CMT, false, true><<<cgrid, 256, smem, st>>>(p);
-    } else compact_gemm_kernel<false, CMT><<<cgrid, 256, smem, st>>>(p);
-  } else {
-    const bool stage = row_perm != nullptr;
-    if (vec) {
-      // the flat path addresses x rows with a 24-bit multiply: the table must not name a row >= 2^24 - 1 (n_in bounds it)
-      const bool flat = cin == 28 && zs == 1 && !flip_k && !w_transposed && !stage && g_conv.flat && ldx <= 32 &&
-                        4ll * K * cin * cout < (1ll << 31) && n_in < (1 << 24) - 1;
-#define MINK_LAUNCH_GG2(M)                                                                          \
-  do {                                                                                              \
-    if (w_transposed && stage) gather_gemm2_kernel<true, true, 0, M><<<grid, 256, 0, st>>>(p);      \
-    else if (w_transposed) gather_gemm2_kernel<true, false, 0, M><<<grid, 256, 0, st>>>(p);         \
-    else if (stage) gather_gemm2_kernel<false, true, 0, M><<<grid, 256, 0, st>>>(p);                \
-    else if (flat) gather_gemm2_kernel<false, false, 28, M><<<grid, 256, 0, st>>>(p);               \
-    else gather_gemm2_kernel<false, false, 0, M><<<grid, 256, 0, st>>>(p);                          \
-  } while (0)
-      if (g_conv.math == 1) MINK_LAUNCH_GG2(1);
-      else if (g_conv.math == 3) MINK_LAUNCH_GG2(3);
-      else MINK_LAUNCH_GG2(0);
-#undef MINK_LAUNCH_GG2
-    } else if (w_transposed) gather_gemm_kernel<true, false><<<grid, 256, 0, st>>>(p);  // operands that are not 16-byte rows (e.g. 27 channels)
-    else gather_gemm_kernel<false, false><<<grid, 256, 0, st>>>(p);
+  if (rc) return rc;
+  MINK_CHECK_LAUNCH();
+  switch (pl.epilogue) {
+    case MINK_EPILOGUE_COLSUM:
+      colsum_f32_kernel<<<dim3(pl.epi_grid), 256, 0, st>>>((const float *)stats_ws, (int64_t)pl.tiles_x, 2 * cout, stats_out);
+      *stats_rows = (int32_t)pl.epi_grid;
+      break;
+    case MINK_EPILOGUE_SPLITK_REDUCE_STATS:
+      splitk_reduce_stats_kernel<<<dim3(pl.epi_grid), 256, (size_t)pl.epi_lds, st>>>(workspace, n_out, cout, pl.slabs, bias, y, ldy, stats_out);
+      *stats_rows = (int32_t)pl.epi_grid;
+      break;
+    case MINK_EPILOGUE_SPLITK_REDUCE:
+      splitk_reduce_kernel<<<dim3(pl.epi_grid), 256, 0, st>>>(workspace, n_out, cout, pl.slabs, bias, y, ldy);
+      break;
+    case MINK_EPILOGUE_SLABS: *slabs_out = pl.slabs; return MINK_OK;
+    default: return MINK_OK;
   }
   MINK_CHECK_LAUNCH();
-  if (stats_direct) {
-    const int rows = (int)std::min<int64_t>(512, cdiv((int64_t)tiles_x, 8));  // >= 8 tiles per partial row: a latency-bound pass
-    colsum_f32_kernel<<<dim3((unsigned)rows), 256, 0, st>>>((const float *)stats_ws, (int64_t)tiles_x, 2 * cout, stats_out);
-    MINK_CHECK_LAUNCH();
-    *stats_rows = rows;
-  }
-  if (zs > 1 && slabs_out) {
-    MINK_REQUIRE(!bias && !stats_out, "gather_gemm: slabs are left to the caller only without bias and statistics");
-    *slabs_out = zs;
-    return MINK_OK;
-  }
-  if (zs > 1 && stats_split) {
-    const int tpr = cout >> 2, rlanes = 256 / tpr;
-    const int rows = (int)std::max<int64_t>(1, std::min<int64_t>(512, cdiv(n_out, (int64_t)rlanes * 4)));  // one four-row trip per thread
-    splitk_reduce_stats_kernel<<<dim3((unsigned)rows), 256, (size_t)rlanes * 2 * cout * sizeof(double), st>>>(
-        workspace, n_out, cout, zs, bias, y, ldy, stats_out);
-    MINK_CHECK_LAUNCH();
-    *stats_rows = rows;
-  } else if (zs > 1) {
-    splitk_reduce_kernel<<<dim3((unsigned)cdiv(n_out * cout, 256)), 256, 0, st>>>(workspace, n_out, cout, zs, bias, y,
-                                                                                  ldy);
-    MINK_CHECK_LAUNCH();
-  }
+  return MINK_OK;
+}
+
+int mink_conv_gather_gemm_launch_info(int64_t n_in, int32_t ldx, int32_t cin, int32_t w_transposed, int32_t flip_k, int64_t n_out,
+                                      int32_t K, int32_t row_perm, int64_t n_virtual, int32_t ldy, int32_t cout, int32_t bias,
+                                      int32_t ksplit, int32_t stats, int32_t slabs, int32_t xw_aligned, int32_t y_aligned,
+                                      MinkConvLaunchInfo *info) {
+  MINK_REQUIRE(info, "gather_gemm_launch_info: NULL info");
+  *info = MinkConvLaunchInfo{};
+  const GatherCall c = gather_call(n_in, ldx, cin, w_transposed, flip_k, n_out, K, row_perm != 0, n_virtual, ldy, cout, ksplit, bias != 0,
+                                   stats != 0, slabs != 0, xw_aligned != 0, y_aligned != 0);
+  GatherPlan pl;
+  if (const int rc = gather_decide(c, g_conv, pl)) return rc;
+  if (pl.family) *info = launch_info(pl.family, pl.targ, 6, pl.grid, pl.lds, pl.slabs, pl.epilogue);
   return MINK_OK;
 }
 

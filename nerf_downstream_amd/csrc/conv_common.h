@@ -1,7 +1,6 @@
 // What the two halves of the sparse convolution share: conv.hip (forward / data gradient, the switch setters, the
 // timing registry) and conv_wgrad.hip (weight gradient).  Only what BOTH reference lives here; a helper that one
-// half uses stays in that half.  (ld4_mask and raw_load_f32 have no caller in either: they stay beside the siblings
-// their comments refer to.)
+// half uses stays in that half.
 #pragma once
 #include "common.h"
 
@@ -33,20 +32,10 @@ __device__ __forceinline__ float4 ld4_sel(const float *base, int64_t off, bool o
   return ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// Same, but the zeroing is a bit mask on the loaded words: the optimiser cannot fold it back
-// into an exec-masked (branchy) load, so the load stays an unconditional, schedulable instruction.
-__device__ __forceinline__ float4 ld4_mask(const float *base, int64_t off, bool ok) {
-  const uint4 u = *reinterpret_cast<const uint4 *>(base + (ok ? off : 0));
-  const unsigned m = ok ? 0xFFFFFFFFu : 0u;
-  return make_float4(__uint_as_float(u.x & m), __uint_as_float(u.y & m), __uint_as_float(u.z & m),
-                     __uint_as_float(u.w & m));
-}
-
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using i32x4 = __attribute__((ext_vector_type(4))) int;
 // raw buffer loads with a per-lane byte offset (VGPR) and a per-item byte offset (SGPR): no address arithmetic per load
 __device__ f32x4 raw_load_v4(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
-__device__ float raw_load_f32(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.f32");
 __device__ int raw_load_i32(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.i32");
 // descriptor of a raw buffer of `bytes` bytes: a load at byte offset >= bytes touches no memory and returns 0
 __device__ __forceinline__ i32x4 raw_rsrc(const void *ptr, unsigned bytes) {
@@ -62,11 +51,10 @@ __device__ __forceinline__ unsigned pack_bf16(float a, float b) {
   return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)a) |
          ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)b) << 16);
 }
-using bf16x8v = __attribute__((ext_vector_type(8))) __bf16;
 
-__device__ __forceinline__ bf16x8v pack_bf16x8(const float (&v)[8]) {
+__device__ __forceinline__ bf16x8 pack_bf16x8(const float (&v)[8]) {
   const uint4 u = make_uint4(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7]));
-  return __builtin_bit_cast(bf16x8v, u);
+  return __builtin_bit_cast(bf16x8, u);
 }
 
 // ---- the switches of both dispatchers and planners: one object per library, defined in conv.hip.  mink_conv_set_stagger
@@ -89,6 +77,16 @@ struct ConvKnobs {
   int wgrad_xcd = 1;  // streaming wgrad: groups of a row split share an XCD (stream_slot; bit 29: plain order)
 };
 extern ConvKnobs g_conv;
+
+// a planner's answer in the words of mink_conv_*_launch_info (workgroups are 256 threads in both halves)
+inline MinkConvLaunchInfo launch_info(int kernel, const int *targ, int ntarg, dim3 grid, int lds, int slabs, int epilogue) {
+  MinkConvLaunchInfo info = {};
+  info.kernel = kernel;
+  for (int i = 0; i < ntarg; ++i) info.targ[i] = targ[i];
+  info.grid[0] = (int32_t)grid.x, info.grid[1] = (int32_t)grid.y, info.grid[2] = (int32_t)grid.z;
+  info.block = 256, info.lds_bytes = lds, info.slabs = slabs, info.epilogue = epilogue;
+  return info;
+}
 
 // ---- kernel timing registry (measurement only; see mink_conv_timing in the header): state and bodies in conv.hip
 struct TimedLaunch {

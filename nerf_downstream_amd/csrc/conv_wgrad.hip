@@ -7,10 +7,10 @@ namespace mink {
 
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ bf16x8v pack_bits_bf16x8(const float (&v)[8]) {  // registers that already hold bf16 bits in their low halves
+__device__ __forceinline__ bf16x8 pack_bits_bf16x8(const float (&v)[8]) {  // registers that already hold bf16 bits in their low halves
   auto lo = [&](int i) { return __float_as_uint(v[i]); };
   const uint4 u = make_uint4(lo(0) | (lo(1) << 16), lo(2) | (lo(3) << 16), lo(4) | (lo(5) << 16), lo(6) | (lo(7) << 16));
-  return __builtin_bit_cast(bf16x8v, u);
+  return __builtin_bit_cast(bf16x8, u);
 }
 
 // ------------------------------------------------------------------------------ wgrad
@@ -703,7 +703,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_stream_bf16_kernel(WgradParams p
     // (nine is a multiple of three: every register index is a compile-time constant without unrolling over blocks)
     for (int q = 0; q < nq; ++q) {
       const int slot = q & 1;
-      const bf16x8v bfrag = b_fragment(q);
+      const bf16x8 bfrag = b_fragment(q);
 #pragma unroll
       for (int sb = 0; sb < G; ++sb) {
         const int cur = sb % 3, nxt = (sb + 1) % 3;
@@ -860,7 +860,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_stream_b16t_kernel(WgradParams p
       }
       *reinterpret_cast<uint4 *>(sBw + st_off) = make_uint4(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7]));
       const uint2 b_lo = lds_tr16(sBw + tr_off), b_hi = lds_tr16(sBw + tr_off + 128);
-      return __builtin_bit_cast(bf16x8v, make_uint4(b_lo.x, b_lo.y, b_hi.x, b_hi.y));
+      return __builtin_bit_cast(bf16x8, make_uint4(b_lo.x, b_lo.y, b_hi.x, b_hi.y));
     };
     // ---- prologue
     load_table(0);
@@ -876,7 +876,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_stream_b16t_kernel(WgradParams p
       spread();  // entries of block q + 1
       {
         unsigned short *sAw = &sA[wave * 3][0];
-        const bf16x8v bfrag = b_operand(q);
+        const bf16x8 bfrag = b_operand(q);
         load_b(q + 1);  // (its parents arrived one block ago)
         load_par(q + 2);
         load_table(q + 2);
@@ -887,7 +887,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_stream_b16t_kernel(WgradParams p
         uint2 a_lo = lds_tr16(sAw + tr_off), a_hi = lds_tr16(sAw + tr_off + 128);
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-          const bf16x8v afrag = __builtin_bit_cast(bf16x8v, make_uint4(a_lo.x, a_lo.y, a_hi.x, a_hi.y));
+          const bf16x8 afrag = __builtin_bit_cast(bf16x8, make_uint4(a_lo.x, a_lo.y, a_hi.x, a_hi.y));
           if (g + 1 < G) {
             unsigned short *slot = sAw + ((g + 1) % 3) * 512;
             *reinterpret_cast<u32x4v *>(slot + st_off) = ga[g + 1];
@@ -947,13 +947,33 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float *__restric
   if (lane == 0 && i < count) out[i] = (s_part[0][o] + s_part[1][o]) + (s_part[2][o] + s_part[3][o]);
 }
 
+// ---- decide, then do: what a weight-gradient call looks like, and the launch wgrad_plan makes of it.  wgrad_impl launches the
+// plan; mink_conv_wgrad_workspace_bytes, mink_conv_wgrad_bn_relu_pool_supported and mink_conv_wgrad_launch_info read it.
+struct WgradCall {
+  int64_t n_in, n_out, n_pool;
+  int ldx, cin, ldy, cout, K;
+  int fuse;      // 0 plain, 1 dy recomputed from pool(relu(bn(y))), 2 the same with x and y stored as bf16
+  bool aligned;  // x | dy on 16 bytes
+};
+
 struct WgradPlan {
   int G, ngroups, nsplit;
   int64_t rows_per_split;
+  int family;   // MINK_KERNEL_WGRAD {G, NARROW, VEC, BUF} / _WGRAD16 {G} / _WGRAD_STREAM {D, FUSE, FLAT} / _WGRAD_STREAM_BF16 {FUSE, B16} / _WGRAD_STREAM_B16T
+  int targ[4];  // ... the template arguments of the instantiation
+  dim3 grid;
+  int ct_tiles;
+  unsigned x_bytes, dy_bytes, nbr_bytes;
+  bool buf_ok;       // every byte size < 2^31 and n_in < 2^24: 32-bit offset arithmetic is safe
+  bool flat;         // flattened (offset, channel) tiling of the streaming fp32 kernel
+  bool streaming;    // the stem shape on the streaming kernels (what a fused call needs)
+  bool bf16_stream;  // ... on the bf16 matrix cores (what a fused call with bf16 storage needs)
 };
 
-static WgradPlan wgrad_plan(int64_t n_out, int K, int cin, int cout) {
-  WgradPlan pl;
+static WgradPlan wgrad_plan(const WgradCall &c, const ConvKnobs &kn) {
+  WgradPlan pl = {};
+  const int64_t n_out = c.n_out;
+  const int K = c.K, cin = c.cin, cout = c.cout;
   const int64_t tiles = cdiv(cin, WT) * cdiv(cout, WT);
   const int64_t row_tiles = cdiv(n_out, WROWS);
   // offsets per workgroup: share the dy tile between as many offsets as parallelism allows
@@ -965,12 +985,12 @@ static WgradPlan wgrad_plan(int64_t n_out, int K, int cin, int cout) {
   // (layer1, one 64 x 64 weight tile and many rows: alone, one offset per workgroup and three times the workgroups win --
   //  kbench wsweep: l1.conv2 G1 z64 89 us against G3 z48 101 -- but inside a step, beside the data-gradient chain, the 1296
   //  workgroups take 208 us where the 432 take 125: the plan stays)
-  if (g_conv.wgrad_force & 0xF) pl.G = (g_conv.wgrad_force & 0xF) == 1 ? 1 : (g_conv.wgrad_force & 0xF) == 2 ? 3 : 9;  // tuning hook
+  if (kn.wgrad_force & 0xF) pl.G = (kn.wgrad_force & 0xF) == 1 ? 1 : (kn.wgrad_force & 0xF) == 2 ? 3 : 9;  // tuning hook
   pl.ngroups = (int)cdiv(K, pl.G);
   const int64_t xy = tiles * pl.ngroups;
   int64_t z = cdiv(512, xy);  // ~2 resident workgroups per CU: fewer partial slabs to write and reduce
   if (tiny) z = 1;
-  if (g_conv.wgrad_force >> 4) z = g_conv.wgrad_force >> 4;
+  if (kn.wgrad_force >> 4) z = kn.wgrad_force >> 4;
   if (z > row_tiles) z = row_tiles;
   if (z < 1) z = 1;
   const bool streamed = pl.G == 9 && K == 27 && cin <= 32 && tiles == 1 && z >= 16;  // see stream_slot: splits in eights
@@ -979,7 +999,50 @@ static WgradPlan wgrad_plan(int64_t n_out, int K, int cin, int cout) {
   pl.nsplit = (int)cdiv(n_out, pl.rows_per_split);
   if (pl.nsplit < 1) pl.nsplit = 1;
   if (streamed) pl.nsplit = (int)align_up(pl.nsplit, 8);  // trailing splits may be empty: they store zero slabs
+
+  // ---- the kernel and its launch configuration
+  pl.ct_tiles = (int)cdiv(cout, WT);
+  pl.grid = dim3((unsigned)(pl.ngroups * cdiv(cin, WT) * pl.ct_tiles), (unsigned)pl.nsplit);
+  const int esz = c.fuse == 2 ? 2 : 4;
+  const int64_t xb = esz * c.n_in * c.ldx, db = esz * n_out * c.ldy, nb = 4 * n_out * K;
+  pl.x_bytes = (unsigned)xb, pl.dy_bytes = (unsigned)db, pl.nbr_bytes = (unsigned)nb;
+  pl.buf_ok = xb < (1ll << 31) && db < (1ll << 31) && nb < (1ll << 31) && c.n_in < (1 << 24) && xb <= 0xFFFFFFll * 4 * c.ldx;
+  const bool stream_ok = K == 27 && cin <= 32 && c.ldx < 64 && c.n_in < (1 << 24) && 4 * c.n_in * c.ldx < (1ll << 31) &&
+                         4 * n_out * c.ldy < (1ll << 31) && 4 * n_out * K < (1ll << 31);  // what the buffer-offset arithmetic assumes
+  pl.streaming = pl.G == 9 && stream_ok && kn.wgrad_stream;
+  const bool bf16_math = kn.math == 1 && !kn.wgrad_bf16_off;
+  pl.bf16_stream = bf16_math && pl.streaming;
+  // flattened (offset, channel) tiling: 24 instead of 27 tiles when the axis fits three groups of 256 rows and the
+  // padded channels are worth saving; ldx <= 32 keeps "no neighbour" + "past the axis" inside 32-bit offset arithmetic
+  pl.flat = K * cin <= 768 && K * cin > 512 && c.ldx <= 32 && cin >= 16;
+  const bool strides4 = ((c.ldx | c.ldy) & 3) == 0;
+  if (c.fuse == 2 && cout == 64 && c.ldx == 32 && !kn.b16t_off) {  // (set_stagger bit 11: the 2-byte-gather kernel, A/B tests)
+    pl.family = MINK_KERNEL_WGRAD_STREAM_B16T;
+  } else if (c.fuse == 2 || pl.bf16_stream) {  // (four row pairs in flight: 2 / 6 / 8 measured, DESIGN appendix)
+    pl.family = MINK_KERNEL_WGRAD_STREAM_BF16;
+    pl.targ[0] = c.fuse != 0, pl.targ[1] = c.fuse == 2;
+  } else if (c.fuse || pl.streaming) {  // (a fused call the streaming kernels do not take is refused: wgrad_plan_check)
+    pl.family = MINK_KERNEL_WGRAD_STREAM;
+    pl.targ[0] = 4, pl.targ[1] = c.fuse != 0, pl.targ[2] = pl.flat;
+  } else if (bf16_math && pl.G != 9 && cin % WT == 0 && cout % WT == 0 && pl.buf_ok && c.aligned && strides4) {
+    // --math bf16: the mid-layer weight gradients on the bf16 matrix cores too (wgrad16_kernel)
+    pl.family = MINK_KERNEL_WGRAD16;
+    pl.targ[0] = pl.G == 3 ? 3 : 1;
+  } else {
+    const bool vec = c.aligned && strides4 && ((cin | cout) & 3) == 0;
+    pl.family = MINK_KERNEL_WGRAD;
+    pl.targ[0] = pl.G, pl.targ[1] = cin <= 32, pl.targ[2] = vec, pl.targ[3] = vec && pl.buf_ok;
+  }
   return pl;
+}
+
+// The refusals of a fused call, which need the plan; before any launch.
+static int wgrad_plan_check(const WgradCall &c, const WgradPlan &pl) {
+  if (!c.fuse) return MINK_OK;
+  MINK_REQUIRE(pl.streaming && 4 * c.n_pool * c.ldy < (1ll << 31),
+               "wgrad_bn_relu_pool: shape not supported by the streaming kernel (ask mink_conv_wgrad_bn_relu_pool_supported)");
+  MINK_REQUIRE(c.fuse != 2 || pl.bf16_stream, "wgrad_bn_relu_pool_b16: needs bf16 math (mink_conv_set_math(1))");
+  return MINK_OK;
 }
 
 // ------------------------------------------------ tiled weight gradient on the bf16 matrix cores (mid layers, --math bf16)
@@ -1100,8 +1163,8 @@ __global__ __launch_bounds__(256, 4) void wgrad16_kernel(WgradParams p) {
           const int r_lo = s_row[g * LL + pa], r_hi = s_row[g * LL + pa + 4];
           const uint2 a_lo = lds_tr16(sX + img(pa, 32 * wm + tr_c)), a_hi = lds_tr16(sX + img(pa + 4, 32 * wm + tr_c));
           const uint2 b_lo = lds_tr16(sD + img(r_lo, 32 * wn + tr_c)), b_hi = lds_tr16(sD + img(r_hi, 32 * wn + tr_c));
-          acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8v, make_uint4(a_lo.x, a_lo.y, a_hi.x, a_hi.y)),
-                                                           __builtin_bit_cast(bf16x8v, make_uint4(b_lo.x, b_lo.y, b_hi.x, b_hi.y)), acc[g], 0, 0, 0);
+          acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, make_uint4(a_lo.x, a_lo.y, a_hi.x, a_hi.y)),
+                                                           __builtin_bit_cast(bf16x8, make_uint4(b_lo.x, b_lo.y, b_hi.x, b_hi.y)), acc[g], 0, 0, 0);
         }
         if (g + 1 < ng) {
           __syncthreads();  // everyone done reading sX
@@ -1128,17 +1191,16 @@ __global__ __launch_bounds__(256, 4) void wgrad16_kernel(WgradParams p) {
 }
 
 template <int G>
-static void launch_wgrad(const WgradParams &p, dim3 grid, hipStream_t st) {
-  const bool vec = (((uintptr_t)p.x | (uintptr_t)p.dy) & 15) == 0 && ((p.ldx | p.ldy | p.cin | p.cout) & 3) == 0;
-  constexpr int buf_on = 1;
-  if (p.cin <= 32) {
-    if (vec && p.buf_ok && buf_on) wgrad_kernel<G, true, true, true><<<grid, 256, 0, st>>>(p);
-    else if (vec) wgrad_kernel<G, true, true><<<grid, 256, 0, st>>>(p);
-    else wgrad_kernel<G, true, false><<<grid, 256, 0, st>>>(p);
+static void launch_wgrad(const WgradParams &p, const WgradPlan &pl, hipStream_t st) {  // wgrad_kernel<G, NARROW, VEC, BUF> of the plan
+  const bool narrow = pl.targ[1], vec = pl.targ[2], buf = pl.targ[3];
+  if (narrow) {
+    if (buf) wgrad_kernel<G, true, true, true><<<pl.grid, 256, 0, st>>>(p);
+    else if (vec) wgrad_kernel<G, true, true><<<pl.grid, 256, 0, st>>>(p);
+    else wgrad_kernel<G, true, false><<<pl.grid, 256, 0, st>>>(p);
   } else {
-    if (vec && p.buf_ok && buf_on) wgrad_kernel<G, false, true, true><<<grid, 256, 0, st>>>(p);
-    else if (vec) wgrad_kernel<G, false, true><<<grid, 256, 0, st>>>(p);
-    else wgrad_kernel<G, false, false><<<grid, 256, 0, st>>>(p);
+    if (buf) wgrad_kernel<G, false, true, true><<<pl.grid, 256, 0, st>>>(p);
+    else if (vec) wgrad_kernel<G, false, true><<<pl.grid, 256, 0, st>>>(p);
+    else wgrad_kernel<G, false, false><<<pl.grid, 256, 0, st>>>(p);
   }
 }
 
@@ -1148,8 +1210,14 @@ using namespace mink;
 
 extern "C" {
 
+static WgradCall wgrad_call(int64_t n_in, int32_t ldx, int32_t cin, int32_t ldy, int32_t cout, int64_t n_out, int32_t K) {
+  WgradCall c = {};
+  c.n_in = n_in, c.n_out = n_out, c.ldx = ldx, c.cin = cin, c.ldy = ldy, c.cout = cout, c.K = K;
+  return c;
+}
+
 int64_t mink_conv_wgrad_workspace_bytes(int64_t n_out, int32_t K, int32_t cin, int32_t cout) {
-  const WgradPlan pl = wgrad_plan(n_out, K, cin, cout);
+  const WgradPlan pl = wgrad_plan(wgrad_call(0, cin, cin, cout, cout, n_out, K), g_conv);  // (the split needs only these four)
   return pl.nsplit > 1 ? (int64_t)pl.nsplit * K * cin * cout * 4 : 0;
 }
 
@@ -1161,16 +1229,20 @@ struct WgradFuse {  // dy = input gradient of pool(relu(bn(y))): see mink_conv_w
   int b16;  // x and y are bf16 (x: [n_in][ldx] with ldx = 32; y: [n_out][cout]) -- bf16 storage of the full-resolution stage
 };
 
-static bool wgrad_stream_ok(int64_t n_in, int32_t ldx, int32_t cin, int32_t ldy, int32_t cout, int64_t n_out, int32_t K) {
-  return K == 27 && cin <= 32 && ldx < 64 && n_in < (1 << 24) && 4 * n_in * ldx < (1ll << 31) &&
-         4 * n_out * ldy < (1ll << 31) && 4 * n_out * K < (1ll << 31);  // what the buffer-offset arithmetic assumes
+static int wgrad_shape_check(const WgradCall &c) {
+  MINK_REQUIRE(c.K >= 1 && c.K <= KMAX && c.cin >= 1 && c.cout >= 1 && c.ldx >= c.cin && c.ldy >= c.cout && c.n_out >= 0 && c.n_in >= 0,
+               "wgrad: bad shape");
+  return MINK_OK;
 }
 
+// Validate, plan (wgrad_plan), launch, reduce the row splits.
 static int wgrad_impl(const float *x, int64_t n_in, int32_t ldx, int32_t cin, const float *dy, int32_t ldy, int32_t cout,
                       const int32_t *nbr, int64_t n_out, int32_t K, float *dw, void *workspace, int64_t workspace_bytes,
                       const WgradFuse *fuse, void *stream) {
-  MINK_REQUIRE(K >= 1 && K <= KMAX && cin >= 1 && cout >= 1 && ldx >= cin && ldy >= cout && n_out >= 0 && n_in >= 0,
-               "wgrad: bad shape");
+  WgradCall c = wgrad_call(n_in, ldx, cin, ldy, cout, n_out, K);
+  c.fuse = !fuse ? 0 : fuse->b16 ? 2 : 1, c.n_pool = fuse ? fuse->n_pool : 0;
+  c.aligned = (((uintptr_t)x | (uintptr_t)dy) & 15) == 0;
+  if (const int rc = wgrad_shape_check(c)) return rc;
   MINK_REQUIRE(dw, "wgrad: NULL dw");
   hipStream_t st = (hipStream_t)stream;
   if (n_out == 0) {
@@ -1178,53 +1250,50 @@ static int wgrad_impl(const float *x, int64_t n_in, int32_t ldx, int32_t cin, co
     return MINK_OK;
   }
   MINK_REQUIRE(x && dy && nbr, "wgrad: NULL pointer");
-  ScopedTimer timer(2, n_in, n_out, K, cin, cout, nbr, st);
-  const WgradPlan pl = wgrad_plan(n_out, K, cin, cout);
+  const WgradPlan pl = wgrad_plan(c, g_conv);
   MINK_REQUIRE(pl.nsplit == 1 || workspace, "wgrad: needs a workspace");
   // (the slab count comes from the plan, which tuning knobs can change between the caller's size query and this launch)
   MINK_REQUIRE(pl.nsplit == 1 || workspace_bytes >= (int64_t)pl.nsplit * K * cin * cout * 4,
                "wgrad: workspace of %lld bytes, %lld needed for the %d row splits of this plan", (long long)workspace_bytes,
                (long long)((int64_t)pl.nsplit * K * cin * cout * 4), pl.nsplit);
+  if (const int rc = wgrad_plan_check(c, pl)) return rc;
+  ScopedTimer timer(2, n_in, n_out, K, cin, cout, nbr, st);
   WgradParams p;
   p.x = x, p.dy = dy, p.nbr = nbr, p.out = pl.nsplit > 1 ? (float *)workspace : dw;
   p.n_out = n_out, p.rows_per_split = pl.rows_per_split, p.ldx = ldx, p.cin = cin, p.ldy = ldy, p.cout = cout, p.K = K;
-  p.ct_tiles = (int)cdiv(cout, WT);
+  p.ct_tiles = pl.ct_tiles;
   p.ngroups = pl.ngroups;
   p.ablate = g_conv.stagger | (g_conv.wgrad_xcd ? 0 : 4096);
-  const dim3 grid((unsigned)(pl.ngroups * cdiv(cin, WT) * p.ct_tiles), (unsigned)pl.nsplit);
-  const int esz = fuse && fuse->b16 ? 2 : 4;
-  const int64_t xb = esz * n_in * ldx, db = esz * n_out * ldy, nb = 4 * n_out * K;
-  p.x_bytes = (unsigned)xb, p.dy_bytes = (unsigned)db, p.nbr_bytes = (unsigned)nb;
-  p.buf_ok = xb < (1ll << 31) && db < (1ll << 31) && nb < (1ll << 31) && n_in < (1 << 24) && xb <= 0xFFFFFFll * 4 * ldx;
-  const bool stream_ok = wgrad_stream_ok(n_in, ldx, cin, ldy, cout, n_out, K);
-  const bool bf16_stream = g_conv.math == 1 && !g_conv.wgrad_bf16_off && pl.G == 9 && stream_ok && g_conv.wgrad_stream;
-  // flattened (offset, channel) tiling: 24 instead of 27 tiles when the axis fits three groups of 256 rows and the
-  // padded channels are worth saving; ldx <= 32 keeps "no neighbour" + "past the axis" inside 32-bit offset arithmetic
-  constexpr int flat_on = 1;
-  const bool flat = flat_on && K * cin <= 768 && K * cin > 512 && ldx <= 32 && cin >= 16;
+  p.x_bytes = pl.x_bytes, p.dy_bytes = pl.dy_bytes, p.nbr_bytes = pl.nbr_bytes;
+  p.buf_ok = pl.buf_ok;
   if (fuse) {
-    MINK_REQUIRE(pl.G == 9 && stream_ok && g_conv.wgrad_stream && 4 * fuse->n_pool * ldy < (1ll << 31),
-                 "wgrad_bn_relu_pool: shape not supported by the streaming kernel (ask mink_conv_wgrad_bn_relu_pool_supported)");
     p.dyp = fuse->dyp, p.in2out = fuse->in2out, p.mean = fuse->mean, p.invstd = fuse->invstd, p.gamma = fuse->gamma;
     p.beta = fuse->beta, p.dgamma = fuse->dgamma, p.dbeta = fuse->dbeta, p.inv_n = 1.f / (float)n_out;
     p.dyp_bytes = (unsigned)(4 * fuse->n_pool * ldy), p.i2o_bytes = (unsigned)(4 * n_out);
-    MINK_REQUIRE(!fuse->b16 || bf16_stream, "wgrad_bn_relu_pool_b16: needs bf16 math (mink_conv_set_math(1))");
-    if (fuse->b16 && cout == 64 && ldx == 32 && !g_conv.b16t_off) wgrad_stream_b16t_kernel<<<grid, 256, 0, st>>>(p);  // (bit 11: the 2-byte-gather kernel, A/B tests)
-    else if (fuse->b16) wgrad_stream_bf16_kernel<true, true><<<grid, 256, 0, st>>>(p);
-    else if (bf16_stream) wgrad_stream_bf16_kernel<true><<<grid, 256, 0, st>>>(p);  // (four row pairs in flight: 2 / 6 / 8 measured, DESIGN appendix)
-    else if (flat) wgrad_stream_kernel<4, true, true><<<grid, 256, 0, st>>>(p);
-    else wgrad_stream_kernel<4, true><<<grid, 256, 0, st>>>(p);
-  } else if (bf16_stream) wgrad_stream_bf16_kernel<false><<<grid, 256, 0, st>>>(p);
-  else if (pl.G == 9 && stream_ok && g_conv.wgrad_stream && flat) wgrad_stream_kernel<4, false, true><<<grid, 256, 0, st>>>(p);
-  else if (pl.G == 9 && stream_ok && g_conv.wgrad_stream) wgrad_stream_kernel<4><<<grid, 256, 0, st>>>(p);
-  else if (g_conv.math == 1 && !g_conv.wgrad_bf16_off && pl.G != 9 && cin % WT == 0 && cout % WT == 0 && p.buf_ok &&
-           (((uintptr_t)x | (uintptr_t)dy) & 15) == 0 && ((ldx | ldy) & 3) == 0) {
-    // --math bf16: the mid-layer weight gradients on the bf16 matrix cores too (wgrad16_kernel)
-    if (pl.G == 3) wgrad16_kernel<3><<<grid, 256, 0, st>>>(p);
-    else wgrad16_kernel<1><<<grid, 256, 0, st>>>(p);
-  } else if (pl.G == 9) launch_wgrad<9>(p, grid, st);
-  else if (pl.G == 3) launch_wgrad<3>(p, grid, st);
-  else launch_wgrad<1>(p, grid, st);
+  }
+  const bool t0 = pl.targ[0], t1 = pl.targ[1], t2 = pl.targ[2];
+  switch (pl.family) {
+    case MINK_KERNEL_WGRAD_STREAM_B16T: wgrad_stream_b16t_kernel<<<pl.grid, 256, 0, st>>>(p); break;
+    case MINK_KERNEL_WGRAD_STREAM_BF16:  // <FUSE, B16>
+      if (t1) wgrad_stream_bf16_kernel<true, true><<<pl.grid, 256, 0, st>>>(p);
+      else if (t0) wgrad_stream_bf16_kernel<true><<<pl.grid, 256, 0, st>>>(p);
+      else wgrad_stream_bf16_kernel<false><<<pl.grid, 256, 0, st>>>(p);
+      break;
+    case MINK_KERNEL_WGRAD_STREAM:  // <4, FUSE, FLAT>
+      if (t1 && t2) wgrad_stream_kernel<4, true, true><<<pl.grid, 256, 0, st>>>(p);
+      else if (t1) wgrad_stream_kernel<4, true><<<pl.grid, 256, 0, st>>>(p);
+      else if (t2) wgrad_stream_kernel<4, false, true><<<pl.grid, 256, 0, st>>>(p);
+      else wgrad_stream_kernel<4><<<pl.grid, 256, 0, st>>>(p);
+      break;
+    case MINK_KERNEL_WGRAD16:
+      if (pl.targ[0] == 3) wgrad16_kernel<3><<<pl.grid, 256, 0, st>>>(p);
+      else wgrad16_kernel<1><<<pl.grid, 256, 0, st>>>(p);
+      break;
+    default:
+      if (pl.G == 9) launch_wgrad<9>(p, pl, st);
+      else if (pl.G == 3) launch_wgrad<3>(p, pl, st);
+      else launch_wgrad<1>(p, pl, st);
+  }
   MINK_CHECK_LAUNCH();
   if (pl.nsplit > 1) {
     const int64_t count = (int64_t)K * cin * cout;
@@ -1242,7 +1311,22 @@ int mink_conv_wgrad(const float *x, int64_t n_in, int32_t ldx, int32_t cin, cons
 
 int mink_conv_wgrad_bn_relu_pool_supported(int64_t n_in, int32_t ldx, int32_t cin, int64_t n_out, int32_t K, int32_t cout) {
   if (n_out <= 0) return 0;
-  return wgrad_plan(n_out, K, cin, cout).G == 9 && wgrad_stream_ok(n_in, ldx, cin, cout, cout, n_out, K) && g_conv.wgrad_stream;
+  return wgrad_plan(wgrad_call(n_in, ldx, cin, cout, cout, n_out, K), g_conv).streaming;
+}
+
+int mink_conv_wgrad_launch_info(int64_t n_in, int32_t ldx, int32_t cin, int32_t ldy, int32_t cout, int64_t n_out, int32_t K,
+                                int32_t fuse, int64_t n_pool, int32_t aligned, MinkConvLaunchInfo *info) {
+  MINK_REQUIRE(info, "wgrad_launch_info: NULL info");
+  *info = MinkConvLaunchInfo{};
+  MINK_REQUIRE(fuse >= 0 && fuse <= 2, "wgrad_launch_info: fuse %d", fuse);
+  WgradCall c = wgrad_call(n_in, ldx, cin, ldy, cout, n_out, K);
+  c.fuse = fuse, c.n_pool = n_pool, c.aligned = aligned != 0;
+  if (const int rc = wgrad_shape_check(c)) return rc;
+  if (n_out == 0) return MINK_OK;  // (a memset, no kernel: the info stays zero)
+  const WgradPlan pl = wgrad_plan(c, g_conv);
+  if (const int rc = wgrad_plan_check(c, pl)) return rc;
+  *info = launch_info(pl.family, pl.targ, 4, pl.grid, 0, pl.nsplit, pl.nsplit > 1 ? MINK_EPILOGUE_SLAB_REDUCE : MINK_EPILOGUE_NONE);
+  return MINK_OK;
 }
 
 int mink_conv_wgrad_bn_relu_pool(const float *x, int64_t n_in, int32_t ldx, int32_t cin, const float *y, int32_t cout,

@@ -8,6 +8,7 @@ the next, so each operator is held to what its own kernel test holds it to.
 
 Tables are the trunk's: nbr[n_out, K] = input row of output row o at offset k, or -1 (oracle/maps.py kernel_map_table);
 weights are [K, cin, cout]."""
+import ctypes
 from dataclasses import dataclass
 
 import torch
@@ -86,19 +87,21 @@ class ConvForm:
 
 
 def conv_form(op, K, cin, cout, math, n_out=1, ldx=None, ldy=None, row_perm=False, aligned=True, ksplit=1, force_g=0, perm16=True,
-              shortcut_dense=True):
-    """The launch form and operand rounding of one convolution operator, restated from the dispatchers gather_gemm_impl
-    (csrc/conv.hip) and wgrad_impl (csrc/conv_wgrad.hip) with the default switches and within their 32-bit
-    size limits.
+              shortcut_dense=True, flip=False, acc=False):
+    """The launch form and operand rounding of one convolution operator, restated from the planners plan_gather
+    (csrc/conv.hip) and wgrad_plan (csrc/conv_wgrad.hip) with the default switches and within their 32-bit
+    size limits; tests/test_conv_dispatch_cpu.py holds the restatement to the library's own answer.
 
     op: "fwd" (W as [K][cin][cout]), "dgrad" (the same-map or class-permuted gather with the forward weights read transposed),
     "wgrad" (dW[k] = X[nbr[:, k]]^T dY) or "store" (the stem's y under "bf16s").  cin / cout are the CONVOLUTION's; ldx is the
     row stride of the gathered operand (x, or dY for "dgrad"; default: contiguous), ldy that of dY for "wgrad".  row_perm: the
     launch goes through a class permutation (a strided data gradient, or the forward of a transposed convolution).  aligned:
     the operand pointers are 16-byte aligned (torch allocations are).  ksplit: the split the launch is asked for.  force_g:
-    set_stagger bits 12-26 (wgrad_plan's hook).  perm16: set_stagger bit 27 clear (the class-permuted bf16 data gradient on
-    compact_gemm_kernel).  shortcut_dense: a K = 1 class-permuted data gradient is the exact-fp32 dense GEMM mink_dense_xwt +
-    a scatter (functional.py ConvolutionFunction.backward, trunk.hip), not a gather."""
+    set_stagger bits 12-26 (wgrad_plan's hook).  flip / acc: flip_k bits 0 / 1 of a gather launch (weights of offset K-1-k;
+    y += result) -- a flipped launch never takes the flat stem path, an accumulating one never the class-permuted compact
+    kernel.  perm16: set_stagger bit 27 clear (the class-permuted bf16 data gradient on compact_gemm_kernel).  shortcut_dense:
+    a K = 1 class-permuted data gradient is the exact-fp32 dense GEMM mink_dense_xwt + a scatter (functional.py
+    ConvolutionFunction.backward, trunk.hip), not a gather."""
     m = CONV_MATH[math]
     if op == "store":
         return ConvForm("bf16 store" if math == "bf16s" else "fp32 store", frozenset({"y"}) if math == "bf16s" else frozenset())
@@ -107,13 +110,13 @@ def conv_form(op, K, cin, cout, math, n_out=1, ldx=None, ldy=None, row_perm=Fals
         ldy = cout if ldy is None else ldy
         G, nsplit = wgrad_plan(n_out, K, cin, cout, force_g)
         tag = f" G{G}" + (" split" if nsplit > 1 else "")
-        # the streaming kernels take the stem shape (wgrad_stream_ok in conv_wgrad.hip)
+        # the streaming kernels take the stem shape (stream_ok of wgrad_plan in conv_wgrad.hip)
         stream_ok = K == 27 and cin <= 32 and ldx < 64
         if G == 9 and stream_ok:
-            if m == 1:  # wgrad_impl in conv_wgrad.hip: bf16_stream
+            if m == 1:  # wgrad_plan in conv_wgrad.hip: bf16_stream
                 return ConvForm("wgrad_stream_bf16" + tag, frozenset({"x", "dy"}))
             return ConvForm("wgrad_stream" + tag, frozenset())
-        if m == 1 and G != 9 and cin % WT == 0 and cout % WT == 0 and aligned and (ldx | ldy) % 4 == 0:  # wgrad_impl in conv_wgrad.hip: the wgrad16_kernel branch
+        if m == 1 and G != 9 and cin % WT == 0 and cout % WT == 0 and aligned and (ldx | ldy) % 4 == 0:  # wgrad_plan in conv_wgrad.hip: the wgrad16_kernel branch
             return ConvForm(f"wgrad16<{3 if G == 3 else 1}>" + tag, frozenset({"x", "dy"}))
         return ConvForm("wgrad fp32" + tag, frozenset())  # launch_wgrad<G>: exact fp32 under every math (bf16x3 included)
     assert op in ("fwd", "dgrad"), op
@@ -123,21 +126,21 @@ def conv_form(op, K, cin, cout, math, n_out=1, ldx=None, ldy=None, row_perm=Fals
     gin, gout = (cout, cin) if wt else (cin, cout)  # the GEMM's reduction / output widths
     names = {"dy", "w"} if wt else {"x", "w"}
     ldx = gin if ldx is None else ldx
-    vec = aligned and ldx % 4 == 0 and gin % 4 == 0 and (wt or gout % 4 == 0)  # gather_gemm_impl in conv.hip: al, vec
+    vec = aligned and ldx % 4 == 0 and gin % 4 == 0 and (wt or gout % 4 == 0)  # plan_gather in conv.hip: al, vec
     if m == 0:
         return ConvForm("fp32", frozenset())
-    # the class-permuted branch (compact_perm_shape in conv.hip and its use in gather_gemm_impl): bf16 math takes it for the data gradient only
+    # the class-permuted branch (compact_perm_shape in conv.hip and its use in plan_gather): bf16 math takes it for the data gradient only
     if (row_perm and wt and m == 1 and perm16 and K >= 8 and gin >= 64 and gin % BK == 0 and gout % BN == 0 and vec
-            and gout % 4 == 0):
+            and gout % 4 == 0 and not acc):
         return ConvForm("class-permuted compact bf16", frozenset(names))
-    if not vec:  # gather_gemm_kernel (gather_gemm_impl in conv.hip, its last branch): operands that are not 16-byte rows -- no MATH parameter, exact fp32
+    if not vec:  # gather_gemm_kernel (plan_gather in conv.hip, its last branch): operands that are not 16-byte rows -- no MATH parameter, exact fp32
         return ConvForm("scalar gather_gemm", frozenset())
-    # gather_gemm2_kernel<W_T, STAGE, FLAT, MATH> (gather_gemm_impl in conv.hip: flat, MINK_LAUNCH_GG2; the row-compacted forms need fp32 math: compact_ok)
+    # gather_gemm2_kernel<W_T, STAGE, FLAT, MATH> (plan_gather in conv.hip: flat; the row-compacted forms need fp32 math: compact_ok)
     if row_perm:
         form = "staged gather_gemm2" + (" (transposed weights)" if wt else " (transposed-conv fwd)")
     elif wt:
         form = "dense gather_gemm2 (transposed weights)"
-    elif gin == 28 and ldx <= 32 and _cdiv(K, _cdiv(K, ksplit)) == 1:
+    elif gin == 28 and ldx <= 32 and not flip and _cdiv(K, _cdiv(K, ksplit)) == 1:
         form = "flat gather_gemm2 (cin 28)"  # FLAT = 28: un-split forward launches only
     else:
         form = "dense gather_gemm2"
@@ -150,7 +153,7 @@ CKP = 9  # conv_common.h: offsets per workgroup of the row-compacted kernel
 
 
 def gather_launch_form(n_out, K, cin, cout, ldx, ldy, wt, flip, perm, acc, ksplit, math="fp32", pipe=0):
-    """(launch form, slabs written) of one mink_conv_gather_gemm call -- gather_gemm_impl (csrc/conv.hip) for 16-byte aligned
+    """(launch form, slabs written) of one mink_conv_gather_gemm call -- plan_gather (csrc/conv.hip) for 16-byte aligned
     operands and default set_stagger switches, fp32 math included (conv_form names the fp32 launches just "fp32": its callers ask
     which operands are rounded, this one which kernel runs and how many slabs it writes).  cin / cout are the GEMM's reduction /
     output widths (the ABI's arguments), wt / flip / perm / acc its w_transposed, flip_k bit 0, row_perm and flip_k bit 1, ksplit
@@ -175,7 +178,7 @@ def gather_launch_form(n_out, K, cin, cout, ldx, ldy, wt, flip, perm, acc, kspli
     if math:
         conv_cin, conv_cout = (cout, cin) if wt else (cin, cout)
         cf = conv_form("dgrad" if wt else "fwd", K, conv_cin, conv_cout, {0: "fp32", 1: "bf16", 3: "bf16x3"}[math], n_out=n_out, ldx=ldx, row_perm=perm,
-                          ksplit=ksplit, shortcut_dense=False)
+                          ksplit=ksplit, shortcut_dense=False, flip=flip, acc=acc)
         return cf.form, zs
     if not vec:
         return "scalar gather_gemm", zs
@@ -184,6 +187,78 @@ def gather_launch_form(n_out, K, cin, cout, ldx, ldy, wt, flip, perm, acc, kspli
     if cin == 28 and zs == 1 and not flip and not wt and ldx <= 32:
         return "flat gather_gemm2 (cin 28)", zs
     return "dense gather_gemm2" + (" (transposed weights)" if wt else ""), zs
+
+
+def _launch_info_consts():
+    from nerf_downstream_amd import _lib
+
+    return _lib.constants("MINK_KERNEL_")
+
+
+def ask_gather_launch(L, n_in, ldx, cin, wt, flip, n_out, K, perm, n_virtual, ldy, cout, ksplit, acc=False, bias=False, stats=False,
+                      slabs=False, xw_aligned=True, y_aligned=True):
+    """The library's own answer for one mink_conv_gather_gemm / _stats / _slabs call under the switches now set
+    (mink_conv_gather_gemm_launch_info: the planner the launch runs) -> (return code, ConvLaunchInfo)."""
+    from nerf_downstream_amd import _lib
+
+    info = _lib.ConvLaunchInfo()
+    rc = L.mink_conv_gather_gemm_launch_info(n_in, ldx, cin, int(wt), int(flip) | (2 if acc else 0), n_out, K, int(perm), n_virtual, ldy, cout,
+                                             int(bias), ksplit, int(stats), int(slabs), int(xw_aligned), int(y_aligned), ctypes.byref(info))
+    return rc, info
+
+
+def ask_wgrad_launch(L, n_in, ldx, cin, ldy, cout, n_out, K, fuse=0, n_pool=0, aligned=True):
+    """The same for mink_conv_wgrad (fuse 0), mink_conv_wgrad_bn_relu_pool (1) and _b16 (2)."""
+    from nerf_downstream_amd import _lib
+
+    info = _lib.ConvLaunchInfo()
+    rc = L.mink_conv_wgrad_launch_info(n_in, ldx, cin, ldy, cout, n_out, K, fuse, n_pool, int(aligned), ctypes.byref(info))
+    return rc, info
+
+
+def launch_form_name(info, cin, acc=False):
+    """A gather-GEMM launch the library names (ConvLaunchInfo) in gather_launch_form's words.  cin (the GEMM's reduction width)
+    and acc are the call's: conv_form tags a channel tail under reduced math, gather_launch_form an accumulating staged launch.
+    The instantiation that carries the timing switches, which the restatement does not cover, reads "... ablation"."""
+    kind = _launch_info_consts()
+    t = list(info.targ)
+    if info.kernel == kind["COMPACT"]:
+        _, perm, abl, math, p3, sk = t
+        if sk:
+            return "stream-K"
+        return (("class-permuted compact" if perm else "row-compacted") + (" bf16" if math == 1 else "") + (" three-stage" if p3 else "")
+                + (" ablation" if abl else ""))
+    if info.kernel == kind["GATHER_SCALAR"]:
+        return "scalar gather_gemm"
+    assert info.kernel == kind["GATHER2"], info.kernel
+    wt, stage, flat, math = t[:4]
+    if stage:
+        form = "staged gather_gemm2" + (" (transposed weights)" if wt else " (transposed-conv fwd)" if math else "")
+    elif wt:
+        form = "dense gather_gemm2 (transposed weights)"
+    else:
+        form = "flat gather_gemm2 (cin 28)" if flat else "dense gather_gemm2"
+    if math:
+        return form + (" + channel tail" if cin % BK and not flat else "") + (" bf16x3" if math == 3 else " bf16")
+    return form + (" accumulate" if stage and acc else "")
+
+
+def wgrad_form_name(info, instantiation=False):
+    """A weight-gradient launch the library names in conv_form("wgrad")'s words ("wgrad16<3> G3 split"), or, `instantiation`,
+    the streaming kernels by their template arguments ("wgrad_stream<FUSE, FLAT>": the fused stem cases)."""
+    kind = _launch_info_consts()
+    t = list(info.targ)
+    tag = " split" if info.slabs > 1 else ""
+    if info.kernel == kind["WGRAD"]:
+        return f"wgrad fp32 G{t[0]}" + tag
+    if info.kernel == kind["WGRAD16"]:
+        return f"wgrad16<{t[0]}> G{t[0]}" + tag
+    args = {kind["WGRAD_STREAM"]: [n for n, on in (("FUSE", t[1]), ("FLAT", t[2])) if on],
+            kind["WGRAD_STREAM_BF16"]: [n for n, on in (("FUSE", t[0]), ("B16", t[1])) if on], kind["WGRAD_STREAM_B16T"]: []}[info.kernel]
+    name = {kind["WGRAD_STREAM"]: "wgrad_stream", kind["WGRAD_STREAM_BF16"]: "wgrad_stream_bf16", kind["WGRAD_STREAM_B16T"]: "wgrad_stream_b16t"}[info.kernel]
+    if instantiation:
+        return name + (f"<{', '.join(args)}>" if args else "")
+    return name + " G9" + tag  # (the streaming kernels take nine offsets per workgroup: wgrad_plan's `streaming`)
 
 
 def rounded_operands(op, K, cin, cout, math, **shape):

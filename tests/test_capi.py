@@ -260,7 +260,7 @@ def test_reader_raises_on_what_it_does_not_know(text, names):
 
 
 _STRUCTS = ("KernelMapDesc", "ConvLayer", "NormLayer", "Exec", "Stem", "BasicBlock", "LevelMaps", "Net", "ClassPartitionDesc",
-            "TimingEntry")
+            "TimingEntry", "ConvLaunchInfo")
 
 
 def test_struct_layout_against_the_c_compiler(tmp_path):

@@ -13,7 +13,8 @@ test_gpu_reduced_math, with torch on the GPU from contiguous copies of the logic
   batch-norm family, head, pools    the allclose limits of test_gpu_ops / test_gpu_compat
 Each case names the launch form it is meant for and asserts that the dispatcher's rules (restated in layerwise.gather_launch_form /
 conv_form / wgrad_plan, and asked of mink_conv_plan / mink_conv_wgrad_workspace_bytes / _supported where the library
-answers) take it there.  Nothing here is meant to fault: no buffer is smaller than the library asks for."""
+answers) take it there; the convolution cases also assert that the library's own plan for the very call they make
+(mink_conv_gather_gemm_launch_info / mink_conv_wgrad_launch_info) is that form.  Nothing here is meant to fault: no buffer is smaller than the library asks for."""
 import contextlib
 import ctypes
 
@@ -252,6 +253,13 @@ def test_gather_gemm_stays_inside_its_buffers(c):
             assert 1 <= L.mink_conv_plan(perm.numel(), K, cin, cout, 1) <= max(cin // BK, 1)
         common = (xg.ptr, n_in, ldx, cin, wg.ptr)
         tail = (_ptr(slab), slab.nbytes if slab else 0)
+        # the library's own answer for the call below (the planner the launch runs) is the form in the case id
+        rc, info = LW.ask_gather_launch(L, n_in, ldx, cin, wt, flip, n_out, K, perm is not None, perm.numel() if perm is not None else 0, ldy,
+                                        cout, ks, acc=c["acc"], bias=bg is not None and c["api"] != "slabs", stats=c["api"] == "stats",
+                                        slabs=c["api"] == "slabs", xw_aligned=(xg.ptr | wg.ptr) % 16 == 0,
+                                        y_aligned=(yg.ptr | (_ptr(slab) or 0) | (_ptr(bg) or 0 if c["api"] != "slabs" else 0)) % 16 == 0)
+        check(rc)
+        assert (LW.launch_form_name(info, cin, c["acc"]), info.slabs) == (c["form"], zs), (LW.launch_form_name(info, cin, c["acc"]), info.slabs)
         if c["api"] == "stats":
             sw = _ws(L.mink_conv_stats_workspace_bytes(n_out, cout), "stats_ws")
             so = _gout((512, 2, cout), torch.float64, name="stats_out")
@@ -402,6 +410,9 @@ def test_weight_gradient_stays_inside_its_buffers(c):
             assert L.mink_conv_wgrad_bn_relu_pool_supported(n_in, ldx, cin, n_out, K, cout) == 1
             assert L.mink_conv_wgrad_bn_relu_pool_supported(n_in, ldx, cin, n_out - 1, K, cout) == 0  # the threshold itself
         slabs = _gout((nsplit, K, cin, cout), name="row-split slabs") if need else None
+        rc, info = LW.ask_wgrad_launch(L, n_in, ldx, cin, ldy, cout, n_out, K, aligned=(xg.ptr | dg.ptr) % 16 == 0)
+        check(rc)
+        assert (LW.wgrad_form_name(info), info.slabs) == (c["form"], nsplit)  # the library's own answer for the call below
         check(L.mink_conv_wgrad(xg.ptr, n_in, ldx, cin, dg.ptr, ldy, cout, ng.ptr, n_out, K, dw.ptr, _ptr(slabs), need, _st()))
         torch.cuda.synchronize()
     _done(xg, dg, ng, dw, slabs)
@@ -445,7 +456,7 @@ def test_fused_stem_weight_gradient_stays_inside_its_buffers(cin, ldx, cout, kin
     math = 0 if kind == "fp32" else 1
     g = torch.Generator().manual_seed(cin * 5 + cout + len(kind))
     n_in, n_pool, nbr, x, y, in2out, dyp, mean, invstd, gamma, beta, dgamma, dbeta = _fused_operands(n_out, cin, cout, g, b16)
-    # (which kernel: wgrad_impl in csrc/conv_wgrad.hip -- flat when 512 < K cin <= 768, ldx <= 32, cin >= 16; b16t when cout == 64)
+    # (which kernel: wgrad_plan in csrc/conv_wgrad.hip -- flat when 512 < K cin <= 768, ldx <= 32, cin >= 16; b16t when cout == 64)
     flat = 512 < K * cin <= 768 and ldx <= 32 and cin >= 16
     want = {"fp32": "wgrad_stream<FUSE" + (", FLAT>" if flat else ">"), "bf16": "wgrad_stream_bf16<FUSE>",
             "b16": "wgrad_stream_b16t" if cout == 64 else "wgrad_stream_bf16<FUSE, B16>"}[kind]
@@ -464,6 +475,10 @@ def test_fused_stem_weight_gradient_stays_inside_its_buffers(cin, ldx, cout, kin
         _, nsplit = LW.wgrad_plan(n_out, K, cin, cout)
         assert nsplit > 1 and need == 4 * nsplit * K * cin * cout
         slabs = _gout((nsplit, K, cin, cout), name="row-split slabs")
+        rc, info = LW.ask_wgrad_launch(L, n_in, 32 if b16 else ldx, cin, cout, cout, n_out, K, fuse=2 if b16 else 1, n_pool=n_pool,
+                                       aligned=(xg.ptr | yg.ptr) % 16 == 0)
+        check(rc)
+        assert (LW.wgrad_form_name(info, instantiation=True), info.slabs) == (form, nsplit)  # the library's own answer for the call below
         stats = (mg.ptr, isg.ptr, gag.ptr, beg.ptr, dgg.ptr, dbg.ptr, ng.ptr, n_out, K, dw.ptr, slabs.ptr, need, _st())
         if b16:
             check(L.mink_conv_wgrad_bn_relu_pool_b16(xg.ptr, n_in, cin, yg.ptr, cout, dpg.ptr, n_pool, iog.ptr, *stats))

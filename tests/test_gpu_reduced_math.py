@@ -4,7 +4,7 @@ test_row_compacted_kernel_against_float64: ragged row counts (1, 63, 65, a few t
 64-row tile lacks.
 
 What a form computes is read from the shape-aware rounding table (layerwise.conv_form, a restatement of gather_gemm_impl in
-csrc/conv.hip and wgrad_impl in csrc/conv_wgrad.hip):
+csrc/conv.hip and wgrad_plan in csrc/conv_wgrad.hip):
   * bf16 forms:    float64 over bf16_rne(x) and bf16_rne(w) (or dY);
   * bf16x3 forms:  float64 over the three products xh*wh + xh*wl + xl*wh, h = rne(v) and l = rne(v - h) taken in fp32
                    (conv_common.h pack_bf16 / conv.hip bf16_residual; layerwise.bf16_split);

@@ -175,23 +175,23 @@ def _launch_forms(L, n_rows, K, cin, cout, perm, wt, stats):
     (torch allocations are 16-byte aligned and rows contiguous, so the alignment terms hold).  cin / cout are the GEMM's:
     a data gradient's are the convolution's cout / cin."""
     ks = int(L.mink_conv_plan(n_rows, K, cin, cout, int(perm)))  # (functional.py _plan_ksplit: n_rows = the permutation's length)
-    vec = cin % 4 == 0 and (wt or cout % 4 == 0)  # gather_gemm_impl in conv.hip: al, vec
+    vec = cin % 4 == 0 and (wt or cout % 4 == 0)  # plan_gather in conv.hip: al, vec
     # compact_perm_shape (conv.hip) and the class-permuted branch of gather_gemm_impl
     if perm and not stats and vec and K >= 8 and cin >= 64 and cin % BK == 0 and cout % BN == 0:
         ncc = cin // BK
         return {"class-permuted compact"} | ({"split-K"} if _cdiv(ncc, _cdiv(ncc, ks)) > 1 else set())
     kper = _cdiv(K, ks)
-    zs = _cdiv(K, kper)  # gather_gemm_impl in conv.hip: zs
+    zs = _cdiv(K, kper)  # plan_gather in conv.hip: zs
     forms = {"split-K"} if zs > 1 else set()
-    if vec and not perm and K >= 8 and kper <= CKP and cin >= 64 and cin % BK == 0 and cout % BN == 0:  # gather_gemm_impl in conv.hip: compact_ok, compact
+    if vec and not perm and K >= 8 and kper <= CKP and cin >= 64 and cin % BK == 0 and cout % BN == 0:  # plan_gather in conv.hip: compact_ok, compact
         forms.add("row-compacted")
-    elif vec:  # gather_gemm2_kernel: `stage` = a row permutation (gather_gemm_impl in conv.hip: stage)
+    elif vec:  # gather_gemm2_kernel: `stage` = a row permutation (plan_gather in conv.hip: stage)
         forms.add("staged gather_gemm2" if perm else "dense gather_gemm2")
         if cin % BK:
             forms.add("channel tail")
     else:
         forms.add("scalar gather_gemm")
-    if stats:  # gather_gemm_impl in conv.hip: want_stats, stats_direct, stats_split
+    if stats:  # plan_gather in conv.hip: want_stats, stats_direct, stats_split
         if zs == 1 and vec:
             forms.add("stats direct")
         elif zs > 1 and cout % 4 == 0 and cout <= 1024:
