@@ -630,6 +630,44 @@ int mink_ln_bwd(const float *dy, const float *x, const float *y, int64_t n, int3
                 const float *gamma, int32_t relu, float *dx, float *dresidual, float *dgamma, float *dbeta, void *workspace,
                 int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ PowerNorm (csrc/powernorm.hip)
+ * MinkowskiPowerNorm (modules/powernorm.py:246-329; `get_norm("PN")`, modules/common.py:29-30) on x[n][C] with a row pitch
+ * ldx >= C (every other matrix -- y, residual, dy, dx, dresidual -- is contiguous, pitch C; the pad columns of x may hold
+ * anything, NaN included: no value of them reaches a result), `groups` groups of C / groups channels (groups must divide C):
+ *   r[row][g] = 1/sqrt(mean over the group's channels of x^2 + 1e-5)   xh = x * r    (the group scaling; its epsilon is fixed)
+ *   training: it = ++iters[0];  var[c] = mean over rows of xh^2;  scale = it <= warmup_iters ? 1/sqrt(var + eps)
+ *             : 1/sqrt(running_phi + eps) (running_phi BEFORE this step's update);  then, if it < warmup_iters,
+ *             running_phi = running_phi (it-1)/it + var/it;  always running_phi = alpha_fwd running_phi + (1-alpha_fwd) var
+ *   eval    : scale = 1/sqrt(running_phi + eps); no buffer changes
+ *   y = [relu]( weight * (xh * scale) + bias [+ residual] )
+ * Limits: 1 <= C <= 4096 (MINK_PN_MAX_C; refused beyond, before any launch), 1 <= groups <= C, n < 2^31; mink_pn_fwd and
+ * mink_pn_bwd refuse n == 0 (an empty batch has no second moment), mink_pn_apply accepts it.  16-byte accesses when
+ * (C / groups) % 4 == 0, ldx % 4 == 0 and x, y, residual, dy, dx, dresidual are 16-byte aligned, dword accesses otherwise; the [C] vectors
+ * and rscale may have any 4-byte alignment, iters (int64 [1]) is 8-byte aligned.
+ * Everything is decided on the device: iters is bumped and read there, the warm-up branch and both running_phi updates
+ * happen there, nothing is read back.  Sums are accumulated in double in a fixed order and rounded once; no floating-point
+ * atomics; two runs from the same state are bitwise equal.
+ * Outputs kept for backward: rscale[n][groups] (r above), var[C], scale[C].  Four launches.
+ *   workspace : >= mink_pn_workspace_bytes(n, C, groups), 8-byte aligned (0 from the query = a shape the family refuses) */
+#define MINK_PN_MAX_C 4096
+int64_t mink_pn_workspace_bytes(int64_t n, int32_t C, int32_t groups);
+int mink_pn_fwd(const float *x, int32_t ldx, int64_t n, int32_t C, int32_t groups, float eps, float alpha_fwd, int64_t warmup_iters,
+                const float *weight, const float *bias, const float *residual, int32_t relu, float *y, float *rscale, float *var,
+                float *scale, float *running_phi, int64_t *iters, void *workspace, int64_t workspace_bytes, void *stream);
+/* Eval-mode forward (three launches): rscale[n][groups] and scale[C] are outputs, as above. */
+int mink_pn_apply(const float *x, int32_t ldx, int64_t n, int32_t C, int32_t groups, float eps, const float *running_phi, const float *weight,
+                  const float *bias, const float *residual, int32_t relu, float *y, float *rscale, float *scale, void *stream);
+/* Backward (three launches): PowerNorm's approximate derivative, then the exact one of the group scaling.  With dym = dy
+ * masked by y > 0 (y is only read when relu != 0), z = xh * scale:
+ *   a = dym weight - (1 - alpha_bkw) ema_gz z   (ema_gz as it is when the call is made);   ema_gz += mean over rows of a z
+ *   dxh = a / sqrt(var + eps)   (the BATCH var, also after warm-up);   dx = r (dxh - xh * mean over the group of dxh xh)
+ *   dweight = sum over rows of dym z;  dbias = sum over rows of dym;  dresidual (may be NULL) = dym
+ * training == 0 (a forward by mink_pn_apply): a = dym weight, dxh = a * scale, ema_gz and var are not touched (may be NULL). */
+int mink_pn_bwd(const float *dy, const float *x, int32_t ldx, const float *y, int64_t n, int32_t C, int32_t groups, float eps, float alpha_bkw,
+                int32_t training, const float *rscale, const float *var, const float *scale, const float *weight, int32_t relu,
+                float *ema_gz, float *dx, float *dresidual, float *dweight, float *dbias, void *workspace, int64_t workspace_bytes,
+                void *stream);
+
 /* ------------------------------------------------------------------ trilinear interpolation and splat (csrc/interp.hip)
  * ME.MinkowskiInterpolation (reference co3d_3d/src/data/transforms.py:472,514-521 PerlinNoise; models/mink/fcnn.py:194-208
  * `y.interpolate(x)`) and TensorField.splat (fcnn.py:186) [ME-recall of interpolation_map_weight / TensorField.splat; parity

@@ -21,8 +21,15 @@ reference's `--sparsify --sparse_mode 1,1,1,1,1,1,1,1,1` boils down to:
 
         --ginb "get_model.sparse=[1,1,1,1,1,1,1,1,1]" --ginb "evaluate.layout='csr'"
 
-The command-line flags --sparsify / --sparse_mode / --layout themselves, and the reference's powernorm / --device cpu / --profile
-options, are refused here."""
+PowerNorm (the reference declares --convert_powernorm and never uses it): the binding
+
+        --ginb "evaluate.convert_powernorm=True"
+
+turns every batch norm of the model into a MinkowskiPowerNorm, before the checkpoint is loaded when it was trained with PN
+layers, after it for a batch-norm checkpoint.
+
+The command-line flags --sparsify / --sparse_mode / --layout / --convert_powernorm themselves, and the reference's
+--device cpu / --profile options, are refused here."""
 import argparse
 import json
 import logging
@@ -45,6 +52,8 @@ logger = logging.getLogger(__name__)
 OUT_OF_SCOPE = ("convert_powernorm", "sparsify", "sparse_mode", "layout", "profile", "device")
 SPARSE_HINT = ("a pruned checkpoint is evaluated through gin bindings, not through --sparsify / --sparse_mode / --layout: "
                "--ginb \"get_model.sparse=[1,1,1,1,1,1,1,1,1]\" --ginb \"evaluate.layout='csr'\"")
+POWERNORM_HINT = ("PowerNorm is reached through a gin binding, not through --convert_powernorm: "
+                  "--ginb \"evaluate.convert_powernorm=True\" (training: --ginb \"train.convert_powernorm=True\")")
 
 
 def _gin_or(name, default):
@@ -63,11 +72,13 @@ def _scene_name(batch, index):
 
 @gin.configurable
 def evaluate(save_path, load_path, training_module: str = "SegmentationTraining", tag="default", visualize=False, replace=False,
-             val_phase="val", val_num_workers=None, ME=None, device=None, seed: int = 777, layout="csr"):
+             val_phase="val", val_num_workers=None, ME=None, device=None, seed: int = 777, layout="csr", convert_powernorm=False):
     """-> the `val/*` dict written to <save_path>/<tag>.json, or None when that file exists and `replace` is not set.
     `ME` / `device` are test hooks, as in train(): the CPU tests inject the oracle namespace.  `layout`: what `sparsify()` is
     called with when the checkpoint is a pruned one ("csr" / "coo": the sparse kernel, "strided": the dense one on the masked
-    weights)."""
+    weights).  `convert_powernorm` (`--ginb "evaluate.convert_powernorm=True"`): every batch norm becomes a MinkowskiPowerNorm
+    -- before the checkpoint is loaded when its keys contain `.pn.running_phi` (a checkpoint trained with PN layers), after it
+    otherwise (a batch-norm checkpoint evaluated as PN: `running_var` becomes `running_phi`)."""
     os.makedirs(save_path, exist_ok=True)
     json_path = os.path.join(save_path, f"{tag}.json")
     if not replace and os.path.isfile(json_path):
@@ -84,12 +95,18 @@ def evaluate(save_path, load_path, training_module: str = "SegmentationTraining"
     torch.manual_seed(seed)
     model = (get_model(ME=ME) if ME is not None else get_model()).to(device)
     refuse_instance_head(model, "co3d_3d.eval")
-    is_pruned = any("_mask" in k for k in T.load_checkpoint_file(load_path)["state_dict"])
+    keys = list(T.load_checkpoint_file(load_path)["state_dict"])
+    is_pruned = any("_mask" in k for k in keys)
+    pn_checkpoint = any(".pn.running_phi" in k for k in keys)
+    if convert_powernorm and pn_checkpoint:
+        model = T.to_powernorm(model, ME)
     if is_pruned:  # identity pruning gives every prunable parameter the `_orig` / `_mask` pair the checkpoint holds
         logger.info("received checkpoint of pruned network")
         to_prune = P.get_parameters_to_prune(model)
         P.register_prune_buffers(to_prune)
     T.load_checkpoint(load_path, model, weights_only=True)  # tensors and plain containers only: nothing from the file is executed
+    if convert_powernorm and not pn_checkpoint:
+        model = T.to_powernorm(model, ME)
     sparsified = False
     if is_pruned:
         num = P.count_parameters(model)
@@ -181,6 +198,8 @@ def main(argv=None):
         print("out of scope here (the reference's pruning / sparse-layout / profiling study): --" + ", --".join(bad), file=sys.stderr)
         if any(b in ("sparsify", "sparse_mode", "layout") for b in bad):
             print(SPARSE_HINT, file=sys.stderr)
+        if "convert_powernorm" in bad:
+            print(POWERNORM_HINT, file=sys.stderr)
         return 2
     if not args.load_path:
         print("--load_path is required", file=sys.stderr)

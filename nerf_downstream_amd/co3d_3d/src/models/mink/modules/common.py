@@ -8,13 +8,19 @@ backend (default) and, in tests, on the CPU oracle."""
 from nerf_downstream_amd import minkowski as _HIP_ME
 
 
+POWERNORM_HINT = ("MinkowskiPowerNorm layers come from converting every batch norm of a network: "
+                  "--ginb \"train.convert_powernorm=True\" / --ginb \"evaluate.convert_powernorm=True\", or "
+                  "ME.MinkowskiPowerNorm.convert_powernorm(model)")
+
+
 def default_me():
     return _HIP_ME
 
 
 def get_norm(norm_type, n_channels, D=3, bn_momentum=0.1, ME=None):
     """"BN" / "IN" / "LN" (reference common.py:22-32).  "PN" (PowerNorm, part of the reference's pruning study) is not
-    implemented."""
+    implemented as a norm type: the layer exists (ME.MinkowskiPowerNorm) and is reached by converting a network's batch norms
+    (POWERNORM_HINT)."""
     ME = ME or _HIP_ME
     if norm_type == "BN":
         return ME.MinkowskiBatchNorm(n_channels, momentum=bn_momentum)
@@ -23,7 +29,7 @@ def get_norm(norm_type, n_channels, D=3, bn_momentum=0.1, ME=None):
     if norm_type == "LN":
         return ME.MinkowskiLayerNorm(n_channels)
     if norm_type == "PN":
-        raise ValueError("Norm type: PN (PowerNorm) is not implemented; use BN, IN or LN")
+        raise ValueError(f"Norm type: PN (PowerNorm) is not implemented as a norm type; use BN, IN or LN. {POWERNORM_HINT}")
     raise ValueError(f"Norm type: {norm_type} not supported (BN, IN and LN are; PN is not implemented)")
 
 

@@ -149,6 +149,17 @@ def validate(module, loader, device, world):
     return module.val_metrics(validation_pass(module, loader, device, world))
 
 
+def to_powernorm(model, ME=None):
+    """MinkowskiPowerNorm.convert_powernorm(model) of the namespace the model was built from.  PowerNorm exists on the HIP
+    backend only: an injected namespace without it (the CPU oracle) is refused."""
+    if ME is None:
+        from nerf_downstream_amd import minkowski as ME
+    if not hasattr(ME, "MinkowskiPowerNorm"):
+        raise ValueError("convert_powernorm=True: the injected ME namespace has no MinkowskiPowerNorm (PowerNorm runs on the HIP "
+                         "backend only)")
+    return ME.MinkowskiPowerNorm.convert_powernorm(model)
+
+
 @gin.configurable
 def train(
     save_path: str,
@@ -195,9 +206,13 @@ def train(
     ME=None,
     device=None,
     seed: int = 777,
+    convert_powernorm: bool = False,
 ):
     """Same parameters (and gin bindings `train.*`) as the reference.  `ME` / `device` are test
-    hooks: the CPU tests inject the oracle namespace to run BASELINE config #1 on the host."""
+    hooks: the CPU tests inject the oracle namespace to run BASELINE config #1 on the host.
+    `convert_powernorm` (`--ginb "train.convert_powernorm=True"`): every batch norm of the model becomes a
+    MinkowskiPowerNorm before the optimizer is built (wider than NORM_TYPE, which in the Mink-ResNets selects the stem's norm
+    only).  PowerNorm statistics and `ema_gz` stay local to a rank; a checkpoint holds rank 0's buffers."""
     if scheduler_interval != "step":
         raise NotImplementedError("the classification configs step the scheduler per iteration")
     world, rank, local_rank = _dist_env()
@@ -224,6 +239,8 @@ def train(
         from nerf_downstream_amd import minkowski
 
         model = minkowski.MinkowskiSyncBatchNorm.convert_sync_batchnorm(model)
+    if convert_powernorm:
+        model = to_powernorm(model, ME)
     model = model.to(device)
     if run_name is None or "default" in run_name.lower() or run_name == "":
         run_name = f"b{batch_size}x{gpus}-{model.__class__.__name__}"

@@ -25,6 +25,7 @@ from .modules import (  # noqa: F401
     MinkowskiMaxPooling,
     MinkowskiNetwork,
     MinkowskiPositionalEncoding,
+    MinkowskiPowerNorm,
     MinkowskiPReLU,
     MinkowskiReLU,
     MinkowskiSELU,
@@ -49,5 +50,5 @@ class SparseTensorQuantizationMode(enum.Enum):
 
 
 BACKEND = "hip-gfx950"
-SUPPORTS_FUSED_NORM = True  # Minkowski{Batch,Instance,Layer}Norm.forward(x, relu=, residual=)
+SUPPORTS_FUSED_NORM = True  # Minkowski{Batch,Instance,Layer,Power}Norm.forward(x, relu=, residual=)
 SUPPORTS_PREPARE_AHEAD = True  # TensorField.prepare_ahead(plan) + CoordinateManager.trace

@@ -487,7 +487,7 @@ from .head import (  # noqa: E402,F401
     slice_rows,
 )
 from .interp import InterpolationFunction, SplatFunction  # noqa: E402,F401
-from .norm import BatchNormFunction, BNReLUSumPoolFunction, InstanceNormFunction, LayerNormFunction, SyncBatchNormFunction  # noqa: E402,F401
+from .norm import BatchNormFunction, BNReLUSumPoolFunction, InstanceNormFunction, LayerNormFunction, PowerNormFunction, SyncBatchNormFunction  # noqa: E402,F401
 from .pool import (  # noqa: E402,F401
     AvgPoolFunction,
     GlobalAvgPoolFunction,

@@ -12,7 +12,14 @@ from .coords import ORIGIN_TS, CoordinateMapKey, _as_int
 from .eltwise import ActivationFunction, ReLUFunction
 from .field import FieldGatherCatFunction, lazy_index_csr
 from .interp import InterpolationFunction
-from .norm import BatchNormFunction, BNReLUSumPoolFunction, InstanceNormFunction, LayerNormFunction, SyncBatchNormFunction
+from .norm import (
+    BatchNormFunction,
+    BNReLUSumPoolFunction,
+    InstanceNormFunction,
+    LayerNormFunction,
+    PowerNormFunction,
+    SyncBatchNormFunction,
+)
 from .pool import (
     AvgPoolFunction,
     GlobalAvgPoolFunction,
@@ -405,6 +412,87 @@ class MinkowskiLayerNorm(nn.Module):
         beta = ln.bias if ln.bias is not None else torch.zeros(C, device=F.device)
         out = LayerNormFunction.apply(F, gamma, beta, ln.eps, residual.F if residual is not None else None, bool(relu))
         return _same_kind(input, out)
+
+
+class _PowerNormState(nn.Module):
+    """Parameters, buffers and settings of one PowerNorm layer under the names the reference's MaskPowerNorm gives them
+    (modules/powernorm.py:142-177), so `*.pn.weight`, `*.pn.bias`, `*.pn.running_phi`, `*.pn.ema_gz` and `*.pn.iters` load
+    key for key.  `weight` and `bias` are always parameters; `affine` is stored and ignored, as there."""
+
+    def __init__(self, num_features, eps, alpha_fwd, alpha_bkw, affine, warmup_iters, group_num):
+        super().__init__()
+        self.num_features, self.eps, self.affine = num_features, eps, affine
+        self.weight = nn.Parameter(torch.ones(num_features))
+        self.bias = nn.Parameter(torch.zeros(num_features))
+        self.register_buffer("running_phi", torch.ones(1, num_features, 1, 1))
+        self.register_buffer("ema_gz", torch.zeros(1, num_features, 1, 1))
+        self.register_buffer("iters", torch.zeros(1, dtype=torch.int64))
+        self.afwd, self.abkw = alpha_fwd, alpha_bkw
+        self.warmup_iters, self.group_num = warmup_iters, group_num
+
+
+@gin.configurable
+class MinkowskiPowerNorm(nn.Module):
+    """The reference's MinkowskiPowerNorm (modules/powernorm.py:246-329): every row is scaled by the root second moment of
+    each of its `group_num` channel groups, every channel by the root of the batch's second moment (the first
+    `warmup_iters` training steps) or of the running one `pn.running_phi` (afterwards, and in eval mode); no mean is
+    subtracted.  The backward is PowerNorm's approximate derivative with the running state `pn.ema_gz`.  The step counter
+    `pn.iters`, the warm-up branch and the buffer updates live on the device (csrc/powernorm.hip): no host synchronisation
+    per layer and step, where the reference reads the counter back with `.item()`.
+    Takes a SparseTensor or a TensorField and returns the same kind; at most 4096 channels, divisible by `group_num`.
+    Statistics and `ema_gz` are local to a rank under data parallelism.
+
+    Extension shared with MinkowskiBatchNorm: `forward(x, relu=True, residual=r)` computes relu(norm(x) + r) in one pass."""
+
+    def __init__(self, num_features, eps=1e-5, alpha_fwd=0.9, alpha_bkw=0.9, affine=True, warmup_iters=10000, group_num=1):
+        super().__init__()
+        if int(group_num) < 1 or int(num_features) % int(group_num):
+            raise ValueError(f"MinkowskiPowerNorm({num_features}, group_num={group_num}): the channels must divide into the groups")
+        self.pn = _PowerNormState(num_features, eps, alpha_fwd, alpha_bkw, affine, warmup_iters, group_num)
+
+    def forward(self, input, relu=False, residual=None):
+        pn = self.pn
+        if residual is not None:
+            _check_same(input, residual)
+        out = PowerNormFunction.apply(
+            _features(input), pn.weight, pn.bias, pn.running_phi, pn.ema_gz, pn.iters, pn.training, pn.eps, pn.afwd, pn.abkw,
+            pn.warmup_iters, pn.group_num, residual.F if residual is not None else None, bool(relu))
+        return _same_kind(input, out)
+
+    def __repr__(self):
+        pn = self.pn
+        return (f"{self.__class__.__name__}({pn.num_features}, eps={pn.eps}, affine={pn.affine}, alpha_fwd={pn.afwd}, "
+                f"alpha_bkw={pn.abkw}, warmup_iters={pn.warmup_iters}, group_num={pn.group_num})")
+
+    @classmethod
+    def convert_powernorm(cls, module):
+        """Recursively replace every MinkowskiBatchNorm (its synchronised subclass included) by a
+        MinkowskiPowerNorm(C, eps=bn.eps, affine=bn.affine) that shares `weight` and `bias`, takes `running_var` as
+        `running_phi` and `num_batches_tracked` as `iters`; `running_mean` is dropped (reference powernorm.py:291-329).
+        Networks that cached what they know about their batch norms (the list of step counters one launch bumps, the native
+        trunk's plan) are told to look again: a converted network runs module by module."""
+        if isinstance(module, MinkowskiBatchNorm):
+            bn = module.bn
+            new = cls(bn.num_features, eps=bn.eps, affine=bn.affine)
+            pn = new.pn
+            if bn.affine:
+                pn.weight, pn.bias = bn.weight, bn.bias
+            ref = bn.weight if bn.affine else bn.running_var
+            if ref is not None:
+                new.to(ref.device)
+            if bn.running_var is not None:
+                pn.running_phi = bn.running_var.detach().reshape(1, -1, 1, 1)
+            if bn.num_batches_tracked is not None:
+                pn.iters = bn.num_batches_tracked.detach().reshape(1)
+            new.train(module.training)
+            return new
+        for name, child in list(module.named_children()):
+            setattr(module, name, cls.convert_powernorm(child))
+        if hasattr(module, "_norms"):  # the batch norms whose step counters the network bumps in one launch: none are left below
+            module._norms = [m for m in module.modules() if isinstance(m, MinkowskiBatchNorm)]
+        if hasattr(module, "_trunk_plan"):
+            module._trunk_plan = None
+        return module
 
 
 class MinkowskiLinear(nn.Module):

@@ -1,10 +1,12 @@
-"""Batch, instance, layer and cross-rank batch normalisation of feature rows, each optionally fused with the residual add
-and ReLU that follow it (csrc/batchnorm.hip, csrc/norm.hip)."""
+"""Batch, instance, layer, power and cross-rank batch normalisation of feature rows, each optionally fused with the residual
+add and ReLU that follow it (csrc/batchnorm.hip, csrc/norm.hip, csrc/powernorm.hip)."""
 import torch
 
-from .._lib import check, lib
+from .._lib import CONSTANTS, check, lib
 from . import streams
 from ._rt import _check_offsets, _f32c, _ptr, _scratch, _stream
+
+PN_MAX_C = CONSTANTS["MINK_PN_MAX_C"]  # the widest layer the PowerNorm kernels take
 
 
 # -------------------------------------------------------------------------- batch norm
@@ -334,3 +336,99 @@ class BNReLUSumPoolFunction(torch.autograd.Function):
             )
         )
         return gx, dgamma, dbeta, None, None, None, None, None, None, None, None
+
+
+class PowerNormFunction(torch.autograd.Function):
+    """PowerNorm over the rows of F (the reference's MaskPowerNorm behind MinkowskiPowerNorm, csrc/powernorm.hip) with the
+    residual add and ReLU of BatchNormFunction.  `running_phi`, `ema_gz` (fp32, C elements) and `iters` (int64 [1]) are the
+    module's device buffers: the kernels bump the counter, pick the warm-up branch and update the buffers themselves, so
+    neither forward nor backward reads anything back.  The backward is PowerNorm's approximate derivative (it updates
+    `ema_gz`), followed by the exact derivative of the group scaling.  Kept for backward beside x (and y under a fused
+    ReLU): the row scale [n, groups] and two [C] vectors."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_phi, ema_gz, iters, training, eps, alpha_fwd, alpha_bkw, warmup_iters, groups,
+                residual, relu):
+        L = lib()
+        x = _f32c(x)
+        n, C = x.shape
+        dev = x.device
+        groups = int(groups)
+        if groups < 1 or C % groups:
+            raise ValueError(f"PowerNorm: {C} channels are not divisible into {groups} groups")
+        if C > PN_MAX_C:
+            raise ValueError(f"PowerNorm: {C} channels, the kernels take at most {PN_MAX_C}")
+        if training and n == 0:
+            raise ValueError("PowerNorm in training mode needs at least one row: an empty batch has no second moment "
+                             "(running_phi would become NaN)")
+        weight, bias = _f32c(weight).reshape(-1), _f32c(bias).reshape(-1)
+        if residual is not None:
+            residual = _f32c(residual)
+        y = torch.empty_like(x)
+        ctx.training, ctx.relu, ctx.has_res = bool(training), bool(relu), residual is not None
+        ctx.eps, ctx.alpha_bkw, ctx.groups = float(eps), float(alpha_bkw), groups
+        ctx.ema_gz = ema_gz  # (a buffer the backward updates in place, not a saved tensor: its version moves with every step)
+        if n == 0:
+            ctx.save_for_backward(x, None, None, None, None, weight)
+            return y
+        rscale = torch.empty(n, groups, dtype=torch.float32, device=dev)
+        scale = torch.empty(C, dtype=torch.float32, device=dev)
+        if training:
+            _check_pn_buffers(running_phi, ema_gz, iters, C, dev)
+            var = torch.empty(C, dtype=torch.float32, device=dev)
+            ws = _scratch(L.mink_pn_workspace_bytes(n, C, groups), dev, "pn")
+            check(
+                L.mink_pn_fwd(
+                    x.data_ptr(), C, n, C, groups, eps, alpha_fwd, int(warmup_iters), weight.data_ptr(), bias.data_ptr(),
+                    _ptr(residual), int(relu), y.data_ptr(), rscale.data_ptr(), var.data_ptr(), scale.data_ptr(),
+                    running_phi.data_ptr(), iters.data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
+                )
+            )
+        else:
+            _check_pn_buffers(running_phi, None, None, C, dev)
+            var = None
+            check(
+                L.mink_pn_apply(
+                    x.data_ptr(), C, n, C, groups, eps, running_phi.data_ptr(), weight.data_ptr(), bias.data_ptr(), _ptr(residual),
+                    int(relu), y.data_ptr(), rscale.data_ptr(), scale.data_ptr(), _stream(),
+                )
+            )
+        ctx.save_for_backward(x, y if relu else None, rscale, var, scale, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        L = lib()
+        x, y, rscale, var, scale, weight = ctx.saved_tensors
+        gy = _f32c(gy)
+        n, C = x.shape
+        dev = x.device
+        none = (None,) * 9
+        if n == 0:
+            z = torch.zeros(C, dtype=torch.float32, device=dev)
+            return (torch.empty_like(x), z, z.clone(), *none, torch.empty_like(x) if ctx.has_res else None, None)
+        gx = torch.empty_like(x)
+        gres = torch.empty_like(x) if ctx.has_res else None
+        dweight = torch.empty(C, dtype=torch.float32, device=dev)
+        dbias = torch.empty(C, dtype=torch.float32, device=dev)
+        ws = _scratch(L.mink_pn_workspace_bytes(n, C, ctx.groups), dev, "pn")
+        check(
+            L.mink_pn_bwd(
+                gy.data_ptr(), x.data_ptr(), C, _ptr(y), n, C, ctx.groups, ctx.eps, ctx.alpha_bkw, int(ctx.training),
+                rscale.data_ptr(), _ptr(var), scale.data_ptr(), weight.data_ptr(), int(ctx.relu),
+                ctx.ema_gz.data_ptr() if ctx.training else None, gx.data_ptr(), _ptr(gres), dweight.data_ptr(), dbias.data_ptr(),
+                ws.data_ptr(), ws.numel(), _stream(),
+            )
+        )
+        return (gx, dweight, dbias, *none, gres, None)
+
+
+def _check_pn_buffers(running_phi, ema_gz, iters, C, dev):
+    """The PowerNorm state the kernels write through raw pointers: fp32 / int64, contiguous, on the features' device."""
+    for name, t, dtype, numel in (("running_phi", running_phi, torch.float32, C), ("ema_gz", ema_gz, torch.float32, C),
+                                  ("iters", iters, torch.int64, 1)):
+        if t is None:
+            continue
+        if t.dtype != dtype or t.numel() != numel or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"PowerNorm: buffer {name} must be a contiguous {dtype} tensor of {numel} elements on {dev}, "
+                             f"got {t.dtype} {tuple(t.shape)} on {t.device}")
