@@ -62,7 +62,7 @@ const char *mink_last_error(void);
 #define MINK_ABI_VERSION 4
 int mink_abi_version(void);
 
-/* ------------------------------------------------------------------ coordinate maps (csrc/coords.hip)
+/* ------------------------------------------------------------------ coordinate maps (csrc/coords.hip; the 5^3 / 7^3 cube tables: csrc/conv_bigk.hip)
  * Coordinate hash map: open addressing, linear probing, 64-bit packed keys
  * (16 bits each for batch | x+2^15 | y+2^15 | z+2^15), int32 values.
  * Replaces ME's CoordinateMapCPU/GPU (insert_and_map / stride / kernel_map) behind
@@ -171,6 +171,18 @@ typedef struct MinkKernelMapDesc {
 } MinkKernelMapDesc;
 int mink_kernel_map_batch(int32_t n, const MinkKernelMapDesc *descs, void *stream);
 
+/* Neighbour table of a centred CUBE of ks^3 offsets, ks = 5 (K = 125) or 7 (K = 343): the sizes beyond the 27 offsets that
+ * MinkKernelMapDesc.offsets holds.  Semantics of mink_kernel_map: nbr[o][k] = the input row at out_coords[o] + offset_k or -1, k
+ * enumerating x fastest and z slowest, offset_k = (k % ks - r, k / ks % ks - r, k / ks^2 - r) * step with r = (ks - 1) / 2 and
+ * step = dilation * input tensor stride; nbr_t[i][k] = o (may be NULL; cleared to -1 here).  A neighbour whose coordinate
+ * leaves the packable range (-32768..32767 per axis) is absent.  The entry inserts the input rows (unique, as the rows of a
+ * map are) into a per-voxel hash map of its own in `workspace` (>= mink_kernel_map_cube_workspace_bytes(n_in)), so it does not
+ * depend on the level's map having been filled (mink_coords_build_levels leaves it empty for ascending rows), and probes it
+ * once per (row, offset).  Refuses n_out * K >= 2^31.  Coordinates and workspace on 16 bytes. */
+int64_t mink_kernel_map_cube_workspace_bytes(int64_t n_in);
+int mink_kernel_map_cube(const int32_t *in_coords, int64_t n_in, const int32_t *out_coords, int64_t n_out, int32_t ks,
+                         int32_t step, int32_t *nbr, int32_t *nbr_t, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Process-wide overflow sink of the block-index builds: a 32-bit word in PINNED host memory (device-mapped; NULL = none), zero
  * initialised by the caller.  A build whose blk_cap was too small writes 1 into it (besides clearing its own blk_counter) and
  * nobody ever refills it, so a caller that looks at the word before queuing its next batch learns of a violated capacity
@@ -214,7 +226,7 @@ int mink_class_partition_batch(int32_t n_maps, const MinkClassPartitionDesc *des
 int mink_batch_offsets(const int32_t *coords, int64_t n, int32_t B, int32_t *batch_offsets,
                        uint32_t *status, void *stream);
 
-/* ------------------------------------------------------------------ sparse convolution (csrc/conv.hip, csrc/conv_wgrad.hip)
+/* ------------------------------------------------------------------ sparse convolution (csrc/conv.hip, csrc/conv_wgrad.hip; kernel volumes above 27: csrc/conv_bigk.hip)
  * Replaces ME ConvolutionForward/BackwardKernel behind ME.MinkowskiConvolution
  * (modules/common.py:116-125; the algorithm is re-stated by the reference at
  * sparse_conv.py:122-144): out[o] = sum_k in[nbr[o][k]] @ W[k]  (+ bias).
@@ -360,6 +372,24 @@ int mink_conv_wgrad_bn_relu_pool(const float *x, int64_t n_in, int32_t ldx, int3
                                  const float *invstd, const float *gamma, const float *beta,
                                  const float *dgamma, const float *dbeta, const int32_t *nbr, int64_t n_out,
                                  int32_t K, float *dw, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Kernel volumes 27 < K <= MINK_BIGK_MAX_K (the 5^3 and 7^3 cubes; csrc/conv_bigk.hip).  Exact fp32 on the matrix cores in
+ * EVERY mink_conv_set_math mode; no atomics, fixed summation order (bit-identical runs).  Arguments as mink_conv_gather_gemm
+ * (w_transposed, flip_k bit 0, pitches ldx / ldy; any cin, cout >= 1; no alignment beyond 4 bytes) without row_perm and split:
+ * ONE launch, a workgroup owns MINK_BIGK_ROW_TILE rows x 64 columns, walks its table in chunks of 32 offsets, drops the offsets
+ * no row of the tile has and reduces flattened over (present offset, channel).  The weight gradient works on steps of
+ * MINK_BIGK_WGRAD_ROWS rows, skips an offset none of them has, splits the rows over workgroups and sums the splits in order
+ * through `workspace` (>= mink_conv_bigk_wgrad_workspace_bytes()). */
+#define MINK_BIGK_MAX_K 343
+#define MINK_BIGK_ROW_TILE 64
+#define MINK_BIGK_WGRAD_ROWS 32
+int mink_conv_bigk_gather_gemm(const float *x, int64_t n_in, int32_t ldx, int32_t cin, const float *w, int32_t w_transposed,
+                               int32_t flip_k, const int32_t *nbr, int64_t n_out, int32_t K, float *y, int32_t ldy, int32_t cout,
+                               const float *bias, void *stream);
+int64_t mink_conv_bigk_wgrad_workspace_bytes(int64_t n_out, int32_t K, int32_t cin, int32_t cout);
+int mink_conv_bigk_wgrad(const float *x, int64_t n_in, int32_t ldx, int32_t cin, const float *dy, int32_t ldy, int32_t cout,
+                         const int32_t *nbr, int64_t n_out, int32_t K, float *dw, void *workspace, int64_t workspace_bytes,
+                         void *stream);
 
 /* ------------------------------------------------------------------ dense GEMM, classifier head and loss (csrc/dense.hip) */
 /* Data gradient of a 1x1x1 convolution as a plain GEMM: y[n][N] = x[n][Kd] @ W^T with the FORWARD kernel W[N = cin][Kd = cout]

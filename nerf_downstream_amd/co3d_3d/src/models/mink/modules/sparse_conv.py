@@ -69,6 +69,9 @@ class _WeightSparse:
         self.layout = layout
         if self.use_mm:  # a plain matrix product stays one (reference :347)
             return
+        if self.kernel.shape[0] > 27:
+            raise ValueError(f"sparsify: the weight-sparse kernel holds 27 offsets at most; this kernel has {self.kernel.shape[0]} "
+                             "(kernel sizes 5 and 7 run dense, through ME.MinkowskiConvolution)")
         with torch.no_grad():
             w = self.kernel.detach()
             if self.sparse_mode is SparseConvMode.ZAXIS:

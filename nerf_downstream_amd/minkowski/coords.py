@@ -42,6 +42,7 @@ def _as_int(v):
 
 
 _OFFSET_CACHE = {}
+CUBE_KERNEL_SIZES = (5, 7)  # centred cubes beyond 27 offsets: mink_kernel_map_cube, csrc/conv_bigk.hip
 
 # Process-wide overflow sink of the block-index builds (include/mink_hip.h: mink_set_overflow_sink): a pinned host word the insert
 # kernel sets when a table was given fewer slots than its map has blocks -- rows are then MISSING from the neighbour tables.  The
@@ -282,7 +283,10 @@ class CoordinateManager:
         for _, ts_in, ts_out, ks, dil, transposed in ops:
             ent = self.tables.get((ts_in, ts_out, ks, dil))
             if ts_in in self.levels and ts_out in self.levels and (ent is None or (transposed and ent[1] is None)):
-                todo.append((ts_in, ts_out, ks, dil, transposed))
+                if ks > 3:
+                    self._build_cube_table(ts_in, ts_out, ks, dil, transposed)
+                else:
+                    todo.append((ts_in, ts_out, ks, dil, transposed))
         if not todo:
             return
         check_block_index_overflow()  # (an earlier batch's builds; arms the sink on first use)
@@ -332,6 +336,21 @@ class CoordinateManager:
         self._blk_pool = bpool  # (scratch of the call; kept until the manager goes so no stream bookkeeping is needed)
         for ts_in, (cap, boff, _, n_pad) in blk.items():  # the builds' overflow words (MinkKernelMapDesc.blk_counter)
             self._blk_flags[ts_in] = bpool[boff + 5 * cap + 2 * n_pad : boff + 5 * cap + 2 * n_pad + 1]
+
+    def _build_cube_table(self, ts_in, ts_out, ks, dil, transposed):
+        """The table of a 5^3 / 7^3 cube (mink_kernel_map_cube): beyond the 27 offsets a MinkKernelMapDesc holds, so one call
+        per table, through a per-voxel hash map the entry fills itself in its workspace."""
+        if ks not in CUBE_KERNEL_SIZES:
+            raise ValueError(f"kernel size {ks}: neighbour tables are implemented for kernel sizes 1, 2, 3 and the centred cubes 5 and 7")
+        L, lin, lout, K = lib(), self.levels[ts_in], self.levels[ts_out], ks ** 3
+        if lout.n * K >= 2 ** 31 or (transposed and lin.n * K >= 2 ** 31):
+            raise ValueError(f"kernel size {ks}: a table of {max(lout.n, lin.n)} rows x {K} offsets overflows int32 indexing")
+        nbr = self._take((lout.n, K), torch.int32)
+        nbr_t = self._take((lin.n, K), torch.int32) if transposed else None
+        ws = self._take(int(L.mink_kernel_map_cube_workspace_bytes(lin.n)), torch.uint8)
+        check(L.mink_kernel_map_cube(lin.coords.data_ptr(), lin.n, lout.coords.data_ptr(), lout.n, ks, dil * ts_in, nbr.data_ptr(),
+                                     None if nbr_t is None else nbr_t.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        self.tables[(ts_in, ts_out, ks, dil)] = (nbr, nbr_t)
 
     def block_index_ok(self):
         """True when every block index built so far found a slot for every block (one host synchronisation; for tests and
@@ -630,6 +649,12 @@ class CoordinateManager:
         assert not is_transpose, "transposed kernel maps are out of scope"
         nbr, _ = self.kernel_table(in_key, out_key, kernel_size, dilation)
         n_out, K = nbr.shape
+        if K > 27:  # (mink_rulebook holds 27 offsets; a diagnostic accessor: torch operations on the table, one host read)
+            tt = nbr.t()
+            kk, oo = (tt >= 0).nonzero(as_tuple=True)  # ordered by offset, then by output row
+            ins, c = tt[kk, oo], [0] + torch.bincount(kk, minlength=K).cumsum(0).tolist()
+            oo = oo.to(torch.int32)
+            return {k: torch.stack([ins[c[k] : c[k + 1]], oo[c[k] : c[k + 1]]]) for k in range(K) if c[k + 1] > c[k]}
         L = lib()
         counts = torch.empty(K + 1, dtype=torch.int32, device=self.device)
         ws = torch.empty(int(L.mink_rulebook_workspace_bytes(n_out, K)), dtype=torch.uint8, device=self.device)

@@ -30,7 +30,8 @@ def set_conv_math(mode="fp32"):
     """Arithmetic of the convolution forward / input-gradient GEMMs: "fp32" (exact, default),
     "bf16" (bf16 MFMA operands, fp32 accumulate -- BASELINE config "bf16 mixed precision") or
     "bf16x3" (split-bf16, three products per step).  Tensors in HBM stay fp32; the weight
-    gradient always runs in exact fp32.  Returns the previous mode name."""
+    gradient always runs in exact fp32, and so does every pass of a 5^3 / 7^3 convolution (K > 27, csrc/conv_bigk.hip) in
+    every mode.  Returns the previous mode name."""
     if mode not in _MATH:
         raise ValueError(f"conv math {mode!r}: choose from {sorted(set(_MATH))}")
     old = lib().mink_conv_set_math(_MATH[mode])
@@ -172,6 +173,17 @@ def gather_gemm(x, w, nbr, cout, w_transposed=False, flip_k=False, bias=None, ro
     n_out, K = nbr.shape
     cin = x.shape[1]
     y = torch.empty(n_out, cout, dtype=torch.float32, device=x.device)
+    if K > 27:  # the 5^3 / 7^3 cubes (csrc/conv_bigk.hip): one launch, fp32 in every math mode, no statistics partial
+        if row_perm is not None:
+            raise ValueError(f"gather_gemm: a row permutation with kernel volume {K} is not implemented (27 offsets at most)")
+        note_table(nbr)
+        check(
+            L.mink_conv_bigk_gather_gemm(
+                x.data_ptr(), x.shape[0], x.stride(0), cin, w.data_ptr(), int(w_transposed), int(flip_k), nbr.data_ptr(), n_out, K,
+                y.data_ptr(), cout, cout, _ptr(bias), _stream(),
+            )
+        )
+        return (y, None) if stats else y
     n_rows = n_out if row_perm is None else row_perm.numel()
     ksplit = _FORCE_KSPLIT or _plan_ksplit(L, n_rows, K, cin, cout, int(row_perm is not None))
     ws = _scratch(4 * ksplit * n_out * cout, x.device, "splitk") if ksplit > 1 else None
@@ -226,7 +238,7 @@ def conv_wgrad(x, dy, nbr, kernel_shape, out=None, on=None):
     raw = _stream() if on is None else on.cuda_stream
     note_table(nbr)
     check(
-        L.mink_conv_wgrad(
+        (L.mink_conv_bigk_wgrad if K > 27 else L.mink_conv_wgrad)(
             x.data_ptr(), x.shape[0], x.stride(0), cin, dy.data_ptr(), dy.stride(0), cout, nbr.data_ptr(), n_out, K,
             dw.data_ptr(), ws.data_ptr(), ws.numel(), raw,
         )
@@ -248,7 +260,7 @@ def _cached_plan(key, query):
 
 
 def _wgrad_ws_bytes(L, n_out, K, cin, cout):
-    return _cached_plan(("wws", n_out, K, cin, cout), L.mink_conv_wgrad_workspace_bytes)
+    return _cached_plan(("wws", n_out, K, cin, cout), L.mink_conv_bigk_wgrad_workspace_bytes if K > 27 else L.mink_conv_wgrad_workspace_bytes)
 
 
 def _plan_ksplit(L, n_rows, K, cin, cout, classes):
@@ -270,7 +282,7 @@ class ConvolutionFunction(torch.autograd.Function):
         w = _f32c(kernel)
         cin = x.shape[1]
         ctx.cin = cin
-        if cin % 4 and not ctx.needs_input_grad[0]:
+        if cin % 4 and not ctx.needs_input_grad[0] and w.shape[0] <= 27:  # (the K > 27 kernels have no alignment needs)
             # e.g. the reference default features=["sh"] (27 channels): one zero column puts the
             # rows on 16-byte boundaries so the vectorised / flattened-K kernels apply
             pad = 4 - cin % 4

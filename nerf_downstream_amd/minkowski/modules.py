@@ -74,6 +74,19 @@ class MinkowskiNetwork(nn.Module):
         self.D = D
 
 
+KERNEL_SIZES = (1, 2, 3, 5, 7)
+
+
+def _kernel_size(kernel_size):
+    """The edge of a cubic kernel the convolution kernels implement, or ValueError naming what they do."""
+    ks = list(kernel_size) if isinstance(kernel_size, (list, tuple)) else [kernel_size]
+    if len(set(int(k) for k in ks)) != 1 or int(ks[0]) not in KERNEL_SIZES:
+        raise ValueError(f"kernel_size={kernel_size!r}: implemented are the cubic kernels of size 1, 2 (offsets {{0,1}}), 3, 5 and 7 "
+                         "(centred; 5 and 7 through csrc/conv_bigk.hip, fp32, strides 1 and 2); other sizes and anisotropic "
+                         "kernels are not")
+    return int(ks[0])
+
+
 class MinkowskiConvolution(nn.Module):
     """ME.MinkowskiConvolution as called by `conv()` (modules/common.py:116-125).
 
@@ -87,8 +100,7 @@ class MinkowskiConvolution(nn.Module):
         assert dimension == 3, "the HIP backend implements dimension=3"
         assert kernel_generator is None and not expand_coordinates, "custom kernel generators are out of scope"
         self.in_channels, self.out_channels = in_channels, out_channels
-        self.kernel_size, self.stride, self.dilation = _as_int(kernel_size), _as_int(stride), _as_int(dilation)
-        assert self.kernel_size in (1, 2, 3), "kernel sizes 1, 2 (offsets {0,1}) and 3 (centred) are implemented"
+        self.kernel_size, self.stride, self.dilation = _kernel_size(kernel_size), _as_int(stride), _as_int(dilation)
         self.kernel_volume = self.kernel_size ** 3
         self.dimension = dimension
         self.use_mm = self.kernel_volume == 1 and self.stride == 1
@@ -124,7 +136,8 @@ class MinkowskiConvolution(nn.Module):
 
             def table_fn(transposed, m=m, in_key=in_key, out_key=out_key):
                 nbr, nbr_t = m.kernel_table(in_key, out_key, ks, dil, transposed=transposed)
-                perm = m.class_perm(in_key) if transposed and self.stride == 2 else None
+                # (the 5^3 / 7^3 data gradient reads the transposed table as it is: no parity-class permutation)
+                perm = m.class_perm(in_key) if transposed and self.stride == 2 and ks <= 3 else None
                 return nbr, nbr_t, perm
 
             # stride 1 and an odd (centred) kernel: the transposed table is the table itself with the offsets
@@ -163,6 +176,9 @@ class MinkowskiConvolutionTranspose(MinkowskiConvolution):
         super().__init__(in_channels, out_channels, kernel_size, stride, dilation, bias, kernel_generator,
                          expand_coordinates, convolution_mode, dimension)
         assert self.stride == 2 and not self.use_mm, "the HIP backend up-samples by 2 (upsample_stride=2)"
+        if self.kernel_size > 3:
+            raise ValueError(f"MinkowskiConvolutionTranspose(kernel_size={self.kernel_size}): transposed convolutions are implemented "
+                             "for kernel sizes 2 and 3 (the 5 and 7 cubes only for MinkowskiConvolution)")
         stdv = 1.0 / math.sqrt(self.out_channels * self.kernel_volume)
         with torch.no_grad():
             self.kernel.uniform_(-stdv, stdv)
