@@ -766,6 +766,41 @@ int mink_segment_sum(const float *x, int32_t ldx, int32_t C, const int32_t *memb
 int mink_segment_mean_bwd(const float *dy, int32_t ldy, int32_t C, const int32_t *members, const int32_t *seg, int64_t n_out,
                           int64_t n_members, int64_t n_in, float *dx, int32_t lddx, void *stream);
 
+/* ------------------------------------------------------------------ generative decoders: children and pruning (csrc/generate.hip)
+ * Coordinate maps a network makes and unmakes (ME.MinkowskiGenerativeConvolutionTranspose, ME.MinkowskiPruning): int32
+ * coordinate rows (b, x, y, z), 16-byte aligned; feature rows as in the pooling and field families above (fp32, row pitch,
+ * 16-byte lanes when C % 4 == 0 and every pitch and pointer allows, dword lanes otherwise, -1 = absent).  No atomics, and no
+ * kernel waits for memory that another workgroup of the same launch writes.
+ *
+ * Children of the parents coords[n][4] at the even tensor stride ts: children[8 p + k] = (b, x + (k & 1) h, y + ((k >> 1) & 1) h,
+ * z + ((k >> 2) & 1) h), h = ts / 2 -- the offsets of a size-2 kernel at tensor stride ts / 2, x fastest.  Parents that are
+ * multiples of ts inside the 16-bit key range have children inside it (no status word); children of distinct parents are
+ * distinct. */
+int mink_generate_children(const int32_t *coords, int64_t n, int32_t ts, int32_t *children, void *stream);
+
+/* Rows one workgroup of mink_prune_compact owns: row counts next to its multiples are where the compaction can go wrong. */
+#define MINK_PRUNE_BLOCK 256
+/* Stable compaction of the rows i < n with mask[i] != 0 (one byte per row: a torch bool tensor), n >= 1, B samples:
+ *   kept[n]          : first *total entries: the kept old rows, ascending
+ *   old2new[n]       : the new row of every old row, -1 for a pruned one
+ *   out_coords[n][4] : first *total rows: coords of the kept rows
+ *   batch_offsets[B + 1] : row ranges of the samples among the KEPT rows (the batch column of coords is non-decreasing); a
+ *                      sample that lost every voxel has an empty range, batch_offsets[B] = *total
+ *   total            : device int32
+ * Three launches -- counts per MINK_PRUNE_BLOCK rows, one workgroup scanning the counts, the scatter -- through `workspace`
+ * (mink_prune_workspace_bytes(n), 8-byte aligned). */
+int64_t mink_prune_workspace_bytes(int64_t n);
+int mink_prune_compact(const uint8_t *mask, const int32_t *coords, int64_t n, int32_t B, int32_t *kept, int32_t *old2new,
+                       int32_t *out_coords, int32_t *batch_offsets, int32_t *total, void *workspace, int64_t workspace_bytes,
+                       void *stream);
+/* Forward of the pruning: y[j][:] = x[kept[j]][:], j < n_out (zeros where kept[j] is outside 0 .. n_in - 1). */
+int mink_prune_gather(const float *x, int32_t ldx, int64_t n_in, int32_t C, const int32_t *kept, int64_t n_out, float *y, int32_t ldy,
+                      void *stream);
+/* Its backward in one pass: dx[i][:] = dy[old2new[i]][:] for a kept row, zeros for a pruned one (old2new[i] < 0), i < n_in --
+ * every row of dx is written exactly once. */
+int mink_prune_gather_bwd(const float *dy, int32_t ldy, int64_t n_out, int32_t C, const int32_t *old2new, int64_t n_in, float *dx,
+                          int32_t lddx, void *stream);
+
 /* ------------------------------------------------------------------ elementwise (csrc/elementwise.hip) */
 /* Elementwise: mode 0: y = max(x,0); mode 1: dx = (y>0) ? dy : 0 (a=dy,b=y);
  * mode 2: y = a + b. */

@@ -193,6 +193,7 @@ class CoordinateManager:
         self._boff = {}
         self._batch_size = None
         self._batch_checked = False
+        self._base_ts = 1  # tensor stride of the finest level (above 1 only for a manager of from_coordinates)
         self.trace = []  # every map request, in order: lets the next batch be prepared ahead of use
         self._pending_field = None  # pyramid launched, row counts not read back yet (insert_field(defer=True))
         self.prepared = False
@@ -462,6 +463,30 @@ class CoordinateManager:
             self.finish_field()
         return CoordinateMapKey(1)
 
+    @classmethod
+    def from_coordinates(cls, coords, tensor_stride, batch_size, batch_offsets=None):
+        """A DERIVED manager: one whose finest level is the int32 rows coords[n, 4] at `tensor_stride` (which may be above 1)
+        -- the map an operator made inside a network (MinkowskiPruning, MinkowskiGenerativeConvolutionTranspose), on a
+        manager of its own as TensorField.splat() does.  The rows must be unique, multiples of `tensor_stride` and contiguous
+        per batch index (the callers guarantee it; duplicates raise ValueError); they keep their order.  `batch_size` is the
+        parent's batch count -- a sample may have no row left; `batch_offsets` (int32 [B + 1], device) when the caller has
+        them already.  Built on demand through the path stride() takes (one host read of the row count): a plan recorded for
+        `prepare_ahead` never covers a derived manager, its maps are built where they are first asked for."""
+        assert coords.is_cuda and coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 4
+        ts, n = int(tensor_stride), coords.shape[0]
+        if n == 0:
+            raise ValueError("empty coordinate map")
+        m = cls(D=3, device=coords.device)
+        lev, _, _ = m._unique(coords.contiguous(), 1, n, ts)
+        if lev.n != n:
+            raise ValueError(f"from_coordinates: {n - lev.n} of {n} rows repeat an earlier one at tensor stride {ts}")
+        m.levels[ts], m._base_ts, m._batch_size = lev, ts, int(batch_size)
+        if batch_offsets is not None:
+            m._boff[ts] = batch_offsets
+            m._batch_checked = True  # (they come from the kernel that made the rows)
+        m._note_lazy(lev.coords, lev.tkeys, lev.tvals, batch_offsets)
+        return m
+
     def finish_field(self):
         """The one host synchronisation of the whole pyramid: read the row counts back and
         publish the levels.  No-op when nothing is pending."""
@@ -698,7 +723,7 @@ class CoordinateManager:
     def batch_size(self):
         if not self._batch_checked:
             self._batch_checked = True
-            self.batch_offsets(CoordinateMapKey(1))  # validates that the batch column is sorted
+            self.batch_offsets(CoordinateMapKey(self._base_ts))  # validates that the batch column is sorted
         return self._batch_size
 
     def batch_offsets(self, key):
@@ -712,7 +737,7 @@ class CoordinateManager:
             status = self._take(1, torch.int32)
             status.zero_()
             check(lib().mink_batch_offsets(lev.coords.data_ptr(), lev.n, B, boff.data_ptr(), status.data_ptr(), _stream()))
-            if key.ts == 1 and int(status.item()) & _STATUS_UNSORTED:
+            if key.ts == self._base_ts and int(status.item()) & _STATUS_UNSORTED:
                 raise ValueError("batch indices must be non-decreasing (use ME.utils.sparse_collate)")
             self._boff[key.ts] = boff
             self._note_lazy(boff)
