@@ -1538,6 +1538,41 @@ int mink_attn_bwd(const float *qkv, int32_t ldq, const float *out, int32_t ldo, 
                   int64_t B, int32_t N, int32_t H, int32_t D, float scale, float *dqkv, int32_t lddq, void *workspace,
                   int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ multi-head self-attention on bf16 rows (csrc/attn16.hip)
+ * The attention of a mixed-precision Vision Transformer: the entry points above with qkv, out, dout and dqkv in bf16 (`void *`,
+ * as for mink_stem_conv_bf16s) and the products on v_mfma_f32_16x16x32_bf16.  The row layout, the pitches (in ELEMENTS) and the
+ * shape limits are those of mink_attn_fwd / mink_attn_bwd; lse and the delta workspace, both [B][H][N], are fp32.
+ *
+ * The arithmetic contract (tests/attn16_restate.py derives its bounds from it):
+ *   Every product runs on the bf16 MFMA with fp32 accumulation.
+ *   Everything else is fp32, except these roundings to bf16 (round to nearest even, relative error <= U16 = 2^-8):
+ *     F1: bf16(exp(s - m)) as the operand of P V.  The row sum l, and so lse, use the unrounded fp32 weights.
+ *     F2: the stored out.
+ *     B1: bf16(exp(s - lse)) as the operand of dV = P^T dO.
+ *     B2: bf16(P o (dP - delta)) as the operand of dQ and dK.  It is formed in fp32 from the unrounded P.
+ *     B3: the stored dqkv, after the scale.
+ *   delta_i = sum_d dO_id out_id is an fp32 sum over the stored, rounded out.
+ *   Never rounded to bf16: the scores; dP, delta, m, l and lse; the online-softmax rescale factors; the O, dQ, dK and dV
+ *   accumulators before their final store.
+ *   The maximum (forward) or lse (backward) is subtracted before every exponential.
+ *   `scale` multiplies the finished dot product.
+ *
+ * No atomics, every sum in a fixed order: two calls on the same inputs give the same bits.  mink_attn_bwd_b16 launches three
+ * kernels as mink_attn_bwd does (delta into the workspace, a key-owning kernel for dk and dv, a query-owning kernel for dq).
+ *
+ * bf16 pointers 2-byte aligned, lse 4-byte aligned, the workspace 8-byte aligned and of at least
+ * mink_attn_bwd_b16_workspace_bytes() bytes; anything else, and any shape mink_attn_fwd refuses, is MINK_EINVAL before any
+ * launch.  Only the logical columns of the logical rows are read or written: pad columns may hold NaN and keep their bits, token
+ * rows past N of a tile are neither read nor stored, every logical output element is written exactly once.  16-byte loads and
+ * 8-byte stores when every matrix pointer of the call is 16-byte aligned and every pitch a multiple of 8 elements, 2-byte
+ * accesses otherwise, with identical results bit for bit. */
+int64_t mink_attn_bwd_b16_workspace_bytes(int64_t B, int64_t N, int32_t H, int32_t D);
+int mink_attn_fwd_b16(const void *qkv, int32_t ldq, int64_t B, int32_t N, int32_t H, int32_t D, float scale, void *out, int32_t ldo,
+                      float *lse, void *stream);
+int mink_attn_bwd_b16(const void *qkv, int32_t ldq, const void *out, int32_t ldo, const float *lse, const void *dout, int32_t lddo,
+                      int64_t B, int32_t N, int32_t H, int32_t D, float scale, void *dqkv, int32_t lddq, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ grouped convolution (csrc/gconv.hip)
  * The 3x3 layers of the ResNeXt networks of the 2-D comparison (torchvision's Bottleneck with groups = 32): a convolution over
  * a neighbour table whose G groups do not mix.  Rows are [n][ld] fp32; group g owns the input columns g cg_in .. (g + 1) cg_in and

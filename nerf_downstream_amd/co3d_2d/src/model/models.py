@@ -3,7 +3,8 @@ torchvision ResNet (zero_init_residual=True) with its `fc` replaced by Identity,
 Linear(in_features, 51).  The ResNet itself is defined here on the dense layers of model/dense.py with torchvision's
 module and parameter names (`model.conv1.weight`, `model.layer1.0.bn2.running_var`, `model.layer2.0.downsample.0.weight`
 ...), so a torchvision checkpoint loads unchanged.  `ViTBased` (:37-54) wraps the Vision Transformer of model/vit.py, which
-keeps timm's parameter names (`model.blocks.0.attn.qkv.weight` ...) and runs its attention in csrc/attn.hip; `select_model`
+keeps timm's parameter names (`model.blocks.0.attn.qkv.weight` ...) and runs its attention in csrc/attn.hip (csrc/attn16.hip
+with `ViTBased.math = "bf16"`); `select_model`
 routes the three `vit_*_patch16_224` names of the reference's configs to it.  The Bottleneck networks (`resnet50/101/152`,
 `wide_resnet50_2/101_2`, `resnext50_32x4d`, `resnext101_32x8d`) are torchvision's too: stride on the 3x3 `conv2`, and for
 ResNeXt a grouped `conv2` (32 groups) that runs in csrc/gconv.hip.  The `deit3_*` names of the reference's list (layer scale,
@@ -155,16 +156,21 @@ class ResNetBased(nn.Module):
 
 @gin.configurable
 class ViTBased(nn.Module):
-    """`img_size` (extension, for tests and small runs): a multiple of 16; `pos_embed` is sized to it."""
+    """`img_size` (extension, for tests and small runs): a multiple of 16; `pos_embed` is sized to it.  `math`: "fp32", or
+    "bf16" for the mixed-precision blocks of model/vit.py (bf16 linears, attention in csrc/attn16.hip); it goes with
+    `run.precision = 16`, and the parameters and the state dict are the same in both."""
 
-    def __init__(self, model="vit_small_patch16_224", pretrained=False, img_size=224):
+    def __init__(self, model="vit_small_patch16_224", pretrained=False, img_size=224, math="fp32"):
         super().__init__()
+        if math not in vit.MATHS:
+            raise ValueError(f"ViTBased.math={math!r}: one of {vit.MATHS}")
+        self.math = math
         if model not in vit.SIZES:
             raise NameError(f"Unknown model name : {model} (Vision Transformers {sorted(vit.SIZES)} are built here)")
         if pretrained:
             raise NotImplementedError("no network access for pretrained weights: load a timm state dict instead")
         dim, depth, heads = vit.SIZES[model]
-        self.model = vit.VisionTransformer(img_size=img_size, dim=dim, depth=depth, heads=heads, num_classes=51)
+        self.model = vit.VisionTransformer(img_size=img_size, dim=dim, depth=depth, heads=heads, num_classes=51, math=math)
 
     def forward(self, x):
         return self.model(x)

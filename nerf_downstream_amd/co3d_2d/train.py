@@ -3,8 +3,11 @@
 gin names (`run.*`, `LitModel.*`, `DataModule.*`, `ResNetBased.*`, `ViTBased.*`) as the reference's co3d_2d/train.py:39-122,164-171,
 as a plain loop instead of a Lightning Trainer.  `run.precision = 16` runs the convolutions on the bf16 matrix cores
 (fp32 accumulate and storage); every convolution, batch norm and pooling is a hand-written gfx950 kernel
-(src/model/dense.py).  The Vision Transformers (configs/vit*.gin, src/model/vit.py) run in fp32 only: `run.precision = 16` with
-one of them is refused.  The grouped 3x3 layers of the ResNeXt networks (configs/resnext*.gin, csrc/gconv.hip) are fp32 in, fp32
+(src/model/dense.py).  The Vision Transformers (src/model/vit.py) run in fp32 by default (configs/vit{small,base,large}.gin) and
+mixed with `ViTBased.math = "bf16"` (configs/vit*_bf16.gin: bf16 linears, attention on the bf16 matrix cores in csrc/attn16.hip,
+fp32 residual stream, norms and master weights).  `run.precision` and `ViTBased.math` must agree: 16 with the default
+math="fp32" is refused (a ViT never runs mixed silently), and so is 32 with math="bf16".  The grouped 3x3 layers of the
+ResNeXt networks (configs/resnext*.gin, csrc/gconv.hip) are fp32 in, fp32
 accumulate and fp32 out whatever `run.precision` says: with 16 the 1x1 layers around them run on the bf16 matrix cores and the
 grouped layers do not follow.
 
@@ -44,7 +47,10 @@ def run(ckpt_path, resume_training, seed, run_name="resnet18", num_gpus=1, log_e
     os.makedirs(out_dir, exist_ok=True)
     data = DataModule()
     model = LitModel().to(dev)
-    if int(precision) == 16 and isinstance(model.model, ViTBased):
+    if int(precision) != 16 and isinstance(model.model, ViTBased) and model.model.math == "bf16":
+        raise ValueError(f"{model.model_name}: ViTBased.math = \"bf16\" goes with run.precision = 16, not run.precision = "
+                         f"{precision}; bind both (configs/vit*_bf16.gin do) or neither")
+    if int(precision) == 16 and isinstance(model.model, ViTBased) and model.model.math != "bf16":
         raise NotImplementedError(f"{model.model_name}: the attention kernel is fp32 only and a ViT does not run mixed; "
                                   "set run.precision = 32 (configs/vit*.gin do)")
     opt = model.configure_optimizers()

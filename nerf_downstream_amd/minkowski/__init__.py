@@ -34,7 +34,7 @@ from .modules import (  # noqa: F401
     cat,
 )
 from .generative import MinkowskiGenerativeConvolutionTranspose, MinkowskiPruning  # noqa: F401
-from .functional import attention, seg_cross_entropy, set_conv_math, set_conv_storage, slice_rows  # noqa: F401
+from .functional import attention, attention_b16, seg_cross_entropy, set_conv_math, set_conv_storage, slice_rows  # noqa: F401
 from .tensor import SparseTensor, TensorField  # noqa: F401
 
 

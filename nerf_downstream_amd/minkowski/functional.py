@@ -482,7 +482,7 @@ class ConvBNReLUSumPoolFunction(torch.autograd.Function):
 # Every public name that moved to a module of its own, so that `functional.<name>` stays valid.  Functions only: the
 # mutable state of streams.py is read there (`streams.X`), never copied here.
 from ._rt import _bytes, _check_offsets, _row_stride  # noqa: E402,F401
-from .attn import AttentionFunction, attention  # noqa: E402,F401
+from .attn import AttentionB16Function, AttentionFunction, attention, attention_b16  # noqa: E402,F401
 from .eltwise import ACT_KINDS, ActivationFunction, AddFunction, ReLUFunction, _eltwise  # noqa: E402,F401
 from .field import FieldGatherCatFunction, SegmentMeanFunction, field_batch_offsets, index_csr, lazy_index_csr, segment_mean  # noqa: E402,F401
 from .gconv import GroupedConvolutionFunction, gconv, gconv_wgrad  # noqa: E402,F401
