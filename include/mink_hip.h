@@ -55,14 +55,14 @@ extern "C" {
 #define MINK_STATUS_NOT_ASCENDING 4u /* mink_coords_build_levels, informational: the input rows' keys are not strictly ascending
                                         (when CLEAR the rows were their own unique rows and level 0's hash map was left empty) */
 
-/* ------------------------------------------------------------------ error text and ABI version (csrc/coords.hip) */
+/* ------------------------------------------------------------------ error text and ABI version (csrc/lib.hip) */
 const char *mink_last_error(void);
 /* 2: every scratch buffer is passed with its size; 3: MinkStem.xb (bf16 storage); 4: mink_net_* (the whole trunk per call).
  * A caller compiled or bound against this header refuses a library that answers another number. */
 #define MINK_ABI_VERSION 4
 int mink_abi_version(void);
 
-/* ------------------------------------------------------------------ coordinate maps (csrc/coords.hip; the 5^3 / 7^3 cube tables: csrc/conv_bigk.hip)
+/* ------------------------------------------------------------------ coordinate maps (csrc/coords.hip)
  * Coordinate hash map: open addressing, linear probing, 64-bit packed keys
  * (16 bits each for batch | x+2^15 | y+2^15 | z+2^15), int32 values.
  * Replaces ME's CoordinateMapCPU/GPU (insert_and_map / stride / kernel_map) behind
@@ -125,6 +125,13 @@ int mink_coords_build_levels(const void *coords, int mode, int64_t n, int32_t nl
                              int32_t *const *index_a, int32_t *const *index_b, int32_t *meta,
                              void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Row ranges of each batch index in a coordinate list whose batch column is
+ * non-decreasing (guaranteed by ME.utils.sparse_collate, data/utils.py:25-30).
+ * batch_offsets[B+1].  Sets MINK_STATUS_UNSORTED otherwise.  (ME origin_map.) */
+int mink_batch_offsets(const int32_t *coords, int64_t n, int32_t B, int32_t *batch_offsets,
+                       uint32_t *status, void *stream);
+
+/* ------------------------------------------------------------------ neighbour tables (csrc/kmap.hip; the 5^3 / 7^3 cube tables: csrc/conv_bigk.hip) */
 /* Kernel map as a neighbour table: for every output row o and offset k probe the INPUT
  * map at out_coords[o] + offsets[k].  offsets_host[K][3] are already scaled by
  * dilation * input tensor stride.  If nbr_t != NULL it must be pre-filled with -1
@@ -189,6 +196,7 @@ int mink_kernel_map_cube(const int32_t *in_coords, int64_t n_in, const int32_t *
  * promise without a device synchronisation or a copy -- one batch late at most, instead of silently missing neighbours. */
 int mink_set_overflow_sink(int32_t *host_word);
 
+/* ------------------------------------------------------------------ rulebook and parity classes: derived orders of a table or a map (csrc/rulebook.hip) */
 /* ME-format rulebook from a neighbour table: per offset k the (in,out) pairs ordered
  * by output row, built with wave64 ballot + prefix sums.
  *   counts[K+1]      : exclusive scan of pairs per offset (device, int32)
@@ -219,12 +227,6 @@ typedef struct MinkClassPartitionDesc {
   int64_t workspace_bytes;
 } MinkClassPartitionDesc;
 int mink_class_partition_batch(int32_t n_maps, const MinkClassPartitionDesc *descs, void *stream);
-
-/* Row ranges of each batch index in a coordinate list whose batch column is
- * non-decreasing (guaranteed by ME.utils.sparse_collate, data/utils.py:25-30).
- * batch_offsets[B+1].  Sets MINK_STATUS_UNSORTED otherwise.  (ME origin_map.) */
-int mink_batch_offsets(const int32_t *coords, int64_t n, int32_t B, int32_t *batch_offsets,
-                       uint32_t *status, void *stream);
 
 /* ------------------------------------------------------------------ sparse convolution (csrc/conv.hip, csrc/conv_wgrad.hip; kernel volumes above 27: csrc/conv_bigk.hip)
  * Replaces ME ConvolutionForward/BackwardKernel behind ME.MinkowskiConvolution
@@ -822,7 +824,7 @@ int mink_activation(const float *x, const float *gy, const float *slope, int32_t
  * zero_grad != 0 clears g behind the update (the next step's zero_grad memset).  One pass over 6 n floats. */
 int mink_sgd_step(float *w, float *g, float *m, int64_t n, float lr, float momentum, float weight_decay, int32_t zero_grad, void *stream);
 
-/* ------------------------------------------------------------------ dataset front-end (csrc/coords.hip)
+/* ------------------------------------------------------------------ dataset front-end (csrc/plenoxel.hip)
  * PeRFception-CO3D `data.npz` batch on the device (reference co3d.py:160-166 de-quantisation,
  * :196-205 links -> coordinates and feature selection): `links[n]` flat indices x*ry*rz + y*rz + z,
  * `density[n]`, `sh_q[n][27]` uint8, per scene b (rows scene_offsets[b] .. scene_offsets[b+1])

@@ -46,6 +46,18 @@ def misaligned(x, requires_grad=False):
     return flat, view
 
 
+def class_perm(cls, pad=128):
+    """mink_class_partition's form from the class (0..7) of every row: rows grouped by class in row order, every segment
+    padded with -1 to a multiple of `pad` (the library's buffer of mink_class_partition_rows entries is this and -1 behind it)."""
+    import torch
+
+    segs = []
+    for c in range(8):
+        rows = torch.nonzero(cls == c).flatten().to(torch.int32)
+        segs += [rows, torch.full(((-len(rows)) % pad,), -1, dtype=torch.int32)]
+    return torch.cat(segs)
+
+
 def trunk_node(out):
     """The native-trunk autograd node (minkowski/trunk.py: TrunkFunction) in the graph of `out`, or None when the forward
     pass went module by module.  (`model._trunk_plan` only says the model COULD take the native trunk: a stem too small for

@@ -45,6 +45,30 @@ def test_argument_validation_without_gpu():
     assert b"multiple of 4" in L.mink_last_error()
 
 
+def test_one_error_text_serves_every_translation_unit():
+    """set_error and the thread-local text behind mink_last_error live in csrc/lib.hip; one refused call into an entry point of
+    each file that took over csrc/coords.hip's kernels (coords.hip, kmap.hip, rulebook.hip, plenoxel.hip) leaves ITS message
+    there.  Every check comes before the first launch: no GPU."""
+    from nerf_downstream_amd import _lib
+
+    L = _lib.lib()
+    P = 0x10000  # aligned, never dereferenced
+    err = L.mink_last_error
+    assert L.mink_coords_make_keys(None, 0, 10, 1, None, None, None) == -1
+    assert err() == b"make_keys: NULL pointer"
+    assert L.mink_kernel_map(None, None, 64, None, 5, None, 28, None, None, None) == -1
+    assert err() == b"kernel_map: kernel volume 28 unsupported (1..27)"
+    need = L.mink_class_partition_workspace_bytes(1000)
+    assert L.mink_class_partition(P, 1000, 2, 128, P, P, need - 1, None) == -1
+    assert err() == f"class_partition: workspace of {need - 1} bytes, {need} needed".encode()
+    assert L.mink_rulebook(P, 1000, 28, P, P, P, P, 1 << 20, None) == -1
+    assert err() == b"rulebook: bad arguments"
+    assert L.mink_decode_plenoxel(P, P, P, P, 1, P, P, 10, 4, 4, 0, 1, -1, -1, None, 28, P, P, 27, None) == -1  # ldf < C
+    assert err() == b"decode_plenoxel: bad shape"
+    assert L.mink_coords_make_keys(None, 2, 10, 1, None, None, None) == -1  # ... and the first file again: the text moved on
+    assert err() == b"make_keys: bad arguments (n=10 ts=1 mode=2)"
+
+
 def test_undersized_workspace_is_refused_before_any_launch():
     """ABI v2: the size of a scratch buffer is an argument, checked against the plan the call is about to launch.  The
     split factors / row splits of a convolution depend on planner state (tuning knobs), so a size cached by the caller

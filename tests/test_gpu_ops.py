@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import batch_scenes
+from helpers import batch_scenes, class_perm
 
 pytestmark = pytest.mark.gpu
 
@@ -721,12 +721,7 @@ def test_row_compacted_kernel_over_permuted_rows_against_float64(n_out, K, cin, 
     else:
         nbr[torch.rand(n_out, K, generator=g) < 0.5] = -1
     # permutation: rows grouped by class, every segment padded with -1 to a multiple of 128 (mink_class_partition's form)
-    segs = []
-    for c in range(8):
-        rows = torch.nonzero(cls == c).flatten().to(torch.int32)
-        pad = (-len(rows)) % 128
-        segs += [rows, torch.full((pad,), -1, dtype=torch.int32)]
-    perm = torch.cat(segs)
+    perm = class_perm(cls)
     x = torch.randn(n_in, cin, generator=g)
     w = torch.randn(K, cin, cout, generator=g) * 0.1
     wk = w.transpose(1, 2).contiguous() if transposed else w

@@ -25,6 +25,7 @@ import pytest
 import torch
 
 import layerwise as LW
+from helpers import class_perm
 
 pytestmark = pytest.mark.gpu
 
@@ -48,12 +49,7 @@ def _table(n_out, K, n_in, g):
 
 def _class_perm(n_out, g):
     """Rows grouped by eight classes, every segment padded with -1 to a multiple of 128 (mink_class_partition's form)."""
-    cls = torch.randint(0, 8, (n_out,), generator=g)
-    segs = []
-    for c in range(8):
-        rows = torch.nonzero(cls == c).flatten().to(torch.int32)
-        segs += [rows, torch.full(((-len(rows)) % 128,), -1, dtype=torch.int32)]
-    return torch.cat(segs)
+    return class_perm(torch.randint(0, 8, (n_out,), generator=g))
 
 
 def _strided(n, c, ld, g, dev):
