@@ -1134,6 +1134,46 @@ int mink_img_finish(const uint8_t *packed, const int64_t *offsets, const int32_t
                     int64_t total_pixels, int32_t B, int32_t width, int32_t S, const void *workspace, int64_t workspace_bytes,
                     float *out, uint8_t *stages, void *stream);
 
+/* ------------------------------------------------------------------ images: background paste (csrc/paste.hip)
+ * The reference's BackgroundAug (co3d_2d/src/data/transforms.py:113-159) for a whole batch, IN PLACE in the packed batch of the
+ * section above, before its chain rounds: the slot of a pasting sample holds the background frame on entry and the composite on
+ * exit.  `packed`, `offsets`, `sizes` as above; `fg`, uint8 [fg_bytes], the HWC RGB frames to paste and `mask`, uint8
+ * [mask_bytes], their mask planes (one byte per pixel), both packed at any byte alignment and neither overlapping `packed`;
+ * `table` [B][MINK_PASTE_PARAMS] int64 on the device, per sample
+ *     FG_OFFSET, MASK_OFFSET   byte offset of its frame in `fg` and of its mask in `mask`
+ *     FG_W, FG_H               size of the frame
+ *     MASK_W, MASK_H           size of the mask (it need not be the frame's)
+ *     RW, RH                   the size both are resized to; RW = 0: the sample does not paste and nothing of it is touched
+ * Frame and mask are resized as Image.resize((RW, RH)) does with Pillow's default filter: BICUBIC (a = -0.5, support
+ * 2 * max(in / out, 1)), horizontal pass first, 8 bits after each pass, coefficients of 22 fractional bits rounded half away
+ * from zero; a pass whose side does not change copies.  With (w, h) the slot's size the rectangle rows [y0, y1) =
+ * [max(0, (h - RH) / 2), min(h, (h + RH) / 2)) -- columns alike -- receives
+ *     out = (uint8) (fg * m + (1 - m) * bg),   m = mask / 255
+ * in double, no product fused with the addition, where fg and mask are read from row RH / 2 - (y1 - y0) / 2 of the resized
+ * images on.  Every other byte of `packed` keeps its value.  One workgroup owns a tile of one rectangle and a thread its own
+ * pixels: no atomics, two calls agree bit for bit.
+ *
+ * max_w, max_h: HOST scalars, the largest rectangle extent of the batch per axis (they size the grid; nothing is read back).
+ * Either 0: no sample pastes and nothing is launched.  A sample whose row does not fit -- offsets outside `fg` / `mask`, a side
+ * outside 1 .. MINK_PASTE_MAX_SIDE, a slot that is not the one `offsets` and `sizes` describe, a rectangle larger than
+ * max_w x max_h -- is skipped whole: nothing of it is read or written. */
+enum {
+  MINK_PASTE_FG_OFFSET = 0,
+  MINK_PASTE_MASK_OFFSET = 1,
+  MINK_PASTE_FG_W = 2,
+  MINK_PASTE_FG_H = 3,
+  MINK_PASTE_MASK_W = 4,
+  MINK_PASTE_MASK_H = 5,
+  MINK_PASTE_RW = 6,
+  MINK_PASTE_RH = 7,
+  MINK_PASTE_PARAMS = 8,
+  MINK_PASTE_MAX_SIDE = 1048576
+};
+
+int mink_img_paste(uint8_t *packed, const int64_t *offsets, const int32_t *sizes, int64_t total_pixels, int32_t B, const uint8_t *fg,
+                   int64_t fg_bytes, const uint8_t *mask, int64_t mask_bytes, const int64_t *table, int32_t max_w, int32_t max_h,
+                   void *stream);
+
 /* ------------------------------------------------------------------ whole residual blocks (csrc/trunk.hip)
  * One call = the complete launch sequence of one stage of the reference network, so the host pays one FFI call per
  * block instead of one per kernel (a Mink-ResNet14 step is ~300 launches; issued one by one from a Python autograd

@@ -6,7 +6,9 @@ a textured background, normalised like ImageNet inputs -- with the same sample d
 `DataModule(source="files")` reads frames instead (loader.py:73-227 of the reference): `Co3DTrainDataset`, `Co3DEvalDataset` and
 their PeRFCeption twins keep the reference's classes, file lists ("<class> <scene> <frames>" per line) and directory layout.  A
 worker only decodes the frame to uint8 and draws the recipe (transforms.py, augmix.py); `collate_images` packs the batch and the
-trainer hands it to `minkowski.utils.prepare_image_batch`, which runs AugMix and the recipe on the GPU (csrc/image.hip)."""
+trainer hands it to `minkowski.utils.prepare_image_batch`, which runs AugMix and the recipe on the GPU (csrc/image.hip).  With
+`PeRFCeptionCo3DTrainDataset.bkgd_on_device` a pasting sample also carries its render and mask, and the same call pastes the render
+over the background first (csrc/paste.hip)."""
 import os
 
 import numpy as np
@@ -70,13 +72,26 @@ def _decode(path):
         return np.array(im.convert("RGB"), dtype=np.uint8)
 
 
+def _decode_mask(path):
+    """Band 0 of a mask file, uint8 [H,W].  A single-band mask is taken as it is (an extension: the reference indexes band 0 of
+    an array that then has none); an alpha band is dropped, not multiplied in."""
+    from PIL import Image
+
+    with Image.open(path) as im:
+        if len(im.getbands()) == 1:
+            return np.array(im.convert("L"), dtype=np.uint8)
+        return np.ascontiguousarray(np.array(im.convert("RGB"), dtype=np.uint8)[..., 0])
+
+
 class _Frames(Dataset):
     """What the four datasets share: a frame is decoded to uint8 [H,W,3] and the recipe is drawn, nothing else."""
 
     def _sample(self, path, label, train):
+        return self._sample_of(_decode(path), label, train)
+
+    def _sample_of(self, x, label, train):
         from .transforms import compile_program
 
-        x = _decode(path)
         size = (x.shape[1], x.shape[0])
         draws = self.augmix.draw(size, self.transforms.draw) if train else self.transforms.draw(size)
         S = (draws["branches"][0] if train else draws)["S"]
@@ -140,12 +155,46 @@ class Co3DEvalDataset(_EvalFrames):
 
 @gin.configurable
 class PeRFCeptionCo3DTrainDataset(_TrainFrames):
+    """`bkgd_aug` is the share of samples whose render is pasted over another scene's background (the reference's loader.py:172-193).
+    The paste runs on the GPU only and changes what a sample and a batch hold, so it is opt-in: `bkgd_on_device=True`.  A scene is
+    <data_root>/<class>/<scene>/ with the renders in fgbg/, the backgrounds in bg/image000.jpg ... and the masks in
+    mask/mask<what follows "image" in the render's name>.  With the binding the draws are the reference's, in its order: the frame,
+    p, and only for p < bkgd_aug the background scene and its frame; then BackgroundAug's scale, then AugMix for a frame of the
+    background's size.  Without it nothing is drawn but the frame, as before."""
     subdir, frames_per_scene = "fgbg", 50
+    bkgd_frames = 50  # frames of a scene's bg/ directory the background is drawn among
 
-    def __init__(self, train_transformations=TRAIN_RECIPE, bkgd_aug=0.0, data_root="co3d_2d/data/perfception", filelist_root="filelist"):
-        if bkgd_aug > 0:
-            raise NotImplementedError("bkgd_aug > 0: BackgroundAug (pasting the frame over another scene's background) is not built")
+    def __init__(self, train_transformations=TRAIN_RECIPE, bkgd_aug=0.0, data_root="co3d_2d/data/perfception", filelist_root="filelist",
+                 bkgd_on_device=False):
+        if bkgd_aug > 0 and not bkgd_on_device:
+            raise NotImplementedError("bkgd_aug > 0: BackgroundAug (pasting the frame over another scene's background) runs on the GPU "
+                                      "only and adds the frame and its mask to every pasting sample: bind "
+                                      "PeRFCeptionCo3DTrainDataset.bkgd_on_device = True (configs/perfception_bkgd.gin)")
         super().__init__(train_transformations, data_root, filelist_root)
+        self.bkgd_aug, self.bkgd_on_device = float(bkgd_aug), bool(bkgd_on_device)
+        if self.bkgd_on_device:
+            from .transforms import BackgroundAug
+
+            self.bkgd_aug_fun = BackgroundAug()
+
+    def __getitem__(self, idx):
+        if not self.bkgd_on_device:
+            return super().__getitem__(idx)
+        random_idx = np.random.randint(self.num_frames[idx])
+        p = np.random.random()
+        fname = sorted(os.listdir(self.files[idx]))[random_idx]
+        fg = _decode(os.path.join(self.files[idx], fname))
+        if not p < self.bkgd_aug:
+            return self._sample_of(fg, self.labels[idx], True)
+        bkgd_idx = np.random.randint(len(self.files))
+        bkgd_frame_idx = np.random.randint(self.bkgd_frames)
+        # (the reference finds both directories by replacing "fgbg" anywhere in the path; here they are the scene's own)
+        bg = _decode(os.path.join(os.path.dirname(self.files[bkgd_idx]), "bg", f"image{bkgd_frame_idx:03d}.jpg"))
+        mask = _decode_mask(os.path.join(os.path.dirname(self.files[idx]), "mask", f"mask{fname[5:]}"))
+        rw, rh = self.bkgd_aug_fun.draw((fg.shape[1], fg.shape[0]))
+        sample = self._sample_of(bg, self.labels[idx], True)
+        sample["paste"] = {"fg": torch.from_numpy(fg), "mask": torch.from_numpy(mask), "size": (rw, rh)}
+        return sample
 
 
 @gin.configurable
@@ -158,17 +207,36 @@ class PeRFCeptionCo3DEvalDataset(_EvalFrames):
 
 def collate_images(samples):
     """Frames of any sizes -> one batch for `prepare_image_batch`: packed uint8 [sum 3wh] (HWC, one image after the other), offsets
-    int64 [B+1] in bytes, sizes int32 [B,2] = (w, h), programs float64 [B, MINK_IMG_PARAMS], size (the S of the recipe), labels."""
+    int64 [B+1] in bytes, sizes int32 [B,2] = (w, h), programs float64 [B, MINK_IMG_PARAMS], size (the S of the recipe), labels.
+    Only when a sample of the batch pastes (it has "paste": its "image" is then the background) the batch also holds paste_fg
+    uint8 [sum 3wh of the pasted frames], paste_mask uint8 [sum wh of their masks] and paste_table int64 [B, MINK_PASTE_PARAMS]."""
     sizes = {int(s["size"]) for s in samples}
     if len(sizes) != 1:
         raise ValueError(f"one output size per batch, got {sorted(sizes)}")
     images = [s["image"] for s in samples]
     nbytes = [im.numel() for im in images]
-    return {"packed": torch.cat([im.reshape(-1) for im in images]),
-            "offsets": torch.tensor(np.concatenate([[0], np.cumsum(nbytes)]), dtype=torch.int64),
-            "sizes": torch.tensor([[im.shape[1], im.shape[0]] for im in images], dtype=torch.int32),
-            "programs": torch.stack([s["program"] for s in samples]), "size": torch.tensor(sizes.pop()),
-            "labels": torch.stack([s["labels"] for s in samples])}
+    batch = {"packed": torch.cat([im.reshape(-1) for im in images]),
+             "offsets": torch.tensor(np.concatenate([[0], np.cumsum(nbytes)]), dtype=torch.int64),
+             "sizes": torch.tensor([[im.shape[1], im.shape[0]] for im in images], dtype=torch.int32),
+             "programs": torch.stack([s["program"] for s in samples]), "size": torch.tensor(sizes.pop()),
+             "labels": torch.stack([s["labels"] for s in samples])}
+    if any("paste" in s for s in samples):
+        from nerf_downstream_amd._lib import constants
+
+        P = constants("MINK_PASTE_")
+        table = torch.zeros(len(samples), P["PARAMS"], dtype=torch.int64)
+        fgs, masks, fo, mo = [], [], 0, 0
+        for b, s in enumerate(samples):
+            if "paste" not in s:
+                continue
+            fg, mask, (rw, rh) = s["paste"]["fg"], s["paste"]["mask"], s["paste"]["size"]
+            for k, v in (("FG_OFFSET", fo), ("MASK_OFFSET", mo), ("FG_W", fg.shape[1]), ("FG_H", fg.shape[0]), ("MASK_W", mask.shape[1]),
+                         ("MASK_H", mask.shape[0]), ("RW", rw), ("RH", rh)):
+                table[b, P[k]] = int(v)
+            fgs.append(fg.reshape(-1)), masks.append(mask.reshape(-1))
+            fo, mo = fo + fg.numel(), mo + mask.numel()
+        batch["paste_fg"], batch["paste_mask"], batch["paste_table"] = torch.cat(fgs), torch.cat(masks), table
+    return batch
 
 
 def images_to_device(batch, device):
@@ -179,8 +247,12 @@ def images_to_device(batch, device):
     from nerf_downstream_amd.minkowski.utils import prepare_image_batch
 
     with torch.cuda.device(device):
+        paste = None
+        if "paste_table" in batch:
+            paste = {"fg": batch["paste_fg"].to(device, non_blocking=True), "mask": batch["paste_mask"].to(device, non_blocking=True),
+                     "table": batch["paste_table"]}
         images = prepare_image_batch(batch["packed"].to(device, non_blocking=True), batch["offsets"], batch["sizes"], batch["programs"],
-                                     size=int(batch["size"]))
+                                     size=int(batch["size"]), paste=paste)
     return {"images": images, "labels": batch["labels"].to(device, non_blocking=True)}
 
 

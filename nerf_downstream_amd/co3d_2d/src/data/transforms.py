@@ -175,8 +175,25 @@ class AugMix(_OnDevice):
 
 @gin.configurable
 class BackgroundAug(_OnDevice):
+    """The render, resized by a random scale with Pillow's default filter, pasted through its mask over the centre of another
+    scene's background (csrc/paste.hip: `mink_img_paste`).  `draw(fg_size)` is the reference's one `np.random.random()`: the
+    resized size (rw, rh) of a frame of fg_size = (w, h)."""
+
     def __init__(self, rescale_range=(0.5, 1.5)):
-        raise NotImplementedError("BackgroundAug (pasting the frame over another scene's background) is not built")
+        lo, hi = float(rescale_range[0]), float(rescale_range[1])
+        if not 0.25 <= lo <= hi <= 4.0:
+            raise ValueError(f"BackgroundAug: rescale_range {tuple(rescale_range)} (0.25 <= min <= max <= 4)")
+        self.rescale_min, self.rescale_max = lo, hi
+
+    def draw(self, fg_size):
+        s = np.random.random() * (self.rescale_max - self.rescale_min) + self.rescale_min
+        rw, rh = int(fg_size[0] * s), int(fg_size[1] * s)
+        if rw < 1 or rh < 1:
+            raise ValueError(f"BackgroundAug: a {fg_size[0]}x{fg_size[1]} frame at scale {s:.3f} has no pixels left")
+        return rw, rh
+
+    def __call__(self, fg=None, bg=None, mask=None):
+        return _OnDevice.__call__(self, fg)
 
 
 _BY_NAME = {c.__name__: c for c in (RandomResizedCrop, ColorJitter, RandomHorizontalFlip, ToTensor, PCALoss, Normalize, CenterCrop,

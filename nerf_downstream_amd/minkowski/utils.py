@@ -519,12 +519,41 @@ def image_batch_check(offsets, sizes, programs, n_bytes):
     return B, int(widths.max())
 
 
-def prepare_image_batch(packed, offsets, sizes, programs, size=224, stages=False):
+def image_paste_check(table, sizes, fg_bytes, mask_bytes):
+    """Host check of the paste table of an image batch (`collate_images`: "paste_table"): int64 [B, MINK_PASTE_PARAMS] against the
+    batch's sizes int32 [B,2] = (w, h) and the byte counts of the packed frames and masks.  Returns (max_w, max_h), the largest
+    paste rectangle of the batch per axis, (0, 0) when no sample pastes.  `mink_img_paste` skips a sample whose row does not fit;
+    here the same thing raises."""
+    from .._lib import constants
+
+    P = constants("MINK_PASTE_")
+    table, sizes = np.asarray(table), np.asarray(sizes)
+    B = sizes.shape[0]
+    if table.shape != (B, P["PARAMS"]) or table.dtype != np.int64 or sizes.shape != (B, 2):
+        raise ValueError(f"paste table: {table.dtype} {table.shape} for {B} images (int64 [B,{P['PARAMS']}])")
+    max_w = max_h = 0
+    for b in np.nonzero(table[:, P["RW"]])[0]:
+        fo, mo, fw, fh, mw, mh, rw, rh = (int(table[b, P[k]]) for k in ("FG_OFFSET", "MASK_OFFSET", "FG_W", "FG_H", "MASK_W", "MASK_H",
+                                                                        "RW", "RH"))
+        if not all(1 <= v <= P["MAX_SIDE"] for v in (fw, fh, mw, mh, rw, rh)):
+            raise ValueError(f"paste table, sample {b}: sides {(fw, fh)}, {(mw, mh)}, {(rw, rh)} (1 .. {P['MAX_SIDE']})")
+        if fo < 0 or fo + 3 * fw * fh > fg_bytes or mo < 0 or mo + mw * mh > mask_bytes:
+            raise ValueError(f"paste table, sample {b}: frame at byte {fo} of {fg_bytes} or mask at byte {mo} of {mask_bytes} does "
+                             "not lie inside its buffer")
+        w, h = int(sizes[b, 0]), int(sizes[b, 1])
+        max_w, max_h = max(max_w, min(w, rw)), max(max_h, min(h, rh))
+    return max_w, max_h
+
+
+def prepare_image_batch(packed, offsets, sizes, programs, size=224, stages=False, paste=None):
     """The input of a batch of decoded frames (co3d_2d/src/data/loader.py: `collate_images`), on the current stream: the three
     rounds of the AugMix chains (`mink_img_chain_round`) and the fused crop / resize / ColorJitter / flip / PCA / Normalize / mix
     tail (`mink_img_finish`).  packed: uint8 [n_bytes] on the device, the HWC RGB images one after the other; offsets int64 [B+1]
     (bytes), sizes int32 [B,2] = (w, h) and programs float64 [B, MINK_IMG_PARAMS] (co3d_2d/src/data/transforms.py:
     `compile_program`) as HOST arrays or CPU tensors: they are checked here and copied.  Nothing is read back.
+    paste: None, or {"fg": uint8 vector on the device, the packed frames to paste, "mask": uint8 vector on the device, their mask
+    planes, "table": HOST int64 [B, MINK_PASTE_PARAMS]} (`image_paste_check`): before the chains run, `mink_img_paste` composites
+    every pasting sample over its slot, so `packed` IS MODIFIED: such a slot holds the background on entry and the composite after.
     Returns float32 [B,3,size,size]; with `stages=True` also uint8 [B, width+1, size, size, 3], every branch after its flip."""
     from .._lib import check, lib
 
@@ -533,6 +562,16 @@ def prepare_image_batch(packed, offsets, sizes, programs, size=224, stages=False
     host = [v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v) for v in (offsets, sizes, programs)]
     offs, szs, progs = host[0].astype(np.int64), host[1].astype(np.int32), np.ascontiguousarray(host[2], np.float64)
     B, width = image_batch_check(offs, szs, progs, packed.numel())
+    if paste is not None:
+        fg, mask = paste["fg"], paste["mask"]
+        for v in (fg, mask):
+            if not (torch.is_tensor(v) and v.device == packed.device and v.dtype == torch.uint8 and v.dim() == 1 and v.is_contiguous()):
+                raise TypeError("prepare_image_batch: paste['fg'] and paste['mask'] are contiguous uint8 vectors on the device of `packed`")
+        if not packed.is_contiguous():
+            raise TypeError("prepare_image_batch: the paste writes into `packed`, which must be contiguous")
+        tab = paste["table"]
+        tab = np.ascontiguousarray(tab.detach().cpu().numpy() if torch.is_tensor(tab) else tab)
+        paste_extent = image_paste_check(tab, szs, fg.numel(), mask.numel())
     dev, S = packed.device, int(size)
     out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
     st = torch.empty(B, width + 1, S, S, 3, dtype=torch.uint8, device=dev) if stages else None
@@ -548,6 +587,10 @@ def prepare_image_batch(packed, offsets, sizes, programs, size=224, stages=False
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
     from .._lib import constants
 
+    if paste is not None and paste_extent[0] > 0:  # (no sample pastes: no upload, no launch)
+        d_tab = up(tab)
+        check(L.mink_img_paste(packed.data_ptr(), d_offs.data_ptr(), d_szs.data_ptr(), n_pix, B, fg.data_ptr(), fg.numel(),
+                               mask.data_ptr(), mask.numel(), d_tab.data_ptr(), paste_extent[0], paste_extent[1], stream))
     I = constants("MINK_IMG_")
     depth = 0
     for k in range(1, width + 1):
