@@ -243,7 +243,8 @@ int mink_class_partition_batch(int32_t n_maps, const MinkClassPartitionDesc *des
  *                        re-uses the forward table: nbr_t[i][k] == nbr[i][K-1-k])
  *   nbr[n_out][K]      : neighbour table;  y[n_out][ldy] receives cout columns.  (cin == 28, the flattened-K
  *                        stem path: taken only when n_in < 2^24 - 1 -- its rows are addressed with a 24-bit
- *                        multiply; larger inputs take the general path.)
+ *                        multiply -- and the table has fewer than 2^32 bytes (4 n_out K: it is read through a
+ *                        32-bit buffer descriptor); larger inputs and tables take the general path.)
  *   bias[cout] or NULL
  *   row_perm/n_virtual : optional row permutation (NULL/0 = identity): tile row v computes
  *                        output row row_perm[v], -1 entries are padding (mink_class_partition)
@@ -357,7 +358,11 @@ int mink_conv_gather_gemm_stats(const float *x, int64_t n_in, int32_t ldx, int32
 
 /* Weight gradient dW[k] = X[nbr[.][k]]^T @ dY, split over row blocks and reduced
  * deterministically (no atomics).  x has n_in rows (every nbr entry is -1 or in [0, n_in)).
- * workspace >= mink_conv_wgrad_workspace_bytes(). */
+ * workspace >= mink_conv_wgrad_workspace_bytes().
+ * The tiled kernels read x, dy and the table through 32-bit buffer offsets only when each has fewer than 2^31 bytes,
+ * n_in < 2^24, and the "no neighbour" offset those kernels form -- the low 32 bits of 0xFFFFFF * 4 ldx -- lies at or
+ * beyond the end of x (for ldx > 64 that product wraps: ldx = 68 puts it at 2^28 - 272); any other call takes the
+ * 64-bit addressed instantiation.  Which one: mink_conv_wgrad_launch_info. */
 int64_t mink_conv_wgrad_workspace_bytes(int64_t n_out, int32_t K, int32_t cin, int32_t cout);
 int mink_conv_wgrad(const float *x, int64_t n_in, int32_t ldx, int32_t cin, const float *dy, int32_t ldy,
                     int32_t cout, const int32_t *nbr, int64_t n_out, int32_t K, float *dw, void *workspace,

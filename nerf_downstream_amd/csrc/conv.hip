@@ -1907,9 +1907,11 @@ static GatherPlan plan_gather(const GatherCall &c, const ConvKnobs &kn) {
       pl.trace = kn.trace_buf && (int64_t)pl.grid.x * pl.grid.y * pl.grid.z <= kn.trace_cap;
     }
   } else if (vec) {
-    // the flat path addresses x rows with a 24-bit multiply: the table must not name a row >= 2^24 - 1 (n_in bounds it)
+    // the flat path addresses x rows with a 24-bit multiply: the table must not name a row >= 2^24 - 1 (n_in bounds it); and it
+    // reads the table through a buffer descriptor, whose size and byte offsets (4 n_out K, 4 row K) are 32-bit: n_out K < 2^31
+    // alone leaves tables of up to 2^33 bytes, whose rows past byte 2^32 it would read 2^32 bytes early
     const bool flat = c.cin == 28 && zs == 1 && !c.flip && !c.w_transposed && !c.perm && kn.flat && c.ldx <= 32 &&
-                      4ll * c.K * c.cin * c.cout < (1ll << 31) && c.n_in < (1 << 24) - 1;
+                      4ll * c.K * c.cin * c.cout < (1ll << 31) && c.n_in < (1 << 24) - 1 && 4ll * c.n_out * c.K < (1ll << 32);
     pl.family = MINK_KERNEL_GATHER2;
     pl.targ[0] = c.w_transposed, pl.targ[1] = c.perm, pl.targ[2] = flat ? 28 : 0, pl.targ[3] = kn.math == 1 ? 1 : kn.math == 3 ? 3 : 0;
   } else {  // operands that are not 16-byte rows (e.g. 27 channels)

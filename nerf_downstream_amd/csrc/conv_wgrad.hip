@@ -1007,6 +1007,14 @@ static WgradPlan wgrad_plan(const WgradCall &c, const ConvKnobs &kn) {
   const int64_t xb = esz * c.n_in * c.ldx, db = esz * n_out * c.ldy, nb = 4 * n_out * K;
   pl.x_bytes = (unsigned)xb, pl.dy_bytes = (unsigned)db, pl.nbr_bytes = (unsigned)nb;
   pl.buf_ok = xb < (1ll << 31) && db < (1ll << 31) && nb < (1ll << 31) && c.n_in < (1 << 24) && xb <= 0xFFFFFFll * 4 * c.ldx;
+  // "No neighbour" is row 0xFFFFFF, and the kernels form its byte offset as the low 32 bits of 0xFFFFFF * 4 ldx (__umul24):
+  // with ldx > 64 the product passes 2^32 and the offset the load sees is the wrapped one -- 2^26 (ldx mod 64) - 4 ldx, e.g.
+  // 2^28 - 272 at ldx = 68 -- which lies INSIDE an x of more bytes than that: a tile's padding pairs then multiply real rows
+  // of x instead of zeros.  The 64-bit comparison above does not see the wrap; on top of it, the offset as the kernel computes
+  // it must lie at or beyond the end of x for every column of a row (+ 4 cin without passing 2^32), and so must that offset
+  // with the "column past the width" bit 31 added.
+  const uint32_t none32 = (uint32_t)(0xFFFFFFull * 4ull * (uint64_t)c.ldx);
+  pl.buf_ok = pl.buf_ok && (int64_t)none32 >= xb && (int64_t)none32 + 4ll * cin <= (1ll << 32) && (int64_t)(uint32_t)(none32 + 0x80000000u) >= xb;
   const bool stream_ok = K == 27 && cin <= 32 && c.ldx < 64 && c.n_in < (1 << 24) && 4 * c.n_in * c.ldx < (1ll << 31) &&
                          4 * n_out * c.ldy < (1ll << 31) && 4 * n_out * K < (1ll << 31);  // what the buffer-offset arithmetic assumes
   pl.streaming = pl.G == 9 && stream_ok && kn.wgrad_stream;
