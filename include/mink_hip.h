@@ -808,6 +808,45 @@ int mink_prune_gather(const float *x, int32_t ldx, int64_t n_in, int32_t C, cons
 int mink_prune_gather_bwd(const float *dy, int32_t ldy, int64_t n_out, int32_t C, const int32_t *old2new, int64_t n_in, float *dx,
                           int32_t lddx, void *stream);
 
+/* ------------------------------------------------------------------ union of tensors on different maps (csrc/union.hip)
+ * ME.MinkowskiUnion: the map of the union of k coordinate lists and the sum of the inputs over it (the skip of a U-shaped
+ * completion net).  Conventions of the generative section above: int32 coordinate rows (b, x, y, z), 16-byte aligned; fp32
+ * feature rows with a row pitch, 16-byte lanes when C % 4 == 0 and every pitch and pointer allows, dword lanes otherwise;
+ * -1 = absent; no float atomics, no kernel waits for memory that another workgroup of the same launch writes, and no entry
+ * point synchronises with the host. */
+/* The most inputs of one union: the length of the host arrays below, not a tuning number. */
+#define MINK_UNION_MAX_INPUTS 8
+/* Rows one workgroup of mink_union_build's compaction owns: row counts next to its multiples are where it can go wrong. */
+#define MINK_UNION_BLOCK 256
+/* The union of k coordinate lists (2 <= k <= MINK_UNION_MAX_INPUTS), all at one tensor stride: list i holds n_host[i] >= 1
+ * UNIQUE rows coords[i][n_i][4] with a non-decreasing batch column in [0, B) and its batch offsets batch_offsets[i][B + 1] on
+ * the device; coords, batch_offsets and in2out are HOST arrays of k device pointers; sum n_i < 2^31.
+ * Row order [ME-recall: ME's own union order is unpinned, ME is absent; this is the definition]: sample-major; inside a sample
+ * the rows of input 0 in their order, then the rows of input 1 that no earlier input holds, in their order, and so on.
+ *   out_coords[sum n_i][4]  : first *total rows: the union
+ *   in2out[i][n_i]          : the union row of every row of input i (-1 only for a row the contract above excludes)
+ *   out2in[k][out2in_pitch] : first *total entries of row i: the row of input i behind union row u, -1 = input i lacks it;
+ *                             out2in_pitch >= sum n_i.  Entries and rows of out_coords past *total are not written.
+ *   out_batch_offsets[B + 1]: row ranges of the samples in the union; a sample empty in every input has an empty range,
+ *                             out_batch_offsets[B] = *total
+ *   total                   : device int32
+ * A hash of all sum n_i rows on the packed 64-bit keys, the first occurrence in (input, row) order winning its slot as in
+ * mink_coords_unique, then counts per MINK_UNION_BLOCK positions, one workgroup scanning the counts, the scatter, the rows
+ * that lost, the offsets: separate launches through `workspace` (mink_union_workspace_bytes, 8-byte aligned; -1 and an
+ * error text for counts mink_union_build refuses). */
+int64_t mink_union_workspace_bytes(int32_t k, const int64_t *n_host, int32_t B);
+int mink_union_build(int32_t k, const int32_t *const *coords, const int32_t *const *batch_offsets, const int64_t *n_host, int32_t B,
+                     int32_t *out_coords, int32_t *const *in2out, int32_t *out2in, int64_t out2in_pitch, int32_t *out_batch_offsets,
+                     int32_t *total, void *workspace, int64_t workspace_bytes, void *stream);
+/* y[u][:] = the sum over the inputs that hold union row u (out2in[i][u] >= 0), u < n_out, taken in ascending input index: the
+ * first one present is copied -- a row held by one input comes out bit for bit, -0.0 included -- and the later ones are added
+ * to it in fp32, so the result is a pure function of the inputs; NaN and infinities reach only the union rows their input
+ * row maps to.  x and ldx_host / n_host are host arrays of k device pointers / row pitches / row counts; pad columns of y are
+ * not written; n_out == 0 returns without a launch.  Backward: dx_i[r][:] = dy[in2out[i][r]][:], which is mink_prune_gather
+ * with kept = in2out[i]. */
+int mink_union_sum(int32_t k, const float *const *x, const int32_t *ldx_host, const int64_t *n_host, int32_t C, const int32_t *out2in,
+                   int64_t out2in_pitch, int64_t n_out, float *y, int32_t ldy, void *stream);
+
 /* ------------------------------------------------------------------ elementwise (csrc/elementwise.hip) */
 /* Elementwise: mode 0: y = max(x,0); mode 1: dx = (y>0) ? dy : 0 (a=dy,b=y);
  * mode 2: y = a + b. */

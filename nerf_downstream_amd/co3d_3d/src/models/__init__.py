@@ -6,7 +6,7 @@ from .mink.resnet import ResNet14, ResNet18, ResNet34, ResNet50, ResNet101
 
 from .mink import res16unet as _unet
 from .mink import resunet as _resunet
-from .mink.completion import CompletionNet
+from .mink.completion import CompletionNet, CompletionUNet
 from .mink.dgcnn import DGCNN_cls
 from .mink.fcnn import MinkowskiFCNN, MinkowskiSplatFCNN
 from .mink.paconv import PAConvDGCNN, PAConvPointNet
@@ -19,6 +19,7 @@ MODELS.update({n: c for n, c in vars(_resunet).items()  # registration feature e
                if n.startswith("ResUNet") and isinstance(c, type) and c.NORM_TYPE is not None})
 MODELS.update({c.__name__: c for c in (MinkowskiFCNN, MinkowskiSplatFCNN, MinkowskiPointNet, DGCNN_cls, PAConvPointNet, PAConvDGCNN)})  # point-based classifiers
 MODELS[CompletionNet.__name__] = CompletionNet  # sparse occupancy autoencoder: generative transpose -> classifier -> pruning
+MODELS[CompletionUNet.__name__] = CompletionUNet  # its U-shaped form: every decoder block joins the encoder tensor of its stride (MinkowskiUnion)
 
 
 @gin.configurable

@@ -3,7 +3,7 @@
 data/utils.py:1), backed by hand-written HIP kernels for gfx950 (libmink_hip.so)."""
 import enum
 
-from . import MinkowskiFunctional, MinkowskiOps, eltwise, field, generative, graph, head, norm, paconv, pool, streams, utils  # noqa: F401
+from . import MinkowskiFunctional, MinkowskiOps, eltwise, field, generative, graph, head, norm, paconv, pool, streams, union, utils  # noqa: F401
 from .coords import CoordinateManager, CoordinateMapKey  # noqa: F401
 from .modules import (  # noqa: F401
     MinkowskiAvgPooling,
@@ -34,6 +34,7 @@ from .modules import (  # noqa: F401
     cat,
 )
 from .generative import MinkowskiGenerativeConvolutionTranspose, MinkowskiPruning  # noqa: F401
+from .union import MinkowskiUnion  # noqa: F401
 from .functional import attention, attention_b16, seg_cross_entropy, set_conv_math, set_conv_storage, slice_rows  # noqa: F401
 from .tensor import SparseTensor, TensorField  # noqa: F401
 
